@@ -16,6 +16,12 @@ exchange is one RCCL all-gather of the ranks' best joint vectors, inside the tim
     python bench.py --gpus N ...      # without WORLD_SIZE in the environment: starts the N ranks itself (same launcher)
 
 The number of ranks that took part is checked against --gpus on every rank and reported as "ranks_seen"; a mismatch is an error.
+
+A plain run sets up, warms up, times the K steps and prints the result line (the roofline block is derived from the timed
+steps' own kernel events and the committed profiles, no extra pass).  --full adds the passes after the timed region: the
+unshared-layers rate, the end-to-end figure and the CPU baseline with its parity check (each can still be left out with its
+--no-* option).  --dump-outputs DIR writes what the last timed step hands its caller (rank 0's per-candidate errors, the best
+joint vector(s), the argmin index and error) as float64 .npy files; the inputs are seeded, so two builds compare file for file.
 """
 import argparse
 import json
@@ -156,6 +162,13 @@ def end_to_end(device, n_frames=4096):
                         "frames in host memory when the clock starts, angles back in host memory when it stops"}
 
 
+def dump_outputs(out_dir, err, best_joints, best_index, best_error):
+    """--dump-outputs: the last timed step's results as float64 .npy files (at most 65 535 rows of errors: 0.5 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (('errors', err), ('best_joints', best_joints), ('best_index', [best_index]), ('best_error', [best_error])):
+        np.save(os.path.join(out_dir, name + '.npy'), np.asarray(a, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -180,6 +193,11 @@ def main():
                     help="skip the end-to-end figure (N = 1 only, after the timed region): 256 synthetic 640x480 frames through "
                          "Predictor.run_many — preparation, upload, lookup and every stage in lockstep batches")
     ap.add_argument('--backend', default='nccl', help="'nccl' (RCCL over xGMI); 'gloo' only to rehearse N>1 on a one-GPU box")
+    ap.add_argument('--full', action='store_true',
+                    help="after the timed region also measure unshared_value, end_to_end and cpu_baseline (minus those turned off "
+                         "by --no-unshared / --no-end-to-end / --no-cpu-baseline); a plain run prints the headline only")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's results (errors, best_joints, best_index, best_error) to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -304,10 +322,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        if use_dist and not args.split_candidates:
+            joints = torch.stack(gathered).cpu().numpy()        # every rank's best joint vector, in rank order
+        elif use_dist:
+            joints = g[order[0], :6]
+        else:
+            joints = cand[bi]
+        dump_outputs(args.dump_outputs, e.download(want_err=True)[0], joints, bi, be)
+
     # outside the timed region: the same candidates with nothing shared between them (six links drawn per candidate) —
     # the rate a caller sees when no two candidates agree in their first two joint angles
     kern_u = None
-    if not args.no_unshared:
+    if args.full and not args.no_unshared:
         e.set_strategy(e.NO_LAYERS)
         e.eval_resident(6, loss)
         kern_u = e.profile_eval(6, loss, None, reps=max(2, min(args.steps, 5)))
@@ -380,9 +407,9 @@ def main():
                          "other_kernels_ms": {"fk_mvp+bounds": kern['fk'], "finalize+argmin": kern['finalize'],
                                               "pass_total": kern['total']}},
         }
-        if not args.no_end_to_end and world == 1 and args.workload == 'cfg1':
+        if args.full and not args.no_end_to_end and world == 1 and args.workload == 'cfg1':
             out["end_to_end"] = end_to_end(device)
-        if not args.no_cpu_baseline and world == 1:           # reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:           # reported at N=1 only
             gpu_err = e.download(want_err=True)[0]                 # errors of the last timed pass, outside the timed region
             out["cpu_baseline"] = cpu_baseline(robot, PV, W, H, ZNEAR, ZFAR, cand, tq, min(args.cpu_sample, C), gpu_err, loss, flags)
         print(json.dumps(out))

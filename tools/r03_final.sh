@@ -12,9 +12,9 @@ if [ "$1" == "frames" ]; then      # second call (the two together exceed one gp
     cat $OUT/frames_batch.txt $OUT/prof_batch.txt
     exit 0
 fi
-python bench.py --steps 20 --warmup 3 > $OUT/BENCH_r03.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
-python bench.py --steps 10 --warmup 2 --loss full --no-cpu-baseline --no-end-to-end > $OUT/BENCH_r03_fullloss.json 2>> $OUT/bench.err
-python bench.py --steps 5 --warmup 1 --workload cfg5 --no-cpu-baseline > $OUT/BENCH_r03_cfg5.json 2>> $OUT/bench.err
+python bench.py --steps 20 --warmup 3 --full > $OUT/BENCH_r03.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+python bench.py --steps 10 --warmup 2 --loss full --full --no-cpu-baseline --no-end-to-end > $OUT/BENCH_r03_fullloss.json 2>> $OUT/bench.err
+python bench.py --steps 5 --warmup 1 --workload cfg5 --full --no-cpu-baseline > $OUT/BENCH_r03_cfg5.json 2>> $OUT/bench.err
 timeout -k 10 300 tools/valu_issue_bench.bin > $OUT/r03_valu_issue.json 2> $OUT/valu.err
 ROPE_HIP_LIB=$ROOT/rope_s3d_amd/csrc/librope_hip_profile.so timeout -k 10 200 python tools/kernel_clock.py > $OUT/r03_kernel_clock.json 2> $OUT/clock.err
 timeout -k 10 600 bash tools/rocprof_bench.sh r03 > $OUT/rocprof_r03.log 2>&1 || { tail -5 $OUT/rocprof_r03.log; exit 1; }
