@@ -235,6 +235,8 @@ typedef struct rope_stage {
     double range;             /* InterpolativeSweep: rad about the current angle, NaN = the whole joint range */
 } rope_stage;
 
+typedef void (*rope_eval_hook)(void *user, int32_t stage, int32_t n_render, const double *rows, int32_t n_rows);
+
 typedef struct rope_predict_args {
     const rope_stage *stages;
     int32_t n_stages;
@@ -255,6 +257,10 @@ typedef struct rope_predict_args {
                                      `angles = self.lookup_angles[argmin]` (a numpy view, predict.py:171) followed by
                                      `angles[idx] += rate` (predict.py:212-215) does in the reference.  Results then depend on
                                      the order of the frames: one context, frames in sequence. */
+    rope_eval_hook on_eval;       /* NULL: nothing.  Else called after every scored batch of a stage (not the Lookup grid) with the
+                                     stage's index, its links drawn and the rows in the order they were scored (a viewer shows the
+                                     poses the stages looked at).  Must not call back into the context.  rope_predict only. */
+    void *on_eval_user;           /* handed to on_eval as `user` */
 } rope_predict_args;
 
 /*   angles_out  6 doubles
@@ -293,7 +299,8 @@ int rope_stage_targets(rope_ctx *ctx, int n_frames, const uint64_t *tq, const fl
 int rope_commit_targets(rope_ctx *ctx);
 
 /* rope_predict for the n_frames resident targets of rope_set_targets, in lockstep: the same stage list, limits and camera for all of
- * them (args as rope_predict; lookup_angles_live must be NULL — the table aliasing makes frames depend on their order).  A frame
+ * them (args as rope_predict; lookup_angles_live must be NULL — the table aliasing makes frames depend on their order — and so must
+ * on_eval).  A frame
  * that leaves a Descent stage early simply contributes no rows to the later batches of that stage.  Every frame's angles and trace
  * are those of rope_predict on that frame alone.
  *   angles_out  n_frames x 6;  trace_out  n_frames x n_stages x 6 or NULL;  n_evals  total poses rendered and scored, or NULL */

@@ -32,7 +32,7 @@ def _mask(letters):
 
 def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue, joint_limits, camera_pose,
                       lookup_angles, lookup_crop, do_angles='SLU', min_ang_inc=None, stages=None, seg_masks=None,
-                      lookup_depth=None, lookup_live=None):
+                      lookup_depth=None, lookup_live=None, evaluated=None):
     """-> (final angles, trace [(stage kind, angles after it)], number of E(a) evaluations).
 
     Synthetic mode (default): masks are read from `tgt_blue` as _loadSynthetic does.  Segmentation mode:
@@ -44,7 +44,10 @@ def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue,
     `angles[idx] += rate` (predict.py:212-215) then edits the table in place until some stage rebinds `angles`.
     Pass the same (n, 6) float64 array for every frame of a sequence and this function does exactly that with it
     (the scores keep coming from `lookup_angles`: the reference's depth table is rendered once from the untouched grid).
-    None: every frame starts from a copy of the grid row."""
+    None: every frame starts from a copy of the grid row.
+
+    `evaluated`: a list that receives (links drawn, pose) of every pose rendered after the Lookup grid, in the order
+    rendered (the reference's preview shows exactly those, predict.py:153-157)."""
     min_ang_inc = np.array([.005] * 6) if min_ang_inc is None else np.asarray(min_ang_inc, float)
     tgt_depth = np.asarray(tgt_depth, np.float64)
     H, W = tgt_depth.shape
@@ -78,6 +81,8 @@ def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue,
 
     def E(n, a):                                       # render_at_pos + _error (predict.py:159-161,475-509)
         count[0] += 1
+        if evaluated is not None:
+            evaluated.append((n, a.copy()))
         key = o.raster_key(a, n)
         return float(o.finalize(o.sums(key, orc.LOSS_FULL, n, tq), orc.LOSS_FULL, n, n_pix, flags))
 
@@ -200,6 +205,8 @@ def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue,
                     space = np.linspace(lo, hi, div)
                     score = np.empty(div)
                     for i, a_ in enumerate(space):
+                        if evaluated is not None:
+                            evaluated.append((n, a_.copy()))
                         key = o.raster_key(a_, n)
                         score[i] = o.finalize(o.sums(key, orc.LOSS_TSWEEP, n, None, t_full), orc.LOSS_TSWEEP, n, n_pix, flags)
                     count[0] += div

@@ -47,6 +47,7 @@ struct Machine {
     const rope_predict_args &a;
     const bool batch;                                           // rows go to the resident targets of rope_set_targets
     int64_t evals = 0;
+    int32_t stage = 0;                                          // index of the running stage (on_eval)
     Machine(rope_ctx *ctx, const rope_predict_args &args, bool many) : c(ctx), a(args), batch(many) {}
     std::vector<Vec6> rows;                                     // the step's rows of all frames ...
     std::vector<int32_t> frame_of;                              // ... and the frame each belongs to
@@ -63,7 +64,9 @@ struct Machine {
         if (rows.empty()) return ROPE_OK;
         evals += (int64_t)rows.size();
         if (batch) return rope_eval_targets(c, rows[0].data(), frame_of.data(), (int)rows.size(), n_render, loss, nullptr, err.data());
-        return rope_eval(c, rows[0].data(), (int)rows.size(), n_render, loss, nullptr, err.data(), nullptr, nullptr, nullptr);
+        const int rc = rope_eval(c, rows[0].data(), (int)rows.size(), n_render, loss, nullptr, err.data(), nullptr, nullptr, nullptr);
+        if (rc == ROPE_OK && a.on_eval) a.on_eval(a.on_eval_user, stage, n_render, rows[0].data(), (int32_t)rows.size());
+        return rc;
     }
 };
 
@@ -471,6 +474,7 @@ int run_stages(rope_ctx *c, const rope_predict_args *a, bool batch, int B, doubl
     if (!a->stages || a->n_stages < 1) return fail("rope_predict: no stages");
     if (!a->limits || !a->camera_pose || !a->min_ang_inc) return fail("rope_predict: limits, camera_pose and min_ang_inc are required");
     if (batch && a->lookup_angles_live) return fail("rope_predict_batch: the reference's table aliasing makes frames depend on their order (lookup_angles_live must be NULL)");
+    if (batch && a->on_eval) return fail("rope_predict_batch: on_eval is for one frame (rope_predict); it must be NULL");
     if (B < 1) return fail("rope_predict_batch: no frames");
     for (int i = 0; i < a->n_stages; i++) {
         const rope_stage &s = a->stages[i];
@@ -502,6 +506,7 @@ int run_stages(rope_ctx *c, const rope_predict_args *a, bool batch, int B, doubl
         int rc = ROPE_OK;
         static const char *const names[] = {"rope:stage:Lookup", "rope:stage:Descent", "rope:stage:SFlip", "rope:stage:InterpolativeSweep", "rope:stage:TensorSweep"};
         rope_range_push(names[s.kind]);
+        m.stage = i;
         switch (s.kind) {
         case ROPE_STAGE_LOOKUP: rc = stage_lookup(m, s, sts); break;
         case ROPE_STAGE_DESCENT: rc = stage_descent(m, s, sts); break;

@@ -37,12 +37,15 @@ class StageDesc(C.Structure):
                 ('init_rate', C.c_double * 6), ('rate_reduction', C.c_double), ('early_stop', C.c_double), ('range', C.c_double)]
 
 
+EvalHook = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32)     # rope_eval_hook
+
+
 class PredictArgs(C.Structure):
     """rope_predict_args (include/rope_s3d.h)."""
     _fields_ = [('stages', C.POINTER(StageDesc)), ('n_stages', C.c_int32), ('speculate', C.c_int32),
                 ('limits', C.c_void_p), ('camera_pose', C.c_void_p), ('min_ang_inc', C.c_void_p),
                 ('lookup_angles', C.c_void_p), ('n_lookup', C.c_int32), ('use_table', C.c_int32), ('lookup_crop', C.c_void_p),
-                ('lookup_angles_live', C.c_void_p)]
+                ('lookup_angles_live', C.c_void_p), ('on_eval', EvalHook), ('on_eval_user', C.c_void_p)]
 
 
 class EngineUnavailable(RuntimeError):
@@ -467,10 +470,14 @@ class Engine:
         return scores, int(bi.value), float(be.value)
 
     def predict(self, stages, limits, camera_pose, min_ang_inc, lookup_angles=None, lookup_crop=None, use_table=False,
-                speculate: int = 3, lookup_live: np.ndarray = None):
-        """rope_predict: the whole stage machine of one frame in one call.  `stages` = StageDesc array (or list).
-        -> (angles (6,), trace (n_stages, 6), candidate poses evaluated)."""
+                speculate: int = 3, lookup_live: np.ndarray = None, on_eval=None):
+        """rope_predict: the whole stage machine of one frame in one call.  `stages` = StageDesc array (or list).  `on_eval`:
+        callable(stage index, n_render, rows (R, 6)) after every scored batch of a stage, handed a copy of the rows (on_eval of
+        rope_predict_args; it must not use this engine).  -> (angles (6,), trace (n_stages, 6), candidate poses evaluated)."""
         a, keep = self._predict_args(stages, limits, camera_pose, min_ang_inc, lookup_angles, lookup_crop, use_table, speculate, lookup_live)
+        if on_eval is not None:
+            hook = EvalHook(lambda _, stage, n_render, rows, n: on_eval(stage, n_render, np.ctypeslib.as_array(rows, (n, 6)).copy()))
+            a.on_eval = hook                            # `hook` lives until the call returns
         out, trace, n = np.empty(6), np.empty((a.n_stages, 6)), C.c_int64()
         self._check(self._lib.rope_predict(self._ctx, C.byref(a), _p(out), _p(trace), C.byref(n)), 'rope_predict')
         return out, trace, int(n.value)

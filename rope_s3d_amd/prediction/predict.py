@@ -2,14 +2,13 @@
 
 `Predictor` keeps the reference's constructor and `run` signature
 (robotpose/prediction/predict.py:37-48,127,375) so predict_dataset.py / predict_live.py /
-SyntheticPredictor call it unchanged.  The stage machine below follows the reference's
-control flow decision for decision (quirks included, each cited where it appears); what
-changes is how a candidate is evaluated: every `render_at_pos` + `_error` pair of the
-reference (predict.py:159-161,475-509) becomes one row of a batch handed to the HIP
-engine, which does FK, rasterisation and the error reduction on the device.
+SyntheticPredictor call it unchanged.  The stage machine runs in the library (rope_predict,
+csrc/rope_predict.cpp) and follows the reference's control flow decision for decision,
+quirks included; what changes is how a candidate is evaluated: every `render_at_pos` +
+`_error` pair of the reference (predict.py:159-161,475-509) becomes one row of a batch
+handed to the HIP engine, which does FK, rasterisation and the error reduction on the device.
 """
 import os
-import warnings
 from dataclasses import dataclass
 from typing import Callable, Optional
 
@@ -18,8 +17,8 @@ import numpy as np
 from ..config import Paths
 from ..constants import DEFAULT_CAMERA_POSE, DEFAULT_RENDER_COLORS, LOOKUP_JOINTS, LOOKUP_NUM_RENDERED
 from ..crop import Crop
-from ..engine import (LOSS_FULL, LOSS_LOOKUP, LOSS_TSWEEP, STAGE_DESCENT, STAGE_ISWEEP, STAGE_LOOKUP, STAGE_SFLIP, STAGE_TSWEEP, StageDesc,
-                      pack_target, prepare_segmented, prepare_synthetic)
+from ..engine import (STAGE_DESCENT, STAGE_ISWEEP, STAGE_LOOKUP, STAGE_SFLIP, STAGE_TSWEEP, StageDesc, pack_target, prepare_segmented,
+                      prepare_synthetic)
 from ..imgproc import dilate, erode, resize_linear
 from ..projection import Intrinsics
 from ..simulation.lookup import RobotLookupManager
@@ -87,6 +86,19 @@ def segment_targets(seg: dict, target_depth: np.ndarray, lookup_links) -> np.nda
     return lookup_depth
 
 
+def preview_rows(sflip: bool, rows: np.ndarray, limits: np.ndarray) -> np.ndarray:
+    """The poses the reference renders for one scored batch of a stage (rope_predict's on_eval), in its order: the rows
+    themselves, and in an SFlip batch also the pose the reference renders at the lower limit only to overwrite its error
+    (predict.py:270-277), which the library does not ask for.  The library's SFlip batch is [angles, flipped (in limits),
+    upper endpoint (out of or within 0.15 of a limit)]: the last row's S angle is the upper limit exactly when the endpoint
+    branch ran (a last row that is the flipped pose lies at least 0.15 inside it), and the lower endpoint goes before it."""
+    if not sflip or rows[-1][0] != limits[0][1]:
+        return rows
+    lower = rows[-1].copy()
+    lower[0] = limits[0][0]
+    return np.vstack([rows[:-1], lower, rows[-1:]])
+
+
 class _BatchTraces:
     """Per-stage traces of a lockstep batch, frame by frame, as run() keeps them for one frame: entry f is
     [(stage name, angles after the stage), ...].  Built when asked for — a batch of 512 frames is 4 600 small arrays."""
@@ -112,7 +124,6 @@ class Predictor:
     SPECULATE_BATCH = 1     # the same for a lockstep batch of SPECULATE_BATCH_FROM frames or more: with hundreds of frames in every device
     SPECULATE_BATCH_FROM = 16   # batch the GPU is full anyway, and the reference's own order — one joint's under/over pair at a time, 2 rows
                             # per frame instead of 26 — renders a third of the poses (5 550 against 3 220 frames/s at the defaults)
-    NATIVE = True      # run the stage loop in librope_hip.so (rope_predict); False: the Python loop below, same decisions
     NATIVE_PREPARE = True   # synthetic path: prepare() as one pass in the library (rope_prepare_synthetic); False: the numpy steps, same arrays
     BATCH = None       # run_many: frames that walk the stage list in lockstep, every step one device batch over all of them
                        # (rope_predict_batch).  None: as many as fit BATCH_BYTES of target planes, 16..1024 (1024 at 160x90,
@@ -232,7 +243,8 @@ class Predictor:
                              "Please define in rope_s3d_amd/prediction/stages.py.")
 
     def _native_stages(self):
-        """self.stages as rope_stage descriptors (include/rope_s3d.h), or None when a stage has no native form."""
+        """self.stages as rope_stage descriptors (include/rope_s3d.h).  ValueError for a stage the reference could not run
+        either (a cubic through fewer than 4 sweep samples, predict.py:310; a TensorSweep without samples)."""
         nan = float('nan')
         out = (StageDesc * len(self.stages))()
         for d, stage in zip(out, self.stages):
@@ -249,14 +261,18 @@ class Predictor:
                 d.kind, d.to_render, d.count = STAGE_DESCENT, stage.to_render, stage.its
                 d.init_rate[:] = [nan if r is None else float(r) for r in stage.init_rate]
                 d.rate_reduction, d.early_stop = stage.rate_redux, stage.early_stop
-            elif type(stage) is InterpolativeSweep and stage.divs >= 4:
+            elif type(stage) is InterpolativeSweep:
+                if stage.divs < 4:
+                    raise ValueError(f"InterpolativeSweep needs at least 4 divisions, got {stage.divs}")
                 d.kind, d.to_render, d.count = STAGE_ISWEEP, stage.to_render, stage.divs
                 d.range = nan if stage.range is None else float(stage.range)
-            elif type(stage) is TensorSweep and stage.divs >= 1:
+            elif type(stage) is TensorSweep:
+                if stage.divs < 1:
+                    raise ValueError(f"TensorSweep needs at least 1 division, got {stage.divs}")
                 d.kind, d.to_render, d.count = STAGE_TSWEEP, stage.to_render, stage.divs
                 d.range = nan if stage.range is None else float(stage.range)
             else:
-                return None
+                raise ValueError(f"no stage kind of the library for {type(stage).__name__}")
         return out
 
     def _has_tsweep(self) -> bool:
@@ -301,9 +317,10 @@ class Predictor:
 
     def _install(self, prep: PreparedTarget):
         """The frame's target into HBM; from here on the stages score against it."""
-        self._tgt_depth, self._lookup_depth_f32, self._target_masks = prep.tgt_depth, prep.lookup_f32, prep.target_masks
-        self._tq, self._flags, self._preview_links = prep.tq, prep.flags, prep.links_image
+        self._target = prep
         self.engine.set_target(prep.tq, prep.lookup_f32, prep.flags)
+        if self._has_tsweep():          # TensorSweep compares against the whole target depth, not the lookup plane (predict.py:363)
+            self.engine.set_target_tsweep(np.ascontiguousarray(prep.tgt_depth, dtype=np.float32))
 
     def _segmentLoad(self, target_color, target_depth):
         """Segmentation path (predict.py:415-442).  NB: like the reference, zeroes target_depth in place."""
@@ -431,8 +448,9 @@ class Predictor:
         return pool[key]
 
     def _batch_ok(self) -> bool:
-        """The current stage list can walk many frames in lockstep (rope_predict_batch)."""
-        return self.NATIVE and not self.preview and not self.reference_table_aliasing and self._native_stages() is not None
+        """Frames may walk the stage list in lockstep (rope_predict_batch): one preview frame per pose, and the table aliasing,
+        need them one at a time."""
+        return not self.preview and not self.reference_table_aliasing
 
     def _run_planes(self, tq, lookup_f32, flags, tsweep=None) -> np.ndarray:
         """run_batch on the frames' stacked target planes: (B,H,W) uint64, (B,H,W) float32, (B,8) uint8 [, (B,H,W) float32]."""
@@ -561,20 +579,11 @@ class Predictor:
                 out[i] = self.run(None, None, pose(i), prepared=prep)
         return out
 
-    # ------------------------------------------------------------------ evaluation
-    def _errors(self, n_render: int, candidates: np.ndarray) -> list:
-        """Predictor._error of every candidate row (predict.py:475-509), as Python floats."""
-        cand = np.asarray(candidates, dtype=np.float64).reshape(-1, 6)
-        err, _, _, _ = self.engine.eval(cand, n_render, LOSS_FULL)
-        self.evaluations += len(cand)
-        if self.preview:
-            self._show(n_render, cand)
-        return [float(e) for e in err]
-
-    def _show(self, n_render: int, cand: np.ndarray):
-        """preview_if_applicable (predict.py:153-157): one preview frame per evaluated pose."""
+    # ------------------------------------------------------------------ preview
+    def _show(self, stage: int, n_render: int, rows: np.ndarray):
+        """preview_if_applicable (predict.py:153-157): one preview frame per pose a stage evaluated, in the reference's order."""
         self.renderer.setMaxParts(n_render)
-        for q in cand:
+        for q in preview_rows(type(self.stages[stage]) is SFlip, rows, self.u_reader.joint_limits):
             self.renderer.setJointAngles(q)
             color, depth = self.renderer.render()
             self.viz.loadRenderedColor(color)
@@ -591,220 +600,23 @@ class Predictor:
 
     # ------------------------------------------------------------------ the state machine
     def run(self, target_color, target_depth, camera_pose=None, *, prepared: PreparedTarget = None):
+        """One frame through the stage list (rope_predict).  With preview, every pose the stages evaluated is shown afterwards,
+        in the order they were scored: rendering inside the library's callback would re-enter the engine it holds."""
         if camera_pose is not None and np.any(np.asarray(camera_pose) != self.camera_pose):
             self.changeCameraPose(camera_pose)
-
+        self._setStages()
+        stages = self._native_stages()
         self._install(prepared if prepared is not None else self.prepare(target_color, target_depth))
         if self.preview:
             self.viz.loadTargetColor(target_color)
-            self.viz.loadTargetDepth(self._tgt_depth)
-            self.viz.loadSegmentedLinks(self._preview_links)
-
-        limits = self.u_reader.joint_limits
-        lr = np.ones(6) * 0.1
-        history = np.zeros((self.history_length, 6))
-        err_history = np.zeros(self.history_length)
-        angles = np.array([0] * 6, dtype=float)
-        self._setStages()
-        self.trace = []
-        native = self._native_stages() if (self.NATIVE and not self.preview) else None
-        if native is not None:
-            if self._has_tsweep():          # TensorSweep compares against the whole target depth, not the lookup plane (predict.py:363)
-                self.engine.set_target_tsweep(np.ascontiguousarray(self._tgt_depth, dtype=np.float32))
-            angles, trace, n = self.engine.predict(native, limits, self.camera_pose, self.min_ang_inc, self.lookup_angles,
-                                                   self.lookup_crop, self._lookup_table, self.SPECULATE, self._lookup_live)
-            self.evaluations += n
-            self.trace = [(type(stage).__name__, trace[i].copy()) for i, stage in enumerate(self.stages)]
-            return angles
-
-        for stage in self.stages:
-            if type(stage) is Lookup:
-                angles = self._stage_lookup()
-            elif type(stage) is Descent:
-                angles, lr = self._stage_descent(stage, angles, lr, history, err_history, limits)
-            elif type(stage) is SFlip:
-                angles = self._stage_sflip(stage, angles, limits)
-            elif type(stage) is InterpolativeSweep:
-                angles = self._stage_isweep(stage, angles, history, err_history, limits)
-            elif type(stage) is TensorSweep:
-                angles = self._stage_tsweep(stage, angles, limits)
-            self.trace.append((type(stage).__name__, np.array(angles, dtype=float)))
-        return angles
-
-    def _stage_lookup(self):
-        """argmin over the pose grid of mean|T - sqrt(D_k)| * std|T - sqrt(D_k)| on the crop, T not
-        sqrt-ed (predict.py:165-171).  The grid is rendered and scored on the device."""
-        if self._lookup_table:
-            _, best, _ = self.engine.lookup_score()               # stream the stored table (HBM-bound)
-        else:
-            _, _, best, _ = self.engine.eval(self.lookup_angles, LOOKUP_NUM_RENDERED, LOSS_LOOKUP, crop=self.lookup_crop)
-        self.evaluations += len(self.lookup_angles)
-        # The reference returns a row VIEW of its angle table (predict.py:171), which the Descent stage then edits in
-        # place (predict.py:213), so its table drifts from frame to frame.  By default frames stay independent here
-        # (.copy(); DESIGN.md §6) — on a fresh Predictor both agree; reference_table_aliasing=True hands out the view of
-        # the live table, and the stages below then behave as the reference's do (in-place steps, rebinding elsewhere).
-        if self._lookup_live is not None:
-            return self._lookup_live[best]
-        return self.lookup_angles[best].copy()
-
-    def _stage_descent(self, stage, angles, lr, history, err_history, limits):
-        for i in range(6):                                         # predict.py:175-177
-            if stage.init_rate[i] is not None:
-                lr[i] = stage.init_rate[i]
-        n = stage.to_render
-        over_err = under_err = np.inf
-        joints = [int(j) for j in np.where(stage.joints)[0]]
-        with np.errstate(all='ignore'):
-            for _ in range(stage.its):
-                # Learning rates of the whole iteration first: a joint's rate depends on its own angle and on the
-                # history, and neither changes before that joint's turn (predict.py:184-187).
-                for idx in joints:
-                    if abs(np.mean(history, 0)[idx] - angles[idx]) <= lr[idx]:
-                        lr[idx] *= stage.rate_redux
-                    lr = np.max((lr, self.min_ang_inc), 0)
-                # The reference evaluates under/over of one joint, decides, moves on: 2 renders at a time, each waiting
-                # for the last.  Here up to SPECULATE joints go out as ONE batch holding the under/over pair of every
-                # state the earlier decisions can lead to (+lr, -lr, stay: 2, 6, 18 rows); the decisions are then read
-                # off the results in the reference's order.  Rows are independent, so the path taken sees the same bits.
-                for g in range(0, len(joints), self.SPECULATE):
-                    group = joints[g:g + self.SPECULATE]
-                    frontier, rows, index = [angles.copy()], [], {}
-                    for level, idx in enumerate(group):
-                        nxt = []
-                        for k, state in enumerate(frontier):
-                            under = state.copy()
-                            under[idx] -= lr[idx]
-                            over = under.copy()
-                            over[idx] += 2 * lr[idx]
-                            for tag, cand in (('u', under), ('o', over)):
-                                if limits[idx][0] <= cand[idx] <= limits[idx][1]:
-                                    index[(level, k, tag)] = len(rows)
-                                    rows.append(cand)
-                            if level + 1 < len(group):
-                                up, down = state.copy(), state.copy()
-                                up[idx] += lr[idx]
-                                down[idx] -= lr[idx]
-                                nxt += [up, down, state]
-                        frontier = nxt
-                    errs = self._errors(n, np.array(rows)) if rows else []
-                    k = 0
-                    for level, idx in enumerate(group):
-                        under_err = errs[index[(level, k, 'u')]] if (level, k, 'u') in index else np.inf
-                        over_err = errs[index[(level, k, 'o')]] if (level, k, 'o') in index else np.inf
-                        if over_err < under_err:                    # ties and NaN: stay (predict.py:212-215)
-                            angles[idx] += lr[idx]
-                            k = 3 * k
-                        elif over_err > under_err:
-                            angles[idx] -= lr[idx]
-                            k = 3 * k + 1
-                        else:
-                            k = 3 * k + 2
-
-                history[1:] = history[:-1]
-                history[0] = angles
-                err_history[1:] = err_history[:-1]
-                err_history[0] = min(over_err, under_err)           # of the LAST joint only (predict.py:222)
-                if abs(np.mean(err_history) - err_history[0]) / err_history[0] < stage.early_stop:
-                    break
-                spread = history.max(0) - history.min(0)
-                if ((spread <= self.min_ang_inc) + np.isclose(spread, self.min_ang_inc)).all():
-                    break
-                if (history[:3] == history[0]).all():
-                    break
-        return angles, lr
-
-    def _stage_sflip(self, stage, angles, limits):
-        n = stage.to_render
-        temp = angles.copy()
-        cam = self.camera_pose
-        a = cam[5] * np.abs(np.cos(cam[3])) + cam[4] * np.abs(np.sin(cam[3]))     # predict.py:245
-        temp[0] = -temp[0] + 2 * a * np.sign(temp[0])
-        limit_thresh = 0.15
-        close_to_limits = limit_thresh > abs(limits[0, 0] - temp[0]) or limit_thresh > abs(limits[0, 1] - temp[0])
-        in_limits = limits[0, 0] <= temp[0] <= limits[0, 1]
-        # every pose this stage can ask for is known before the first answer: one batch of up to three rows
-        rows = [angles.copy()]
-        if in_limits:
-            rows.append(temp.copy())
-        if not in_limits or close_to_limits:
-            endpoint = temp.copy()
-            if self.preview:                                        # the reference renders the lower limit too, only to
-                endpoint[0] = limits[0][0]                          # overwrite its error (below); shown, never compared
-                rows.append(endpoint.copy())
-            endpoint[0] = limits[0][1]
-            rows.append(endpoint)
-        errs = self._errors(n, np.array(rows))
-        base_err = errs[0]
-        if in_limits:
-            err = errs[1]
-            if err < base_err:
-                angles = temp                                       # alias, as predict.py:261
-                base_err = err
-        if not in_limits or close_to_limits:
-            # predict.py:270-277: both endpoints are written into temp, but the comparison sits after
-            # the loop, so only the upper limit's error is ever used — and when the flip above was
-            # accepted, `angles` IS `temp`, so angles[0] becomes the upper limit regardless.
-            temp[0] = limits[0][1]
-            err = errs[-1]
-            if err < base_err:
-                angles = temp
-                base_err = err
-        return angles
-
-    def _sweep_space(self, stage, angles, idx, limits):
-        lo, hi = angles.copy(), angles.copy()
-        if stage.range is None:
-            lo[idx], hi[idx] = limits[idx, 0], limits[idx, 1]
-        else:
-            lo[idx] = max(lo[idx] - stage.range, limits[idx, 0])
-            hi[idx] = min(hi[idx] + stage.range, limits[idx, 1])
-        return lo, hi, np.linspace(lo, hi, stage.divs)
-
-    def _stage_isweep(self, stage, angles, history, err_history, limits):
-        n, div = stage.to_render, stage.divs
-        base_err = None                                             # not refreshed between joints (predict.py:288-289)
-        for idx in np.where(stage.joints)[0]:
-            lo, hi, space = self._sweep_space(stage, angles, idx, limits)
-            if base_err is None:                                    # the base pose rides along with the first sweep
-                space_err = self._errors(n, np.vstack([angles[None], space]))
-                base_err = space_err.pop(0)
-            else:
-                space_err = self._errors(n, space)
-            x = np.linspace(lo[idx], hi[idx], div * 5)
-            with np.errstate(all='ignore'):
-                predicted = cubic_interp(space[:, idx], np.array(space_err), x)
-            angs = angles.copy()
-            angs[idx] = x[predicted.argmin()]
-            pred_min_err = self._errors(n, angs)[0]
-
-            errs = [base_err, min(space_err), pred_min_err]
-            min_type = errs.index(min(errs))                        # ties go to the earlier entry
-            if min_type == 1:
-                angles = space[space_err.index(min(space_err))]
-                err_history[1:] = err_history[:-1]
-                err_history[0] = min(space_err)
-            elif min_type == 2:
-                angles = angs
-                err_history[1:] = err_history[:-1]
-                err_history[0] = pred_min_err
-            history[1:] = history[:-1]
-            history[0] = angles
-        return angles
-
-    def _stage_tsweep(self, stage, angles, limits):
-        """TensorSweep (predict.py:340-373): whole frame, sqrt of both depths, and the `*-` typo that
-        turns the score into mean * -std, so argmin picks the LARGEST mean*std."""
-        n = stage.to_render
-        full = np.ascontiguousarray(self._tgt_depth, dtype=np.float32)
-        self.engine.set_target(self._tq, full, self._flags)
-        try:
-            for idx in np.where(stage.joints)[0]:
-                _, _, space = self._sweep_space(stage, angles, idx, limits)
-                _, _, best, _ = self.engine.eval(space, n, LOSS_TSWEEP)
-                self.evaluations += len(space)
-                if self.preview:
-                    self._show(n, space)
-                angles = space[best]
-        finally:
-            self.engine.set_target(self._tq, self._lookup_depth_f32, self._flags)
+            self.viz.loadTargetDepth(self._target.tgt_depth)
+            self.viz.loadSegmentedLinks(self._target.links_image)
+        evaluated = []
+        angles, trace, n = self.engine.predict(stages, self.u_reader.joint_limits, self.camera_pose, self.min_ang_inc, self.lookup_angles,
+                                               self.lookup_crop, self._lookup_table, self.SPECULATE, self._lookup_live,
+                                               on_eval=(lambda *batch: evaluated.append(batch)) if self.preview else None)
+        self.evaluations += n
+        self.trace = [(type(stage).__name__, trace[i].copy()) for i, stage in enumerate(self.stages)]
+        for batch in evaluated:
+            self._show(*batch)
         return angles

@@ -247,38 +247,58 @@ def test_run_many_with_camera_poses_that_change_between_groups():
 
 def test_predict_batch_segmentation_path_and_tensor_sweep():
     """The segmentation path's targets (instance merge, dilate 8 / erode 7 body mask) through the batch, and a stage list with
-    TensorSweep stages natively (ROPE_STAGE_TSWEEP): both equal the Python stage loop frame by frame."""
+    TensorSweep stages natively (ROPE_STAGE_TSWEEP): both equal rope_predict frame by frame, and the sequential restatement of
+    the reference on the first frames."""
     from rope_s3d_amd import Predictor, SyntheticPredictor
     from rope_s3d_amd.prediction import predict as predict_mod
+    from rope_s3d_amd.prediction.predict import segment_targets
     from rope_s3d_amd.prediction.stages import Descent, InterpolativeSweep, Lookup, SFlip, TensorSweep
     from rope_s3d_amd.segmentation import ColorSegmenter
     rb = helpers.robot()
     lim = rb.joint_limits
+    names = rb.link_names
     sp = SyntheticPredictor(DEFAULT_CAMERA_POSE, '640_480_color', 4, 'SLU', noise=False, seed=6, lookup_divisions=4)
     frames = _frames(sp.renderer, lim, 12, 1234)
     colors, depths = [f[1] for f in frames], [f[2].astype(np.float64) for f in frames]
-    p = Predictor(DEFAULT_CAMERA_POSE, 4, base_intrin='640_480_color', segmenter=ColorSegmenter(['BG'] + rb.link_names, split_instances=True),
-                  lookup_divisions=4)
+    intr, PV = helpers.camera('640_480_color', ds=4, as_predictor=True)
+    o = helpers.make_oracle(rb, intr, PV)
+    grid = helpers.slu_grid(lim, 4)
+
+    def same_as_reference(p, i, label, **kw):
+        with np.errstate(all='ignore'):
+            want, trace, _ = predictor_ref.predict_reference(o, kw.pop('tgt'), kw.pop('blue', None), names, kw.pop('link_blue', {}), lim,
+                                                             DEFAULT_CAMERA_POSE, grid, p.lookup_crop, 'SLU', **kw)
+        assert len(trace) == len(p.trace)
+        for (k_ref, a_ref), (k_got, a_got) in zip(trace, p.trace):
+            assert np.array_equal(a_ref, a_got), f"{label}, frame {i}, stage {k_got}: {a_got} vs reference {a_ref}"
+        assert np.array_equal(want, p.trace[-1][1])
+
+    seg_fn = ColorSegmenter(['BG'] + names, split_instances=True)
+    p = Predictor(DEFAULT_CAMERA_POSE, 4, base_intrin='640_480_color', segmenter=seg_fn, lookup_divisions=4)
     got = p.run_many(colors, [d.copy() for d in depths])
-    p.NATIVE = False
     for i in range(len(frames)):
         assert np.array_equal(_bits(p.run(colors[i], depths[i].copy())), _bits(got[i])), f"segmentation path, frame {i}"
+        if i < 3:
+            seg = Predictor._reorganize_by_link(p, seg_fn(resize_linear(colors[i], intr.width, intr.height)))
+            tgt = resize_linear(depths[i], intr.width, intr.height)
+            lookup = segment_targets(seg, tgt, names)
+            same_as_reference(p, i, "segmentation path", tgt=tgt, seg_masks={k: v['mask'] for k, v in seg.items()}, lookup_depth=lookup)
     # a custom stage list with TensorSweep stages
     custom = [Lookup(), SFlip(4), TensorSweep(6, 12, 'U'), Descent(4, 6, 'SL', [0.05, 0.05, 0.1, 0.5, 0.5, 0.5], early_stop=0.1),
               TensorSweep(4, 9, 'SL', range=0.2), InterpolativeSweep(6, 10, 'U', 0.1)]
+    ref_stages = [('lookup',), ('sflip', 4), ('tsweep', 6, 12, 'U', None), ('descent', 4, 6, 'SL', [0.05, 0.05, 0.1, 0.5, 0.5, 0.5], 0.5, 0.1),
+                  ('tsweep', 4, 9, 'SL', 0.2), ('isweep', 6, 10, 'U', 0.1)]
     orig = predict_mod.getStages
     predict_mod.getStages = lambda angs: custom
     try:
         q = sp.predictor
-        q.NATIVE = True
-        assert q._setStages() is None and q._native_stages() is not None
+        assert q._setStages() is None and [d.kind for d in q._native_stages()] == [0, 2, 4, 1, 4, 3]
         got = q.run_many(colors, depths)
-        native_single = [q.run(colors[i], depths[i]) for i in range(len(frames))]
-        q.NATIVE = False
+        link_blue = {nm: int(LINK_BLUE[i]) for i, nm in enumerate(names)}
         for i in range(len(frames)):
-            want = q.run(colors[i], depths[i])
-            assert np.array_equal(_bits(want), _bits(got[i])), f"tensor sweep list, frame {i} (batch)"
-            assert np.array_equal(_bits(want), _bits(native_single[i])), f"tensor sweep list, frame {i} (rope_predict)"
+            assert np.array_equal(_bits(q.run(colors[i], depths[i])), _bits(got[i])), f"tensor sweep list, frame {i}"
+            if i < 3:
+                same_as_reference(q, i, "tensor sweep list", tgt=resize_linear(depths[i], intr.width, intr.height),
+                                  blue=resize_linear(colors[i], intr.width, intr.height)[..., 0], link_blue=link_blue, stages=ref_stages)
     finally:
         predict_mod.getStages = orig
-        sp.predictor.NATIVE = True

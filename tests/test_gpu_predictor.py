@@ -101,8 +101,8 @@ def test_segmentation_path_trace_matches_reference(synth, fseed):
             from oracle import oracle as orc
             tq_ref = orc.pack_target(tgt, sum((np.asarray(seg[n]['mask'], np.uint64) << np.uint64(l)) for l, n in enumerate(rb.link_names) if n in seg))
             print("engine errors n=4:", p.engine.eval(rows, 4, 1)[0], " n=6:", p.engine.eval(rows, 6, 1)[0])
-            print("oracle errors n=4:", o.eval(rows, 1, 4, tq_ref, link_flags=p._flags, threads=4), " n=6:", o.eval(rows, 1, 6, tq_ref, link_flags=p._flags, threads=4))
-            print("target planes equal:", np.array_equal(tq_ref, p._tq), "flags", p._flags)
+            print("oracle errors n=4:", o.eval(rows, 1, 4, tq_ref, link_flags=p._target.flags, threads=4), " n=6:", o.eval(rows, 1, 6, tq_ref, link_flags=p._target.flags, threads=4))
+            print("target planes equal:", np.array_equal(tq_ref, p._target.tq), "flags", p._target.flags)
         assert np.array_equal(a_ref, a_got), f"stage {i} {k_got}: {a_got} vs reference {a_ref}"
     assert np.array_equal(got, want)
     if fseed == 123:
@@ -297,8 +297,8 @@ def test_other_robot_as_active_urdf():
 
 def test_preview_shows_the_reference_render_sequence(synth, tmp_path):
     """preview=True (ProjectionViz, predict.py:153-157,510-602): same angles as without it, one preview frame per
-    pose the reference's serial loop renders (== the oracle's evaluation count minus the lookup), and a video file
-    holding exactly those frames."""
+    pose the reference's serial loop renders, those poses in its order (the oracle's evaluations after the lookup),
+    and a video file holding exactly those frames."""
     from rope_s3d_amd import Predictor
     p0 = synth.predictor
     rb = helpers.robot()
@@ -311,6 +311,10 @@ def test_preview_shows_the_reference_render_sequence(synth, tmp_path):
     video = tmp_path / 'preview.avi'
     p = Predictor(DEFAULT_CAMERA_POSE, 4, True, str(video), 'SLU', base_intrin='640_480_color',
                   color_dict=p0.color_dict, lookup_divisions=4)
+    shown, parts = [], [None]
+    set_parts, set_angles = p.renderer.setMaxParts, p.renderer.setJointAngles
+    p.renderer.setMaxParts = lambda n: (parts.__setitem__(0, n), set_parts(n))[1]
+    p.renderer.setJointAngles = lambda q: (shown.append((parts[0], np.array(q, float))), set_angles(q))[1]
     got = p.run(color, depth)
     assert np.array_equal(got, want)
 
@@ -319,10 +323,14 @@ def test_preview_shows_the_reference_render_sequence(synth, tmp_path):
     tgt_depth = resize_linear(depth, intr.width, intr.height).astype(np.float64)
     tgt_blue = resize_linear(color, intr.width, intr.height)[..., 0]
     names = rb.link_names
+    evaluated = []
     _, _, n_eval = predictor_ref.predict_reference(
         o, tgt_depth, tgt_blue, names, {n: int(LINK_BLUE[i]) for i, n in enumerate(names)}, lim, DEFAULT_CAMERA_POSE,
-        helpers.slu_grid(lim, 4), p.lookup_crop, 'SLU')
+        helpers.slu_grid(lim, 4), p.lookup_crop, 'SLU', evaluated=evaluated)
     assert p.viz.shown == n_eval - len(p.lookup_angles)             # the lookup stage renders nothing per frame
+    assert len(shown) == len(evaluated) == p.viz.shown
+    for i, ((n_got, q_got), (n_ref, q_ref)) in enumerate(zip(shown, evaluated)):
+        assert n_got == n_ref and np.array_equal(q_got, q_ref), (i, n_got, q_got, n_ref, q_ref)
     frame = p.viz.frame
     assert frame.shape == (720, 1280, 3) and frame[:360, 640:].any() and frame[360:, :640].any()
     p.viz.close()
@@ -332,31 +340,59 @@ def test_preview_shows_the_reference_render_sequence(synth, tmp_path):
 
 
 @pytest.mark.parametrize('do_angles', ['SLU', 'SL'])
-def test_native_stage_machine_matches_python_loop(do_angles):
-    """rope_predict (the stage loop in librope_hip.so) against Predictor's Python loop on the same frames: same angles
-    after every stage, same number of poses evaluated — with the reference's serial descent order and with the
-    speculative batches."""
+def test_native_stage_machine_matches_the_reference(do_angles):
+    """rope_predict (the stage loop in librope_hip.so) against the sequential restatement of the reference on the same frames,
+    with the reference's serial descent order and with the speculative batches: same angles after every stage.  Serially it
+    evaluates exactly the reference's poses in its order (its on_eval log, with the lower-limit renders SFlip throws away put back
+    as the preview does); the speculative batches evaluate those poses among others."""
     from rope_s3d_amd import SyntheticPredictor
+    from rope_s3d_amd.prediction.predict import preview_rows
+    from rope_s3d_amd.prediction.stages import SFlip
     sp = SyntheticPredictor(DEFAULT_CAMERA_POSE, '640_480_color', 4, do_angles, noise=False, seed=3, lookup_divisions=5)
     p = sp.predictor
-    lim = helpers.robot().joint_limits
-    for seed in range(int(os.environ.get('ROPE_NATIVE_SEEDS', '6'))):
-        q = np.random.default_rng(1000 + seed).uniform(lim[:, 0], lim[:, 1]) * np.array([1, 1, 1, 0, 0, 0])
-        sp.renderer.setJointAngles(q)
-        color, depth = sp.renderer.render()
-        runs = {}
-        for native, spec in ((True, 3), (False, 3), (True, 1), (False, 1)):
-            p.NATIVE, p.SPECULATE, p.evaluations = native, spec, 0
-            got = p.run(color, depth)
-            runs[(native, spec)] = (got, [t[1] for t in p.trace], [t[0] for t in p.trace], p.evaluations)
-        p.NATIVE, p.SPECULATE = True, 3
-        for spec in (3, 1):
-            a, b = runs[(True, spec)], runs[(False, spec)]
-            assert a[2] == b[2]
-            for k, (ta, tb) in enumerate(zip(a[1], b[1])):
-                assert np.array_equal(ta, tb), (seed, spec, k, a[2][k], ta, tb)
-            assert np.array_equal(a[0], b[0]) and a[3] == b[3]
-        assert np.array_equal(runs[(True, 3)][0], runs[(True, 1)][0])
+    rb = helpers.robot()
+    lim = rb.joint_limits
+    names = rb.link_names
+    link_blue = {n: int(LINK_BLUE[i]) for i, n in enumerate(names)}
+    intr, PV = helpers.camera('640_480_color', ds=4, as_predictor=True)
+    o = helpers.make_oracle(rb, intr, PV)
+    log = []
+    predict = p.engine.predict
+    p.engine.predict = lambda *a, **k: predict(*a, **{**k, 'on_eval': lambda stage, n_render, rows: log.append((stage, n_render, rows))})
+    try:
+        for seed in range(int(os.environ.get('ROPE_NATIVE_SEEDS', '6'))):
+            q = np.random.default_rng(1000 + seed).uniform(lim[:, 0], lim[:, 1]) * np.array([1, 1, 1, 0, 0, 0])
+            sp.renderer.setJointAngles(q)
+            color, depth = sp.renderer.render()
+            tgt_depth = resize_linear(depth, intr.width, intr.height).astype(np.float64)
+            tgt_blue = resize_linear(color, intr.width, intr.height)[..., 0]
+            evaluated = []
+            with np.errstate(all='ignore'):
+                want, trace, n_eval = predictor_ref.predict_reference(o, tgt_depth, tgt_blue, names, link_blue, lim, DEFAULT_CAMERA_POSE,
+                                                                      p.lookup_angles, p.lookup_crop, do_angles, evaluated=evaluated)
+            runs = {}
+            for spec in (3, 1):
+                p.SPECULATE, p.evaluations = spec, 0
+                log.clear()
+                got = p.run(color, depth)
+                assert len(trace) == len(p.trace)
+                for k, ((k_ref, a_ref), (k_got, a_got)) in enumerate(zip(trace, p.trace)):
+                    assert np.array_equal(a_ref, a_got), (seed, spec, k, k_got, a_got, a_ref)
+                assert np.array_equal(got, want)
+                runs[spec] = got, [(n, r) for stage, n, rows in log for r in rows], p.evaluations
+                if spec == 1:
+                    shown = [(n, r) for stage, n, rows in log for r in preview_rows(type(p.stages[stage]) is SFlip, rows, lim)]
+                    assert len(shown) == len(evaluated) == n_eval - len(p.lookup_angles)
+                    for i, ((n_got, q_got), (n_ref, q_ref)) in enumerate(zip(shown, evaluated)):
+                        assert n_got == n_ref and np.array_equal(q_got, q_ref), (seed, i, n_got, q_got, n_ref, q_ref)
+                    # evaluations: the reference's renders less the lower-limit ones SFlip throws away
+                    assert p.evaluations == n_eval - (len(shown) - len(runs[1][1]))
+            spec3 = {(n, r.tobytes()) for n, r in runs[3][1]}
+            assert all((n, r.tobytes()) in spec3 for n, r in runs[1][1]), seed
+            assert np.array_equal(runs[3][0], runs[1][0])
+    finally:
+        p.SPECULATE = 3
+        del p.engine.predict
 
 
 def test_native_stage_machine_argument_errors(synth):
@@ -476,11 +512,10 @@ def test_predictor_pool_equals_one_predictor(synth):
     assert np.array_equal(pool.run_many(colors, depths), want)
 
 
-@pytest.mark.parametrize('native', [True, False])
-def test_reference_table_aliasing_over_a_sequence(synth, native):
+def test_reference_table_aliasing_over_a_sequence(synth):
     """Predictor(reference_table_aliasing=True): the reference's drifting angle table (predict.py:171,212-215) over five
-    frames of an arm that barely moves — stage by stage against the restatement that lets numpy do the aliasing, with the
-    stage loop in the library and in Python; frame 1 equals the default mode, later frames start from drifted rows."""
+    frames of an arm that barely moves — stage by stage against the restatement that lets numpy do the aliasing; frame 1
+    equals the default mode, later frames start from drifted rows."""
     from rope_s3d_amd import Predictor
     rb = helpers.robot()
     lim = rb.joint_limits
@@ -488,7 +523,6 @@ def test_reference_table_aliasing_over_a_sequence(synth, native):
     link_blue = {n: int(LINK_BLUE[i]) for i, n in enumerate(names)}
     kw = dict(base_intrin='640_480_color', color_dict=synth.predictor.color_dict, lookup_divisions=4)
     p = Predictor(DEFAULT_CAMERA_POSE, 4, reference_table_aliasing=True, **kw)
-    p.NATIVE = native
     q = Predictor(DEFAULT_CAMERA_POSE, 4, **kw)                        # default: independent frames
     intr, PV = helpers.camera('640_480_color', ds=4, as_predictor=True)
     o = helpers.make_oracle(rb, intr, PV)

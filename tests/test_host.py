@@ -121,6 +121,19 @@ def test_stage_lists():
     assert st.getStages('SLUB') is None and st.getStages('SLURB') is None
 
 
+@pytest.mark.parametrize('stage,text', [(st.InterpolativeSweep(6, 3, 'U'), 'InterpolativeSweep needs at least 4 divisions'),
+                                        (st.TensorSweep(6, 0, 'U'), 'TensorSweep needs at least 1 division')])
+def test_stage_lists_the_library_cannot_run_are_refused(stage, text):
+    """A cubic through fewer than 4 sweep samples (scipy's interp1d refuses it too) or a TensorSweep without samples: ValueError
+    up front.  _native_stages reads only self.stages, so a stand-in object serves (a Predictor needs the GPU)."""
+    from types import SimpleNamespace
+    from rope_s3d_amd.prediction.predict import Predictor
+    ok = Predictor._native_stages(SimpleNamespace(stages=st.getStages('SLU')))
+    assert [d.kind for d in ok] == [0, 2, 1, 2, 3, 2, 2, 3, 1]
+    with pytest.raises(ValueError, match=text):
+        Predictor._native_stages(SimpleNamespace(stages=[st.Lookup(), stage]))
+
+
 def test_lookup_grid_order_and_size_rule():
     lim = URDFReader().joint_limits
     g = lookup_grid(lim, 'SLU', [3, 2, 2, 0, 0, 0])

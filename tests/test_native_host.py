@@ -12,7 +12,8 @@ from oracle import oracle as orc
 from oracle import predictor_ref
 from rope_s3d_amd.constants import DEFAULT_CAMERA_POSE, LINK_BLUE
 from rope_s3d_amd.crop import crop_pose_grid
-from rope_s3d_amd.engine import STAGE_DESCENT, STAGE_ISWEEP, STAGE_LOOKUP, STAGE_SFLIP, PredictArgs, StageDesc
+from rope_s3d_amd.engine import STAGE_DESCENT, STAGE_ISWEEP, STAGE_LOOKUP, STAGE_SFLIP, EvalHook, PredictArgs, StageDesc
+from rope_s3d_amd.prediction.predict import preview_rows
 
 import helpers
 
@@ -71,9 +72,10 @@ def test_stage_loop_against_sequential_reference(shim, do_angles, seed, speculat
     r, c = np.where(cover)
     crop = np.array([max(r.min() - 10, 0), min(r.max() + 10, intr.height - 1), max(c.min() - 10, 0), min(c.max() + 10, intr.width - 1)], np.int32)
     names = rb.link_names
+    evaluated = []
     want, trace, n_eval = predictor_ref.predict_reference(o, tgt, blue, names, {n: int(LINK_BLUE[i]) for i, n in enumerate(names)}, lim,
-                                                          pose, grid, crop, do_angles)
-    calls = []
+                                                          pose, grid, crop, do_angles, evaluated=evaluated)
+    calls, scored = [], []
 
     @C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32))
     def answer(cand, n, n_render, loss, crop_p, err_out, best_idx):
@@ -82,6 +84,7 @@ def test_stage_loop_against_sequential_reference(shim, do_angles, seed, speculat
         if loss == orc.LOSS_LOOKUP:
             err = o.eval(rows, loss, n_render, tq, t32, np.ctypeslib.as_array(crop_p, (4,)), flags, threads=THREADS)
         else:
+            scored.append(rows)
             err = o.eval(rows, loss, n_render, tq, link_flags=flags, threads=THREADS)
         if err_out:
             np.ctypeslib.as_array(err_out, (n,))[:] = err
@@ -89,11 +92,16 @@ def test_stage_loop_against_sequential_reference(shim, do_angles, seed, speculat
             best_idx[0] = int(np.argmin(np.where(np.isnan(err), np.inf, err)))
         return 0
     shim.shim_set_callback(answer)
+    logged = []
+
+    @EvalHook
+    def on_eval(user, stage, n_render, rows, n):
+        logged.append((stage, n_render, np.ctypeslib.as_array(rows, (n, 6)).copy()))
     stages = _stages(do_angles)
     arr = (StageDesc * len(stages))(*stages)
     limits, cam, inc = np.ascontiguousarray(lim, np.float64), np.asarray(pose, np.float64), np.array([.005] * 6)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    args = PredictArgs(arr, len(arr), speculate, p(limits), p(cam), p(inc), p(grid), len(grid), 0, p(crop))
+    args = PredictArgs(arr, len(arr), speculate, p(limits), p(cam), p(inc), p(grid), len(grid), 0, p(crop), None, on_eval)
     out, got_trace, n = np.empty(6), np.empty((len(arr), 6)), C.c_int64()
     rc = shim.rope_predict(C.c_void_p(1), C.byref(args), p(out), p(got_trace), C.byref(n))
     assert rc == 0, shim.shim_last_error()
@@ -101,9 +109,17 @@ def test_stage_loop_against_sequential_reference(shim, do_angles, seed, speculat
     for k, (kind, ang) in enumerate(trace):
         assert np.array_equal(got_trace[k], ang), (k, kind, got_trace[k], ang)
     assert np.array_equal(out, want)
+    # on_eval sees every batch scored after the lookup grid, in order, with the index and links drawn of its stage
+    assert np.array_equal(np.concatenate([rows for _, _, rows in logged]), np.concatenate(scored))
+    assert all(n_render == stages[k].to_render and stages[k].kind != STAGE_LOOKUP for k, n_render, _ in logged)
+    assert [k for k, _, _ in logged] == sorted(k for k, _, _ in logged) and n.value == len(grid) + len(np.concatenate(scored))
     if speculate == 1:
-        # the serial order asks for exactly the reference's renders, minus the lower-limit render SFlip throws away
-        assert n_eval - 4 <= n.value <= n_eval
+        # the serial order asks for exactly the reference's renders, minus the lower-limit render SFlip throws away, which the
+        # preview puts back
+        shown = [(n_render, q) for k, n_render, rows in logged for q in preview_rows(stages[k].kind == STAGE_SFLIP, rows, lim)]
+        assert len(shown) == len(evaluated) == n_eval - len(grid)
+        for i, ((n_got, q_got), (n_ref, q_ref)) in enumerate(zip(shown, evaluated)):
+            assert n_got == n_ref and np.array_equal(q_got.view(np.uint64), q_ref.view(np.uint64)), (i, n_got, q_got, n_ref, q_ref)
     assert calls[0] == len(grid) and max(calls[1:]) <= 26          # the lookup grid, then batches of at most 1 + 25 poses
     assert shim.shim_ranges_opened() >= len(stages) and shim.shim_range_depth() == 0      # one named range per stage, all closed
 
@@ -218,6 +234,12 @@ def test_argument_checks_without_an_engine(shim):
         args = PredictArgs(arr, 1, 3, p(lim), p(cam), p(inc), None, 0, 0, None)
         assert shim.rope_predict(C.c_void_p(1), C.byref(args), p(out), None, None) == -1
         assert text in shim.shim_last_error()
+    # on_eval reports the batches of one frame: refused for a batch of frames
+    arr = (StageDesc * 1)(StageDesc(STAGE_SFLIP, 4))
+    args = PredictArgs(arr, 1, 3, p(lim), p(cam), p(inc), None, 0, 0, None, None, EvalHook(lambda *_: None))
+    shim.rope_predict_batch.argtypes = [C.c_void_p, C.POINTER(PredictArgs), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    assert shim.rope_predict_batch(C.c_void_p(1), C.byref(args), 1, p(out), None, None) == -1
+    assert b'on_eval' in shim.shim_last_error()
 
 
 def test_stage_loop_with_nan_errors_follows_the_reference(shim):
