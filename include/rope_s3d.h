@@ -185,8 +185,23 @@ int rope_lookup_build(rope_ctx *ctx, const double *cand, int C, int n_render, co
 int rope_lookup_score(rope_ctx *ctx, double *scores_out, int32_t *best_idx, double *best_score);
 
 /* One pose to images.  Replaces Renderer.setJointAngles + Renderer.render (render.py:88-98).
- *   depth H x W float32 metres (0 = empty), ids H x W uint8 link id (255 = background) */
+ *   depth H x W float32 metres (0 = empty), ids H x W uint8 link id (255 = background)
+ * rope_render_batch with N = 1, PV = NULL and crop = NULL. */
 int rope_render(rope_ctx *ctx, const double *q, int n_render, float *depth, uint8_t *ids);
+
+/* N poses to images in one device batch.  Replaces N x (Renderer.setJointAngles [+ setCameraPose] + render)
+ * (render.py:88-111) and the render loops of DatasetRenderer.render_at / RobotLookupCreator._generate_depth_array
+ * (render.py:175-183, lookup.py:69-86).
+ *   q      N x 6 joint vectors
+ *   PV     N x 16 row-major P·V per pose (rope_camera_matrix), or NULL = the camera of rope_set_camera
+ *   crop   {r0, r1, c0, c1} inclusive, or NULL = whole frame; planes are (r1-r0+1) x (c1-c0+1)
+ *   depth  N planes float32 metres (0 = empty) or NULL;  ids  N planes uint8 (255 = background) or NULL
+ * Image size, znear / zfar and the context's own camera are those of rope_set_camera, which this call leaves as they are.
+ * Rows go to the device in chunks (at most 65 535 poses, output planes within a fixed device budget), each chunk's planes
+ * copied out before the next one is drawn.  Like rope_eval_views it uses the per-candidate buffers: resident candidates and
+ * the results of the last evaluation are gone afterwards. */
+int rope_render_batch(rope_ctx *ctx, const double *q, const double *PV, int N, int n_render, const int32_t *crop,
+                      float *depth, uint8_t *ids);
 
 /* OR over candidates of "pixel covered" (H x W uint8 0/1).  Replaces the depth-sum loop
  * of Crop._create (crop.py:60-81). */

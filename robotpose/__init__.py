@@ -3,3 +3,4 @@ reference) and `from robotpose import Predictor, JSONCoupling, LiveCamera, Datas
 resolve to the MI355X engine's host package."""
 from rope_s3d_amd import Dataset, Grapher, Intrinsics, Paths, Predictor, Renderer, SyntheticPredictor  # noqa: F401
 from rope_s3d_amd.prediction.feed import JSONCoupling, LiveCamera  # noqa: F401
+from rope_s3d_amd.simulation import DatasetRenderer  # noqa: F401

@@ -190,10 +190,12 @@ struct rope_ctx {
     float *d_t32ts = nullptr;
     bool have_t32ts = false;
 
-    // single-pose render scratch
-    uint32_t *d_key = nullptr;
-    float *d_depth = nullptr;
-    uint8_t *d_ids = nullptr, *d_cover = nullptr;
+    // rope_coverage's plane
+    uint8_t *d_cover = nullptr;
+    // rope_render_batch: the output planes of one chunk of poses (elements allocated)
+    float *d_rdepth = nullptr;
+    uint8_t *d_rids = nullptr;
+    size_t rdepth_cap = 0, rids_cap = 0;
 };
 
 // ---- roctx ranges (the reference times its stages with utils.Timer / FancyTimer, robotpose/utils.py:122-180).
@@ -366,8 +368,8 @@ extern "C" void rope_destroy(rope_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     void *ptrs[] = {c->d_header, c->d_tris, c->d_verts, c->d_joint_fixed, c->d_joint_axes, c->d_PV, c->d_tq, c->d_t32,
-                    c->d_cand, c->d_err, c->d_best_err, c->d_mvp, c->d_bounds, c->d_mask_lo, c->d_mask_hi, c->d_layer_of, c->d_layer_rep, c->d_layers, c->d_layer_sums, c->d_parent_of, c->d_parent_rep, c->d_parents, c->d_table, c->d_tcount, c->d_toff, c->d_tused, c->d_tgoff, c->d_tgval, c->d_ttotal, c->d_zero_total, c->d_tsums, c->d_terr, c->d_qitems, c->d_tile_tris, c->d_tile_tris_lo, c->d_qctr, c->d_touched, c->d_gtile, c->d_aabb, c->d_sums, c->d_best_idx, c->d_key,
-                    c->d_depth, c->d_ids, c->d_cover, c->d_ftq, c->d_ftl, c->d_ftotal, c->d_fempty, c->d_ft32, c->d_vstage, c->d_empty[0], c->d_empty[1], c->d_empty[2], c->d_empty[3],
+                    c->d_cand, c->d_err, c->d_best_err, c->d_mvp, c->d_bounds, c->d_mask_lo, c->d_mask_hi, c->d_layer_of, c->d_layer_rep, c->d_layers, c->d_layer_sums, c->d_parent_of, c->d_parent_rep, c->d_parents, c->d_table, c->d_tcount, c->d_toff, c->d_tused, c->d_tgoff, c->d_tgval, c->d_ttotal, c->d_zero_total, c->d_tsums, c->d_terr, c->d_qitems, c->d_tile_tris, c->d_tile_tris_lo, c->d_qctr, c->d_touched, c->d_gtile, c->d_aabb, c->d_sums, c->d_best_idx,
+                    c->d_rdepth, c->d_rids, c->d_cover, c->d_ftq, c->d_ftl, c->d_ftotal, c->d_fempty, c->d_ft32, c->d_vstage, c->d_empty[0], c->d_empty[1], c->d_empty[2], c->d_empty[3],
                     c->d_total[0], c->d_total[1], c->d_total[2], c->d_total[3], c->d_fts32, c->d_fflags, c->d_tg_total[0], c->d_tg_total[1], c->d_tg_total[2],
                     c->d_tg_total[3], c->d_tg_empty, c->d_frame_of, c->d_tg_t32c, c->d_tg_ltotal, c->d_tg_scores, c->d_tg_best, c->d_t32ts, c->d_tc,
                     c->s_ftq, c->s_ft32, c->s_fts32, c->s_fflags};
@@ -513,9 +515,6 @@ extern "C" int rope_set_camera(rope_ctx *c, const double *PV, int W, int H, doub
         HIP_TRY(c, realloc_dev(&c->d_tq, n));
         HIP_TRY(c, realloc_dev(&c->d_t32, n));
         HIP_TRY(c, realloc_dev(&c->d_t32ts, n));
-        HIP_TRY(c, realloc_dev(&c->d_key, n));
-        HIP_TRY(c, realloc_dev(&c->d_depth, n));
-        HIP_TRY(c, realloc_dev(&c->d_ids, n));
         HIP_TRY(c, realloc_dev(&c->d_cover, n));
         for (int k = 0; k < 4; k++) {
             HIP_TRY(c, realloc_dev(&c->d_empty[k], (size_t)n_tiles * ROPE_SUM_WORDS));
@@ -1394,8 +1393,110 @@ static int raster_only(rope_ctx *c, const double *cand, int C, int n_render, int
     rc = enqueue_geometry(c, n_render, 0, c->fp, false);
     if (rc) return rc;
     RasterArgs a = base_args(c, n_render);
-    a.key_out = c->d_key; a.cover = c->d_cover;
+    a.cover = c->d_cover;
     HIP_TRY(c, launch_raster(mode, ROPE_LOSS_DEPTH, c->C, c->stream, c->fp, c->rp, a, use_clip(c)));
+    c->last_n_render = n_render;
+    return ROPE_OK;
+}
+
+// device -> host for the render planes: one copy straight into page-locked memory, else through the staging block
+static int copy_d2h_out(rope_ctx *c, void *dst, const void *src, size_t bytes)
+{
+    if (bytes >= (64u << 10) && is_pinned_host(dst)) {
+        HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return ROPE_OK;
+    }
+    return copy_d2h_staged(c, dst, src, bytes);
+}
+
+// device bytes of output planes one chunk of rope_render_batch may hold
+static constexpr size_t RENDER_BATCH_BUDGET = (size_t)256 << 20;
+
+extern "C" int rope_render_batch(rope_ctx *c, const double *q, const double *PV, int N, int n_render, const int32_t *crop,
+                                 float *depth, uint8_t *ids)
+{
+    if (!c) return ROPE_E_ARG;
+    if (!q) ARG_FAIL(c, "rope_render_batch: null joint vectors");
+    if (N < 1) ARG_FAIL(c, "rope_render_batch: need N >= 1");
+    if (!depth && !ids) ARG_FAIL(c, "rope_render_batch: no output (depth and ids both null)");
+    if (!c->have_robot || !c->have_camera) ARG_FAIL(c, "rope_render_batch: robot and camera must be set first");
+    if (n_render < 1 || n_render > c->n_links) ARG_FAIL(c, "rope_render_batch: n_render out of range");
+    FrameParams fp = c->fp;
+    if (crop) {
+        if (crop[0] < 0 || crop[1] >= fp.H || crop[0] > crop[1] || crop[2] < 0 || crop[3] >= fp.W || crop[2] > crop[3])
+            ARG_FAIL(c, "rope_render_batch: crop outside the image");
+        fp.r0 = crop[0]; fp.r1 = crop[1]; fp.c0 = crop[2]; fp.c1 = crop[3];
+    }
+    for (size_t i = 0; i < 6 * (size_t)N; i++)
+        if (!std::isfinite(q[i]) || std::fabs(q[i]) > 1.0e4) ARG_FAIL(c, "rope_render_batch: joint angle not finite or |q| > 1e4 rad");
+    bool clip = use_clip(c);
+    if (PV) {
+        for (size_t i = 0; i < 16 * (size_t)N; i++)
+            if (!std::isfinite(PV[i])) ARG_FAIL(c, "rope_render_batch: non-finite view matrix");
+        clip = c->strategy & STRATEGY_CLIP_KERNELS;                // the call's cameras decide, not the context's
+        for (int i = 0; i < N && !clip; i++) clip = near_plane_in_reach(c, PV + 16 * (size_t)i);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t px = (size_t)(fp.r1 - fp.r0 + 1) * (size_t)(fp.c1 - fp.c0 + 1);
+    const size_t per_pose = px * ((depth ? sizeof(float) : 0) + (ids ? 1 : 0));
+    const int chunk = (int)std::min<size_t>({(size_t)N, (size_t)MAX_ROWS, std::max<size_t>(1, RENDER_BATCH_BUDGET / per_pose)});
+    int rc = ensure_capacity(c, chunk);
+    if (rc) return rc;
+    if (depth && (size_t)chunk * px > c->rdepth_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->rdepth_cap = 0;
+        HIP_TRY(c, realloc_dev(&c->d_rdepth, (size_t)chunk * px));
+        c->rdepth_cap = (size_t)chunk * px;
+    }
+    if (ids && (size_t)chunk * px > c->rids_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->rids_cap = 0;
+        HIP_TRY(c, realloc_dev(&c->d_rids, (size_t)chunk * px));
+        c->rids_cap = (size_t)chunk * px;
+    }
+    // the rows of a chunk go up in one block, as rope_eval_views sends its own: joint vectors | view matrices | view index
+    const size_t off_pv = 6 * (size_t)chunk * sizeof(double), off_vo = off_pv + (PV ? 16 * (size_t)chunk * sizeof(double) : 0),
+                 bytes = off_vo + (PV ? (size_t)chunk * sizeof(int32_t) : 0);
+    if (bytes > c->vstage_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->h_vstage) { (void)hipHostFree(c->h_vstage); c->h_vstage = nullptr; }
+        c->vstage_cap = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_vstage, bytes, hipHostMallocDefault));
+        HIP_TRY(c, realloc_dev(&c->d_vstage, bytes));
+        c->vstage_cap = bytes;
+    }
+    // the per-candidate buffers hold render rows from here on (rope_eval_views does the same)
+    c->cand_valid = c->results_valid = false;
+    c->cand_dev = nullptr;
+    c->mvp_valid = false;
+    for (int lo = 0; lo < N; lo += chunk) {
+        const int n = std::min(chunk, N - lo);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));         // the block may still feed the previous chunk's copy
+        std::memcpy(c->h_vstage, q + 6 * (size_t)lo, 6 * (size_t)n * sizeof(double));
+        if (PV) {
+            std::memcpy(c->h_vstage + off_pv, PV + 16 * (size_t)lo, 16 * (size_t)n * sizeof(double));
+            int32_t *vo = reinterpret_cast<int32_t *>(c->h_vstage + off_vo);
+            for (int i = 0; i < n; i++) vo[i] = i;
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->d_vstage, c->h_vstage, bytes, hipMemcpyHostToDevice, c->stream));
+        c->dv_cand = reinterpret_cast<const double *>(c->d_vstage);
+        c->dv_PV = PV ? reinterpret_cast<const double *>(c->d_vstage + off_pv) : c->d_PV;
+        c->dv_view_of = PV ? reinterpret_cast<const int32_t *>(c->d_vstage + off_vo) : nullptr;
+        c->C = n;
+        c->n_layers = n;                                      // nothing shared: every row draws all its links
+        rc = enqueue_geometry(c, n_render, 0, fp, true);
+        if (rc) return rc;
+        if (depth) HIP_TRY(c, hipMemsetAsync(c->d_rdepth, 0, (size_t)n * px * sizeof(float), c->stream));
+        if (ids) HIP_TRY(c, hipMemsetAsync(c->d_rids, 0xFF, (size_t)n * px, c->stream));
+        RasterArgs a = base_args(c, n_render);
+        a.depth_out = depth ? c->d_rdepth : nullptr;
+        a.ids_out = ids ? c->d_rids : nullptr;
+        HIP_TRY(c, launch_raster(MODE_DUMP, ROPE_LOSS_DEPTH, n, c->stream, fp, c->rp, a, clip));
+        if (depth) { rc = copy_d2h_out(c, depth + (size_t)lo * px, c->d_rdepth, (size_t)n * px * sizeof(float)); if (rc) return rc; }
+        if (ids) { rc = copy_d2h_out(c, ids + (size_t)lo * px, c->d_rids, (size_t)n * px); if (rc) return rc; }
+    }
+    c->C = 0;
     c->last_n_render = n_render;
     return ROPE_OK;
 }
@@ -1405,15 +1506,7 @@ extern "C" int rope_render(rope_ctx *c, const double *q, int n_render, float *de
     if (!c) return ROPE_E_ARG;
     if (!q || !depth || !ids) ARG_FAIL(c, "rope_render: null pointer");
     if (!c->have_camera) ARG_FAIL(c, "rope_render: camera not set");
-    HIP_TRY(c, hipSetDevice(c->device));
-    size_t n = (size_t)c->fp.W * c->fp.H;
-    HIP_TRY(c, hipMemsetAsync(c->d_key, 0xFF, n * sizeof(uint32_t), c->stream));
-    int rc = raster_only(c, q, 1, n_render, MODE_DUMP);
-    if (rc) return rc;
-    HIP_TRY(c, launch_resolve(c->stream, c->d_key, (int)n, c->fp, c->d_depth, c->d_ids));
-    rc = copy_d2h_staged(c, depth, c->d_depth, n * sizeof(float));
-    if (rc) return rc;
-    return copy_d2h_staged(c, ids, c->d_ids, n);
+    return rope_render_batch(c, q, nullptr, 1, n_render, nullptr, depth, ids);
 }
 
 extern "C" int rope_coverage(rope_ctx *c, const double *cand, int C, int n_render, uint8_t *cover)

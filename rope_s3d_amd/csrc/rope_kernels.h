@@ -123,7 +123,10 @@ struct RasterArgs {
     // per-link planes per frame, bit 40 = link mask, bits 0..38 = masked target depth) and each candidate's frame index
     const uint64_t *tl;
     const int32_t *frame_of;
-    uint64_t *sums; uint32_t *key_out; uint8_t *cover;
+    uint64_t *sums; uint8_t *cover;
+    // MODE_DUMP: one plane per row over the crop fp.r0..r1 x fp.c0..c1, metric depth (0 = nothing drawn) and link id (255 =
+    // background); either may be null.  Samples of tiles nothing is drawn on keep what the caller's memsets put there
+    float *depth_out; uint8_t *ids_out;
     float *table;                         // MODE_TABLE: C x crop_h x crop_w sqrt-depth (crop = fp.r0..c1)
     // few candidates: the meshlets of a (tile, candidate) are split over `split` workgroups (grid z) that merge
     // their LDS tiles into gtile with atomicMin (MODE_SPLIT); score_gtile_kernel then scores and re-clears it
@@ -204,6 +207,5 @@ hipError_t launch_argmin_sets(hipStream_t st, const double *err, int C, int n_se
 hipError_t launch_table_score_frames(hipStream_t st, const FrameParams &fp, const uint32_t *counts, const unsigned long long *offs,
                                      const uint32_t *goff, const float4 *gval, int C, const float *t32, int n_frames, float *t32c, uint64_t *totals,
                                      double *scores, double *best);
-hipError_t launch_resolve(hipStream_t st, const uint32_t *key, int n, const FrameParams &fp, float *depth, uint8_t *ids);
 
 }  // namespace rope

@@ -1273,9 +1273,37 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const RobotPa
         return;
     }
     if (MODE == MODE_DUMP) {
-        for (int i = tid; i < TILE_W * TILE_H; i += NTHREADS) {
-            int row = row0 + i / TILE_W, col = col0 + i % TILE_W;
-            if (row < fp.H && col < fp.W) ra.key_out[(size_t)row * fp.W + col] = tile[i];
+        // one resolved image per row over the crop (the whole frame unless one is given): metric depth, linear_depth of the key's
+        // 24-bit depth (0 = nothing drawn), and the link id (255 = background); samples of tiles no workgroup draws keep the planes'
+        // memsets.
+        // Four samples a thread: where every crop row starts on a multiple of four, one float4 and one 32-bit id store each
+        const int cw = fp.c1 - fp.c0 + 1, ch = fp.r1 - fp.r0 + 1;
+        const size_t base = (size_t)cand * cw * ch;
+        const bool wide = ((fp.c0 | cw) & 3) == 0;
+        for (int i = tid; i < TILE_W * TILE_H / 4; i += NTHREADS) {
+            const int row = row0 + (4 * i) / TILE_W, col = col0 + (4 * i) % TILE_W;
+            if (row < fp.r0 || row > fp.r1 || col + 3 < fp.c0 || col > fp.c1) continue;
+            const uint4 k4 = reinterpret_cast<const uint4 *>(tile)[i];
+            const uint32_t k[4] = {k4.x, k4.y, k4.z, k4.w};
+            float z[4];
+            uint32_t id = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                z[j] = (k[j] == KEY_EMPTY) ? 0.0f : linear_depth(k[j] >> 8, fp.c_num, fp.c_sum, fp.c_dif);
+                id |= ((k[j] == KEY_EMPTY) ? 255u : (k[j] & 0xFFu)) << (8 * j);
+            }
+            const size_t o = base + (size_t)(row - fp.r0) * cw + (col - fp.c0);
+            if (wide) {                  // c0, cw multiples of 4: the four samples lie inside the crop together, o is a multiple of 4
+                if (ra.depth_out) *reinterpret_cast<float4 *>(ra.depth_out + o) = make_float4(z[0], z[1], z[2], z[3]);
+                if (ra.ids_out) *reinterpret_cast<uint32_t *>(ra.ids_out + o) = id;
+                continue;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (col + j < fp.c0 || col + j > fp.c1) continue;
+                if (ra.depth_out) ra.depth_out[o + j] = z[j];
+                if (ra.ids_out) ra.ids_out[o + j] = (uint8_t)(id >> (8 * j));
+            }
         }
         return;
     }
@@ -1297,7 +1325,7 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const RobotPa
 }
 
 // MODE_SCORE: reduce the loss and add (actual - empty) into the candidate's sums.
-// MODE_DUMP : write the tile's keys to a full-frame key image (single-pose render).
+// MODE_DUMP : write the row's resolved depth and link ids over the crop (rope_render_batch).
 // MODE_COVER: set cover[pixel] = 1 where anything was drawn (crop search).
 template <int LOSS, int MODE, bool CLIP>
 __global__ void __launch_bounds__(NTHREADS, CLIP ? ROPE_MIN_WAVES_CLIP : ((LOSS == ROPE_LOSS_FULL || LOSS == ROPE_LOSS_CAMFULL) ? ROPE_MIN_WAVES_FULL : ROPE_MIN_WAVES_PER_SIMD))
@@ -1815,17 +1843,6 @@ finalize_argmin_kernel(uint64_t *__restrict__ sums, const uint64_t *__restrict__
     }
 }
 
-// key image -> metric depth + link id (single-pose render path)
-__global__ void resolve_kernel(const uint32_t *__restrict__ key, int n, float c_num, float c_sum, float c_dif,
-                               float *__restrict__ depth, uint8_t *__restrict__ ids)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t k = key[i];
-    depth[i] = (k == KEY_EMPTY) ? 0.0f : linear_depth(k >> 8, c_num, c_sum, c_dif);
-    ids[i] = (k == KEY_EMPTY) ? 255 : (uint8_t)(k & 0xFF);
-}
-
 // ------------------------------------------------------------ launch helpers ---
 template <int LOSS, int MODE>
 static void launch_one(dim3 grid, hipStream_t st, const FrameParams &fp, const RobotParams &rp, const RasterArgs &a, bool clip)
@@ -2019,12 +2036,6 @@ hipError_t launch_table_score(hipStream_t st, const FrameParams &fp, const uint3
 {
     hipLaunchKernelGGL(crop_total_kernel, dim3(1), dim3(1024), 0, st, fp, t32, t32c, total);
     hipLaunchKernelGGL(table_score_kernel, dim3(C), dim3(256), 0, st, counts, offs, goff, gval, t32c, total, sums);
-    return hipGetLastError();
-}
-
-hipError_t launch_resolve(hipStream_t st, const uint32_t *key, int n, const FrameParams &fp, float *depth, uint8_t *ids)
-{
-    hipLaunchKernelGGL(resolve_kernel, dim3((n + 255) / 256), dim3(256), 0, st, key, n, fp.c_num, fp.c_sum, fp.c_dif, depth, ids);
     return hipGetLastError();
 }
 

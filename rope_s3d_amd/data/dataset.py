@@ -112,6 +112,10 @@ def write_dataset(name: str, og_img: np.ndarray, depthmaps: np.ndarray, angles: 
     return d
 
 
+# frames per Renderer.render_batch call when a whole set is generated
+_RENDER_BLOCK = 256
+
+
 def make_synthetic_dataset(name: str, n_frames: int, base_intrin: str = '640_480_color', camera_pose=None,
                            do_angles: str = 'SLU', seed: int = 7919, device: int = 0) -> str:
     """Synthetic RGB-D frames rendered by the engine: frame f uses default_rng(seed+f), pose uniform in the
@@ -123,12 +127,12 @@ def make_synthetic_dataset(name: str, n_frames: int, base_intrin: str = '640_480
     r = Renderer('seg', pose, base_intrin, device=device)
     lim = r.robot.joint_limits
     H, W = r.resolution
-    og, dm, ang = np.zeros((n_frames, H, W, 3), np.uint8), np.zeros((n_frames, H, W)), np.zeros((n_frames, 6))
+    og, dm = np.zeros((n_frames, H, W, 3), np.uint8), np.zeros((n_frames, H, W))
+    ang = np.zeros((n_frames, 6))
     for f in range(n_frames):
-        q = np.random.default_rng(seed + f).uniform(lim[:, 0], lim[:, 1]) * str_to_arr(do_angles)
-        r.setJointAngles(q)
-        og[f], dm[f] = r.render()
-        ang[f] = q
+        ang[f] = np.random.default_rng(seed + f).uniform(lim[:, 0], lim[:, 1]) * str_to_arr(do_angles)
+    for a in range(0, n_frames, _RENDER_BLOCK):                # many frames per device batch (rope_render_batch)
+        og[a:a + _RENDER_BLOCK], dm[a:a + _RENDER_BLOCK] = r.render_batch(ang[a:a + _RENDER_BLOCK])
     return write_dataset(name, og, dm, ang, np.tile(pose, (n_frames, 1)), str(r.intrinsics),
                          extra_attrs={'synthetic': True, 'color_dict': r.color_dict})
 
@@ -146,6 +150,10 @@ class _LazyFrames:
         if isinstance(key, slice):
             idx = range(*key.indices(self.shape[0]))
             out = np.empty((len(idx),) + self.shape[1:], self.dtype)
+            if idx.step == 1:                            # a run of frames: one batch, kept for the other plane's read
+                if len(idx):
+                    out[:] = self._owner.frames(idx.start, idx.stop)[self._what]
+                return out
             for k, i in enumerate(idx):
                 out[k] = self._owner.frame(i)[self._what]
             return out
@@ -175,6 +183,7 @@ class SyntheticDataset:
         self._r = Renderer('seg', pose, base_intrin, device=device)
         self._lock = threading.Lock()                    # one engine context: frames are rendered one at a time
         self._last = (None, None)
+        self._block = (None, None)                      # ((a, b), (colours, depths)) of the last run of frames rendered
         lim = self._r.robot.joint_limits
         self.length, self.name = int(n_frames), f'{self.PREFIX}{n_frames}:{seed}:{base_intrin}'
         self.angles = np.stack([np.random.default_rng(seed + f).uniform(lim[:, 0], lim[:, 1]) * str_to_arr(do_angles) for f in range(n_frames)])
@@ -200,6 +209,14 @@ class SyntheticDataset:
                 self._r.setJointAngles(self.angles[i])
                 self._last = (i, self._r.render())
             return self._last[1]
+
+    def frames(self, a: int, b: int):
+        """-> (colours uint8 (b-a, H, W, 3), depths float32 (b-a, H, W)) of frames a..b-1, rendered in one batch and kept:
+        a slice read of og_img followed by the same slice of depthmaps renders once."""
+        with self._lock:
+            if self._block[0] != (a, b):
+                self._block = ((a, b), self._r.render_batch(self.angles[a:b]))
+            return self._block[1]
 
     def close(self):
         pass

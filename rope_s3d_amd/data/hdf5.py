@@ -460,8 +460,9 @@ def write_h5_dataset(path: str, og_img, depthmaps, angles, camera_pose, color_in
     return path
 
 
-def write_arrays(path: str, arrays: dict, attrs: dict = None, gzip: int = None) -> str:
-    """A plain HDF5 file of named arrays ({'group/sub/name': ndarray}); groups are created as needed."""
+def write_arrays(path: str, arrays: dict, attrs: dict = None, gzip=None) -> str:
+    """A plain HDF5 file of named arrays ({'group/sub/name': ndarray}); groups are created as needed.  gzip: one level for every
+    array, or {name: level} for some of them (the others stored uncompressed)."""
     h = lib()
     if os.path.exists(path):
         os.remove(path)
@@ -472,7 +473,7 @@ def write_arrays(path: str, arrays: dict, attrs: dict = None, gzip: int = None) 
         for k, v in (attrs or {}).items():
             _write_attr(fid, k, v)
         for name, data in arrays.items():
-            _write_array(fid, name, np.asarray(data), gzip)
+            _write_array(fid, name, np.asarray(data), gzip.get(name) if isinstance(gzip, dict) else gzip)
     finally:
         h.H5Fclose(fid)
     return path

@@ -20,7 +20,7 @@ TQ_MAX = (1 << 39) - 1
 ABI_SYMBOLS = (
     'rope_create', 'rope_destroy', 'rope_last_error', 'rope_set_robot', 'rope_set_camera', 'rope_set_target',
     'rope_candidates_upload', 'rope_eval_resident', 'rope_sync', 'rope_results_download', 'rope_eval',
-    'rope_lookup_build', 'rope_lookup_score', 'rope_render', 'rope_coverage', 'rope_debug_mvp', 'rope_profile_eval', 'rope_set_strategy',
+    'rope_lookup_build', 'rope_lookup_score', 'rope_render', 'rope_render_batch', 'rope_coverage', 'rope_debug_mvp', 'rope_profile_eval', 'rope_set_strategy',
     'rope_set_frames', 'rope_eval_views', 'rope_predict', 'rope_set_robot_mesh', 'rope_partition_mesh', 'rope_pack_target', 'rope_downsample_even',
     'rope_seg_nms', 'rope_seg_roi_align', 'rope_seg_bias_act',
     'rope_set_target_tsweep', 'rope_set_targets', 'rope_stage_targets', 'rope_commit_targets', 'rope_eval_targets', 'rope_lookup_score_targets', 'rope_predict_batch',
@@ -112,6 +112,7 @@ def load_library(path: str = None):
     lib.rope_lookup_build.argtypes = [vp, vp, i32, i32, vp]
     lib.rope_lookup_score.argtypes = [vp, vp, vp, vp]
     lib.rope_render.argtypes = [vp, vp, i32, vp, vp]
+    lib.rope_render_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     lib.rope_coverage.argtypes = [vp, vp, i32, i32, vp]
     lib.rope_debug_mvp.argtypes = [vp, vp, i32, i32]
     lib.rope_profile_eval.argtypes = [vp, i32, i32, vp, i32, vp]
@@ -489,6 +490,30 @@ class Engine:
         ids = np.empty((self.H, self.W), np.uint8)
         self._check(self._lib.rope_render(self._ctx, _p(q), int(n_render), _p(depth), _p(ids)), 'rope_render')
         return depth, ids
+
+    def render_batch(self, q, n_render: int = 6, PV=None, crop=None, depth: bool = True, ids: bool = True):
+        """rope_render_batch: N poses in one device batch.  q (N, 6); PV (N, 4, 4) per-pose P·V or None = the camera of
+        set_camera (which stays the context's camera); crop (r0, r1, c0, c1) inclusive or None = whole frame.
+        -> (depth (N, h, w) float32 metres | None, ids (N, h, w) uint8, 255 = background | None), h x w the crop."""
+        q = np.ascontiguousarray(q, np.float64).reshape(-1, 6)
+        N = len(q)
+        if PV is not None:
+            PV = np.ascontiguousarray(PV, np.float64).reshape(-1, 16)
+            if len(PV) != N:
+                raise ValueError(f"render_batch: {len(PV)} view matrices for {N} poses")
+        crop_arr = None
+        h, w = self.H, self.W
+        if crop is not None:
+            crop_arr = np.ascontiguousarray(crop, np.int32).reshape(4)
+            h, w = int(crop_arr[1]) - int(crop_arr[0]) + 1, int(crop_arr[3]) - int(crop_arr[2]) + 1
+        if N and (h < 1 or w < 1):
+            raise ValueError(f"render_batch: empty crop {tuple(crop_arr)}")
+        d = np.empty((N, max(h, 0), max(w, 0)), np.float32) if depth else None
+        i = np.empty((N, max(h, 0), max(w, 0)), np.uint8) if ids else None
+        if N == 0:
+            return d, i
+        self._check(self._lib.rope_render_batch(self._ctx, _p(q), _p(PV), N, int(n_render), _p(crop_arr), _p(d), _p(i)), 'rope_render_batch')
+        return d, i
 
     def coverage(self, cand, n_render: int) -> np.ndarray:
         cand = np.ascontiguousarray(cand, np.float64).reshape(-1, 6)

@@ -1,1 +1,2 @@
-from .render import Renderer
+from .lookup import RobotLookupCreator
+from .render import DatasetRenderer, Renderer

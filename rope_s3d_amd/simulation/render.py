@@ -3,7 +3,8 @@
 Reference: robotpose/simulation/render.py:25-163 (pyrender scene of the six link meshes, an
 intrinsics camera, SEG-flag offscreen render returning a flat-colour image and metric
 depth).  Here `render()` is one rope_render call; colours come from the link-id image
-through the same DEFAULT_RENDER_COLORS table.
+through the same DEFAULT_RENDER_COLORS table.  `render_batch` draws many poses (and cameras) in one
+rope_render_batch call; DatasetRenderer (render.py:167-187) is built on it.
 """
 from typing import List, Tuple, Union
 
@@ -138,6 +139,32 @@ class Renderer:
             return shade_depth(depth, ids, self.intrinsics), depth
         return self._lut[ids], depth
 
+    def _views(self, camera_poses, n: int):
+        """P·V per pose from camera_matrix, the one setCameraPose uses; None = the renderer's own camera."""
+        if camera_poses is None:
+            return None
+        poses = np.asarray(camera_poses, dtype=np.float64).reshape(-1, 6)
+        if len(poses) != n:
+            raise ValueError(f"{len(poses)} camera poses for {n} joint vectors")
+        return np.stack([camera_matrix(p, self.intrinsics, ZNEAR, ZFAR) for p in poses]) if n else np.zeros((0, 4, 4))
+
+    def render_ids_batch(self, angles, camera_poses=None, crop=None):
+        """N poses, each under its own camera pose (the renderer's when None), in one rope_render_batch call: what N rounds of
+        setJointAngles [+ setCameraPose] + render_ids give.  The renderer's own angles and camera stay as they were.
+        -> (depths float32 (N, h, w), link ids uint8 (N, h, w)), h x w the crop (whole frame when None)."""
+        angles = np.asarray(angles, dtype=np.float64).reshape(-1, 6)
+        return self.engine.render_batch(angles, self._n_render, self._views(camera_poses, len(angles)), crop)
+
+    def render_batch(self, angles, camera_poses=None):
+        """-> (colours uint8 (N, H, W, 3), depths float32 (N, H, W)): render() for every pose (and camera pose) in one batch."""
+        depth, ids = self.render_ids_batch(angles, camera_poses)
+        if self.mode == 'real':
+            color = np.empty(ids.shape + (3,), np.uint8)
+            for k in range(len(ids)):
+                color[k] = shade_depth(depth[k], ids[k], self.intrinsics)
+            return color, depth
+        return self._lut[ids], depth
+
     @property
     def resolution(self) -> Tuple[int]:
         return (self.intrinsics.height, self.intrinsics.width)
@@ -151,3 +178,53 @@ class Renderer:
         if self.mode == 'seg':
             return {name: color for name, color in zip(self.joint_names[:self._n_render], self._colors)}
         return {'robot': DEFAULT_RENDER_COLORS[0]}
+
+
+class DatasetRenderer(Renderer):
+    """Renders a dataset's frames at their recorded joint angles and camera poses (render.py:167-187).  `dataset` is a name
+    (open_dataset: 'synthetic:...' names too) or an opened Dataset / SyntheticDataset.  render_range / render_indices draw many
+    frames in one batch, each under its own camera pose."""
+
+    def __init__(self, dataset, mode: str = 'seg', camera_pose: np.ndarray = None):
+        from ..data.dataset import open_dataset
+        self.ds = open_dataset(dataset) if isinstance(dataset, str) else dataset
+        self._ds_angles = np.asarray(self.ds.angles[:], dtype=np.float64).reshape(-1, 6)
+        self._ds_poses = np.asarray(self.ds.camera_pose[:], dtype=np.float64).reshape(-1, 6)
+        if camera_pose is None:
+            camera_pose = self._ds_poses[0]
+        super().__init__(mode, camera_pose, str(self.ds.attrs['color_intrinsics']))
+
+    def render_at(self, idx: int):
+        """Render one frame of the dataset at its own joint angles and camera pose."""
+        self.setPosesFromDS(idx)
+        return self.render()
+
+    def setPosesFromDS(self, idx: int):
+        """Set the robot and camera poses to those of frame idx."""
+        self.setJointAngles(self._ds_angles[idx])
+        self.setCameraPose(self._ds_poses[idx])
+
+    def render_indices(self, idx):
+        """-> (colours (N, H, W, 3), depths (N, H, W)) of the frames idx, each at its own angles and camera pose, in one batch;
+        the renderer's own pose stays as it was."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        return self.render_batch(self._ds_angles[idx], self._ds_poses[idx])
+
+    def render_range(self, start: int, stop: int):
+        """render_indices(range(start, stop))."""
+        return self.render_indices(np.arange(start, stop))
+
+    def close(self):
+        """Release the dataset and the engine context."""
+        ds, self.ds = getattr(self, 'ds', None), None
+        if ds is not None:
+            ds.close()
+        eng = getattr(self, 'engine', None)
+        if eng is not None:
+            eng.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
