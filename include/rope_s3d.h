@@ -203,6 +203,32 @@ int rope_render(rope_ctx *ctx, const double *q, int n_render, float *depth, uint
 int rope_render_batch(rope_ctx *ctx, const double *q, const double *PV, int N, int n_render, const int32_t *crop,
                       float *depth, uint8_t *ids);
 
+/* N poses to per-pixel label bit planes.  Replaces, per frame of AutomaticAnnotator.run, Renderer.render + Annotator._mask_color
+ * for every label (annotation.py:117-127,163-176): bit b of masks[p][y][x] is set when any pixel of label b lies within the
+ * pad x pad window anchored at (pad/2, pad/2) around (x, y), which is cv2.dilate(mask_b, ones((pad, pad))).
+ *   q, PV, N, n_render   as rope_render_batch (PV NULL = the context's camera); whole frame only
+ *   label_of_link        n_render entries: the bit (0..7) that a pixel drawn by link l sets, or 255 = none
+ *   pad                  1..64 (1 = no dilation)
+ *   masks                N planes H x W uint8
+ *   boxes                N x 8 x 4 int32 {r0, r1, c0, c1} inclusive per (pose, bit), all -1 when the bit is empty; or NULL
+ * Chunks, cameras and the per-candidate buffers as rope_render_batch; only the masks and boxes leave the device. */
+int rope_render_masks(rope_ctx *ctx, const double *q, const double *PV, int N, int n_render,
+                      const uint8_t *label_of_link, int pad, uint8_t *masks, int32_t *boxes);
+
+/* Borders of one label of a mask plane, as cv2.findContours(mask_b, cv2.RETR_TREE, cv2.CHAIN_APPROX_SIMPLE) of OpenCV 4.5.1
+ * gives them to Annotator._get_contour (annotation.py:77-86,125-127).  Host only, needs no context, thread-safe.
+ *   mask        H x W uint8; the label is bit `bit` (0..7) of each byte; the plane has a frame of zero pixels around it
+ *   box         {r0, r1, c0, c1} inclusive enclosing every set pixel of the bit (rope_render_masks' boxes), all -1 = empty;
+ *               or NULL = the whole plane
+ *   min_points  contours of fewer points are left out (the reference keeps those of at least 20); 0 keeps all
+ *   points      out: (x, y) int32 pairs, capacity points_cap pairs
+ *   starts      out: n_contours + 1 offsets into points (in pairs), capacity starts_cap
+ * Outer and hole borders (Suzuki-Abe, 8-connected foreground) in the order the raster scan finds them; each keeps its start
+ * point and every point where the chain direction changes.  *n_points and *n_contours get the sizes (also when the buffers
+ * are too small: then nothing is written and ROPE_E_NOMEM is returned). */
+int rope_trace_contours(const uint8_t *mask, int H, int W, int bit, const int32_t *box, int min_points, int32_t *points,
+                        int points_cap, int32_t *starts, int starts_cap, int *n_points, int *n_contours);
+
 /* OR over candidates of "pixel covered" (H x W uint8 0/1).  Replaces the depth-sum loop
  * of Crop._create (crop.py:60-81). */
 int rope_coverage(rope_ctx *ctx, const double *cand, int C, int n_render, uint8_t *cover);

@@ -4,3 +4,4 @@ resolve to the MI355X engine's host package."""
 from rope_s3d_amd import Dataset, Grapher, Intrinsics, Paths, Predictor, Renderer, SyntheticPredictor  # noqa: F401
 from rope_s3d_amd.prediction.feed import JSONCoupling, LiveCamera  # noqa: F401
 from rope_s3d_amd.simulation import DatasetRenderer  # noqa: F401
+from rope_s3d_amd.data.annotation import AutomaticAnnotator  # noqa: F401

@@ -196,6 +196,10 @@ struct rope_ctx {
     float *d_rdepth = nullptr;
     uint8_t *d_rids = nullptr;
     size_t rdepth_cap = 0, rids_cap = 0;
+    // rope_render_masks: one chunk's label planes and boxes (elements allocated)
+    uint8_t *d_rmask = nullptr;
+    int32_t *d_rboxes = nullptr;
+    size_t rmask_cap = 0, rboxes_cap = 0;
 };
 
 // ---- roctx ranges (the reference times its stages with utils.Timer / FancyTimer, robotpose/utils.py:122-180).
@@ -369,7 +373,7 @@ extern "C" void rope_destroy(rope_ctx *c)
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     void *ptrs[] = {c->d_header, c->d_tris, c->d_verts, c->d_joint_fixed, c->d_joint_axes, c->d_PV, c->d_tq, c->d_t32,
                     c->d_cand, c->d_err, c->d_best_err, c->d_mvp, c->d_bounds, c->d_mask_lo, c->d_mask_hi, c->d_layer_of, c->d_layer_rep, c->d_layers, c->d_layer_sums, c->d_parent_of, c->d_parent_rep, c->d_parents, c->d_table, c->d_tcount, c->d_toff, c->d_tused, c->d_tgoff, c->d_tgval, c->d_ttotal, c->d_zero_total, c->d_tsums, c->d_terr, c->d_qitems, c->d_tile_tris, c->d_tile_tris_lo, c->d_qctr, c->d_touched, c->d_gtile, c->d_aabb, c->d_sums, c->d_best_idx,
-                    c->d_rdepth, c->d_rids, c->d_cover, c->d_ftq, c->d_ftl, c->d_ftotal, c->d_fempty, c->d_ft32, c->d_vstage, c->d_empty[0], c->d_empty[1], c->d_empty[2], c->d_empty[3],
+                    c->d_rdepth, c->d_rids, c->d_rmask, c->d_rboxes, c->d_cover, c->d_ftq, c->d_ftl, c->d_ftotal, c->d_fempty, c->d_ft32, c->d_vstage, c->d_empty[0], c->d_empty[1], c->d_empty[2], c->d_empty[3],
                     c->d_total[0], c->d_total[1], c->d_total[2], c->d_total[3], c->d_fts32, c->d_fflags, c->d_tg_total[0], c->d_tg_total[1], c->d_tg_total[2],
                     c->d_tg_total[3], c->d_tg_empty, c->d_frame_of, c->d_tg_t32c, c->d_tg_ltotal, c->d_tg_scores, c->d_tg_best, c->d_t32ts, c->d_tc,
                     c->s_ftq, c->s_ft32, c->s_fts32, c->s_fflags};
@@ -1495,6 +1499,105 @@ extern "C" int rope_render_batch(rope_ctx *c, const double *q, const double *PV,
         HIP_TRY(c, launch_raster(MODE_DUMP, ROPE_LOSS_DEPTH, n, c->stream, fp, c->rp, a, clip));
         if (depth) { rc = copy_d2h_out(c, depth + (size_t)lo * px, c->d_rdepth, (size_t)n * px * sizeof(float)); if (rc) return rc; }
         if (ids) { rc = copy_d2h_out(c, ids + (size_t)lo * px, c->d_rids, (size_t)n * px); if (rc) return rc; }
+    }
+    c->C = 0;
+    c->last_n_render = n_render;
+    return ROPE_OK;
+}
+
+// rope_render_batch's chunks, each drawn into id planes only and then turned into label planes on the device (rope_masks.hip):
+// the host gets one byte per pixel with the labels' dilation done, and each label's box
+extern "C" int rope_render_masks(rope_ctx *c, const double *q, const double *PV, int N, int n_render,
+                                 const uint8_t *label_of_link, int pad, uint8_t *masks, int32_t *boxes)
+{
+    if (!c) return ROPE_E_ARG;
+    if (!q || !label_of_link || !masks) ARG_FAIL(c, "rope_render_masks: null pointer");
+    if (N < 1) ARG_FAIL(c, "rope_render_masks: need N >= 1");
+    if (!c->have_robot || !c->have_camera) ARG_FAIL(c, "rope_render_masks: robot and camera must be set first");
+    if (n_render < 1 || n_render > c->n_links) ARG_FAIL(c, "rope_render_masks: n_render out of range");
+    if (pad < 1 || pad > ROPE_MASK_MAX_PAD) ARG_FAIL(c, "rope_render_masks: pad must be 1..64");
+    uint8_t lut[256] = {};                                      // link id -> label bits; background (255) and the rest -> none
+    for (int l = 0; l < n_render; l++) {
+        if (label_of_link[l] == 255) continue;
+        if (label_of_link[l] > 7) ARG_FAIL(c, "rope_render_masks: label bit must be 0..7 or 255");
+        lut[l] = (uint8_t)(1u << label_of_link[l]);
+    }
+    const FrameParams fp = c->fp;
+    for (size_t i = 0; i < 6 * (size_t)N; i++)
+        if (!std::isfinite(q[i]) || std::fabs(q[i]) > 1.0e4) ARG_FAIL(c, "rope_render_masks: joint angle not finite or |q| > 1e4 rad");
+    bool clip = use_clip(c);
+    if (PV) {
+        for (size_t i = 0; i < 16 * (size_t)N; i++)
+            if (!std::isfinite(PV[i])) ARG_FAIL(c, "rope_render_masks: non-finite view matrix");
+        clip = c->strategy & STRATEGY_CLIP_KERNELS;                // the call's cameras decide, not the context's
+        for (int i = 0; i < N && !clip; i++) clip = near_plane_in_reach(c, PV + 16 * (size_t)i);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t px = (size_t)fp.W * (size_t)fp.H;
+    const int chunk = (int)std::min<size_t>({(size_t)N, (size_t)MAX_ROWS, std::max<size_t>(1, RENDER_BATCH_BUDGET / (2 * px))});
+    int rc = ensure_capacity(c, chunk);
+    if (rc) return rc;
+    if ((size_t)chunk * px > c->rids_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->rids_cap = 0;
+        HIP_TRY(c, realloc_dev(&c->d_rids, (size_t)chunk * px));
+        c->rids_cap = (size_t)chunk * px;
+    }
+    if ((size_t)chunk * px > c->rmask_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->rmask_cap = 0;
+        HIP_TRY(c, realloc_dev(&c->d_rmask, (size_t)chunk * px));
+        c->rmask_cap = (size_t)chunk * px;
+    }
+    if ((size_t)chunk * 32 > c->rboxes_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->rboxes_cap = 0;
+        HIP_TRY(c, realloc_dev(&c->d_rboxes, (size_t)chunk * 32));
+        c->rboxes_cap = (size_t)chunk * 32;
+    }
+    // one block up per chunk: joint vectors | view matrices | view index | the 256-byte id -> label table
+    const size_t off_pv = 6 * (size_t)chunk * sizeof(double), off_vo = off_pv + (PV ? 16 * (size_t)chunk * sizeof(double) : 0),
+                 off_lut = (off_vo + (PV ? (size_t)chunk * sizeof(int32_t) : 0) + 15) & ~(size_t)15, bytes = off_lut + sizeof(lut);
+    if (bytes > c->vstage_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->h_vstage) { (void)hipHostFree(c->h_vstage); c->h_vstage = nullptr; }
+        c->vstage_cap = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_vstage, bytes, hipHostMallocDefault));
+        HIP_TRY(c, realloc_dev(&c->d_vstage, bytes));
+        c->vstage_cap = bytes;
+    }
+    c->cand_valid = c->results_valid = false;
+    c->cand_dev = nullptr;
+    c->mvp_valid = false;
+    for (int lo = 0; lo < N; lo += chunk) {
+        const int n = std::min(chunk, N - lo);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));         // the block may still feed the previous chunk
+        std::memcpy(c->h_vstage, q + 6 * (size_t)lo, 6 * (size_t)n * sizeof(double));
+        if (PV) {
+            std::memcpy(c->h_vstage + off_pv, PV + 16 * (size_t)lo, 16 * (size_t)n * sizeof(double));
+            int32_t *vo = reinterpret_cast<int32_t *>(c->h_vstage + off_vo);
+            for (int i = 0; i < n; i++) vo[i] = i;
+        }
+        std::memcpy(c->h_vstage + off_lut, lut, sizeof(lut));
+        HIP_TRY(c, hipMemcpyAsync(c->d_vstage, c->h_vstage, bytes, hipMemcpyHostToDevice, c->stream));
+        c->dv_cand = reinterpret_cast<const double *>(c->d_vstage);
+        c->dv_PV = PV ? reinterpret_cast<const double *>(c->d_vstage + off_pv) : c->d_PV;
+        c->dv_view_of = PV ? reinterpret_cast<const int32_t *>(c->d_vstage + off_vo) : nullptr;
+        c->C = n;
+        c->n_layers = n;
+        rc = enqueue_geometry(c, n_render, 0, fp, true);
+        if (rc) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->d_rids, 0xFF, (size_t)n * px, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_rboxes, 0xFF, (size_t)n * 32 * sizeof(int32_t), c->stream));
+        RasterArgs a = base_args(c, n_render);
+        a.depth_out = nullptr;
+        a.ids_out = c->d_rids;
+        HIP_TRY(c, launch_raster(MODE_DUMP, ROPE_LOSS_DEPTH, n, c->stream, fp, c->rp, a, clip));
+        HIP_TRY(c, launch_masks(c->stream, c->d_rids, n, fp.H, fp.W, reinterpret_cast<const uint8_t *>(c->d_vstage + off_lut), pad,
+                                c->d_rmask, c->d_rboxes));
+        rc = copy_d2h_out(c, masks + (size_t)lo * px, c->d_rmask, (size_t)n * px);
+        if (rc) return rc;
+        if (boxes) { rc = copy_d2h_out(c, boxes + (size_t)lo * 32, c->d_rboxes, (size_t)n * 32 * sizeof(int32_t)); if (rc) return rc; }
     }
     c->C = 0;
     c->last_n_render = n_render;

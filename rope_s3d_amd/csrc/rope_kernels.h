@@ -208,4 +208,11 @@ hipError_t launch_table_score_frames(hipStream_t st, const FrameParams &fp, cons
                                      const uint32_t *goff, const float4 *gval, int C, const float *t32, int n_frames, float *t32c, uint64_t *totals,
                                      double *scores, double *best);
 
+// rope_masks.hip: n id planes H x W (255 = background) -> label bit planes, each bit dilated by a pad x pad window with
+// cv2.dilate's anchor, and per (plane, bit) the box {r0, r1, c0, c1} of the dilated mask (boxes n x 8 x 4 int32, every
+// word set to -1 before the launch; left -1 for an empty bit).  lut: 256 bytes of device memory, id -> label bits.
+constexpr int ROPE_MASK_MAX_PAD = 64;
+hipError_t launch_masks(hipStream_t st, const uint8_t *ids, int n, int H, int W, const uint8_t *lut, int pad, uint8_t *masks,
+                        int32_t *boxes);
+
 }  // namespace rope

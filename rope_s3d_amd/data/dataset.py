@@ -78,6 +78,7 @@ class Dataset:
             if isinstance(self.attrs.get('color_dict'), str):          # a dict has no HDF5 form: stored as JSON text
                 self.attrs['color_dict'] = json.loads(self.attrs['color_dict'])
         self.length = int(self.attrs['length'])
+        self.link_anno_path = os.path.join(self.dataset_dir, 'link_annotations')     # dataset.py:191
         self.og_resolution = self.attrs.get('resolution')
         self.intrinsics = str(self.attrs['color_intrinsics'])
 
@@ -197,6 +198,8 @@ class SyntheticDataset:
         self.attrs = {'name': self.name, 'length': self.length, 'resolution': [H, W], 'color_intrinsics': self.intrinsics,
                       'synthetic': True, 'color_dict': self._r.color_dict}
         self.dataset_dir = self.name
+        # nothing is stored for a synthetic set: its annotations go under the output folder
+        self.link_anno_path = os.path.join(Paths().OUTPUT, self.name.replace(':', '_'), 'link_annotations')
 
     @classmethod
     def from_name(cls, name: str, device: int = 0):

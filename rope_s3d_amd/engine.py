@@ -20,7 +20,7 @@ TQ_MAX = (1 << 39) - 1
 ABI_SYMBOLS = (
     'rope_create', 'rope_destroy', 'rope_last_error', 'rope_set_robot', 'rope_set_camera', 'rope_set_target',
     'rope_candidates_upload', 'rope_eval_resident', 'rope_sync', 'rope_results_download', 'rope_eval',
-    'rope_lookup_build', 'rope_lookup_score', 'rope_render', 'rope_render_batch', 'rope_coverage', 'rope_debug_mvp', 'rope_profile_eval', 'rope_set_strategy',
+    'rope_lookup_build', 'rope_lookup_score', 'rope_render', 'rope_render_batch', 'rope_render_masks', 'rope_trace_contours', 'rope_coverage', 'rope_debug_mvp', 'rope_profile_eval', 'rope_set_strategy',
     'rope_set_frames', 'rope_eval_views', 'rope_predict', 'rope_set_robot_mesh', 'rope_partition_mesh', 'rope_pack_target', 'rope_downsample_even',
     'rope_seg_nms', 'rope_seg_roi_align', 'rope_seg_bias_act',
     'rope_set_target_tsweep', 'rope_set_targets', 'rope_stage_targets', 'rope_commit_targets', 'rope_eval_targets', 'rope_lookup_score_targets', 'rope_predict_batch',
@@ -113,6 +113,8 @@ def load_library(path: str = None):
     lib.rope_lookup_score.argtypes = [vp, vp, vp, vp]
     lib.rope_render.argtypes = [vp, vp, i32, vp, vp]
     lib.rope_render_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
+    lib.rope_render_masks.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
+    lib.rope_trace_contours.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.rope_coverage.argtypes = [vp, vp, i32, i32, vp]
     lib.rope_debug_mvp.argtypes = [vp, vp, i32, i32]
     lib.rope_profile_eval.argtypes = [vp, i32, i32, vp, i32, vp]
@@ -176,6 +178,30 @@ def pack_target(depth: np.ndarray, mask_bits: np.ndarray = None) -> np.ndarray:
     if mask_bits is not None:
         q |= np.asarray(mask_bits, np.uint64) << np.uint64(40)
     return np.ascontiguousarray(q)
+
+
+def trace_contours(mask: np.ndarray, bit: int, box=None, min_points: int = 0) -> list:
+    """rope_trace_contours (host only, thread-safe, no GPU): the borders of bit `bit` of an (H, W) uint8 plane as
+    cv2.findContours(RETR_TREE, CHAIN_APPROX_SIMPLE) finds them, outer and hole borders in raster-scan order, each an (k, 2)
+    int32 array of (x, y) points.  box (r0, r1, c0, c1) must enclose every set pixel of the bit (all -1 = none set) or be
+    None for the whole plane; contours of fewer than min_points points are left out."""
+    lib = load_library()
+    mask = np.ascontiguousarray(mask, np.uint8)
+    if mask.ndim != 2:
+        raise ValueError(f"trace_contours: need one (H, W) plane, got {mask.shape}")
+    box_arr = None if box is None else np.ascontiguousarray(box, np.int32).reshape(4)
+    H, W = mask.shape
+    n_pts, n_con = C.c_int(0), C.c_int(0)
+    pts, starts = np.empty((1024, 2), np.int32), np.empty(65, np.int32)
+    while True:
+        rc = lib.rope_trace_contours(_p(mask), H, W, int(bit), _p(box_arr), int(min_points), _p(pts), len(pts), _p(starts),
+                                     len(starts), C.byref(n_pts), C.byref(n_con))
+        if rc != -3:                                    # ROPE_E_NOMEM: the sizes it needs are in n_pts / n_con
+            break
+        pts, starts = np.empty((max(n_pts.value, 1), 2), np.int32), np.empty(n_con.value + 1, np.int32)
+    if rc != 0:
+        raise EngineError(f"rope_trace_contours failed ({rc}): bad plane, bit or box")
+    return [pts[starts[i]:starts[i + 1]].copy() for i in range(n_con.value)]
 
 
 def build_id() -> str:
@@ -514,6 +540,32 @@ class Engine:
             return d, i
         self._check(self._lib.rope_render_batch(self._ctx, _p(q), _p(PV), N, int(n_render), _p(crop_arr), _p(d), _p(i)), 'rope_render_batch')
         return d, i
+
+    def render_masks(self, q, n_render: int, label_of_link, pad: int, PV=None):
+        """rope_render_masks: N poses to label bit planes, each label dilated by a pad x pad window (cv2.dilate's anchor), in
+        device batches.  label_of_link: n_render bits (0..7, 255 = none); PV (N, 4, 4) per-pose P·V or None = the camera of
+        set_camera.  -> (masks (N, H, W) uint8, boxes (N, 8, 4) int32 {r0, r1, c0, c1} per label bit, -1 when empty)."""
+        q = np.ascontiguousarray(q, np.float64).reshape(-1, 6)
+        N = len(q)
+        lab = np.ascontiguousarray(label_of_link, np.uint8).reshape(-1)
+        if len(lab) != int(n_render):
+            raise ValueError(f"render_masks: {len(lab)} labels for {n_render} links")
+        if PV is not None:
+            PV = np.ascontiguousarray(PV, np.float64).reshape(-1, 16)
+            if len(PV) != N:
+                raise ValueError(f"render_masks: {len(PV)} view matrices for {N} poses")
+        masks = np.empty((N, self.H, self.W), np.uint8)
+        boxes = np.empty((N, 8, 4), np.int32)
+        if N == 0:
+            return masks, boxes
+        self._check(self._lib.rope_render_masks(self._ctx, _p(q), _p(PV), N, int(n_render), _p(lab), int(pad), _p(masks), _p(boxes)),
+                    'rope_render_masks')
+        return masks, boxes
+
+    @staticmethod
+    def trace_contours(mask: np.ndarray, bit: int, box=None, min_points: int = 0) -> list:
+        """engine.trace_contours: host code, no context needed."""
+        return trace_contours(mask, bit, box, min_points)
 
     def coverage(self, cand, n_render: int) -> np.ndarray:
         cand = np.ascontiguousarray(cand, np.float64).reshape(-1, 6)

@@ -165,6 +165,17 @@ class Renderer:
             return color, depth
         return self._lut[ids], depth
 
+    def render_masks_batch(self, angles, camera_poses=None, pad: int = 3):
+        """Label bit planes of N poses (each under its own camera pose, the renderer's when None) in rope_render_masks calls:
+        bit i is the i-th label of color_dict ('seg': link i; 'seg_full': every link is 'robot'), dilated by a pad x pad window
+        as Annotator._mask_color does.  The renderer's own angles and camera stay as they were.
+        -> (masks uint8 (N, H, W), boxes int32 (N, 8, 4) {r0, r1, c0, c1} per bit, -1 when empty)."""
+        if self.mode == 'real':
+            raise ValueError("render_masks_batch: mode 'real' has no labels")
+        angles = np.asarray(angles, dtype=np.float64).reshape(-1, 6)
+        labels = np.arange(self._n_render, dtype=np.uint8) if self.mode == 'seg' else np.zeros(self._n_render, np.uint8)
+        return self.engine.render_masks(angles, self._n_render, labels, pad, self._views(camera_poses, len(angles)))
+
     @property
     def resolution(self) -> Tuple[int]:
         return (self.intrinsics.height, self.intrinsics.width)
