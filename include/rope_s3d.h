@@ -401,6 +401,39 @@ int rope_seg_roi_align(const void *rows_bf16, const float *boxes, const int32_t 
                        const int64_t *level_off, int n_boxes, int channels, int pool, float inv_level_unit, const float *t,
                        void *out_bf16, void *stream);
 
+/* ---- Segmentation training (rope_s3d_amd/training.py: Matterport's training graph, mrcnn/model.py).  Same conventions as the
+ * rope_seg_* calls above.  Random choices are per-element keys from the caller: a kernel keeps the smallest (key, index) pairs.
+ *
+ * rope_seg_rpn_targets: build_rpn_targets of n_frames frames (float64, pixel coordinates).
+ *   anchors     n_anchors x 4 float64 (y1, x1, y2, x2), n_anchors < 131 072;  gt_boxes: n_frames x gt_stride x 4 float64
+ *   gt_count    n_frames int32 (<= gt_stride <= 100);  keys: n_frames x n_anchors uint32
+ *   anchor_max  n_frames x n_anchors float64, anchor_arg n_frames x n_anchors int32 (out: best IoU and its GT);  gt_max: scratch
+ *   match       n_frames x n_anchors int32 out: 1 positive, -1 negative, 0 neutral (at most 128 positives, 256 in all)
+ *   bbox        n_frames x 256 x 4 float64 out: the positives' deltas / RPN_BBOX_STD_DEV in anchor order, zero rows after
+ *
+ * rope_seg_roi_targets: DetectionTargetLayer of n_frames frames (float32, normalised coordinates).
+ *   proposals   n_frames x prop_stride x 4 (prop_stride <= 2048), prop_count valid rows each;  keys: n_frames x prop_stride uint32
+ *   gt_boxes    n_frames x gt_stride x 4;  gt_class, gt_count int32;  gt_masks n_frames x gt_stride x mask_h x mask_w bytes (0/1)
+ *   inv_positive_ratio  float32(1 / ROI_POSITIVE_RATIO)
+ *   out, 200 rows per frame (positives by key, negatives by key, zero rows): rois x 4, class_ids, deltas x 4 / BBOX_STD_DEV,
+ *   masks 28 x 28 (round(crop_and_resize) of the matched GT mask over the roi)
+ *
+ * rope_seg_roi_align_float / rope_seg_roi_align_backward: rope_seg_roi_align on float32 rows (no bfloat16 roundings) and its
+ * transpose: grad_out (n_boxes x pool x pool x channels) times each sample's four bilinear weights, added into grad_rows (the
+ * row table's shape, zeroed by the caller) with global float atomics. */
+int rope_seg_rpn_targets(const double *anchors, int n_anchors, const double *gt_boxes, const int32_t *gt_count, int gt_stride,
+                         int n_frames, const uint32_t *keys, double *anchor_max, int32_t *anchor_arg, uint64_t *gt_max, int32_t *match,
+                         double *bbox, void *stream);
+int rope_seg_roi_targets(const float *proposals, const int32_t *prop_count, int prop_stride, const float *gt_boxes, const int32_t *gt_class,
+                         const int32_t *gt_count, int gt_stride, const uint8_t *gt_masks, int mask_h, int mask_w, int n_frames,
+                         const uint32_t *keys, float inv_positive_ratio, float *rois, int32_t *class_ids, float *deltas, float *masks,
+                         void *stream);
+int rope_seg_roi_align_float(const float *rows, const float *boxes, const int32_t *frame, const int32_t *level_hw, const int64_t *level_off,
+                           int n_boxes, int channels, int pool, float inv_level_unit, const float *t, float *out, void *stream);
+int rope_seg_roi_align_backward(const float *grad_out, const float *boxes, const int32_t *frame, const int32_t *level_hw,
+                                const int64_t *level_off, int n_boxes, int channels, int pool, float inv_level_unit, const float *t,
+                                float *grad_rows, void *stream);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

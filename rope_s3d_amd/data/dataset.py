@@ -199,12 +199,25 @@ class SyntheticDataset:
                       'synthetic': True, 'color_dict': self._r.color_dict}
         self.dataset_dir = self.name
         # nothing is stored for a synthetic set: its annotations go under the output folder
-        self.link_anno_path = os.path.join(Paths().OUTPUT, self.name.replace(':', '_'), 'link_annotations')
+        self.link_anno_path = self.link_anno_path_of(self.name)
+
+    @classmethod
+    def parse_name(cls, name: str):
+        """'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' -> (frames, seed, preset), the defaults filled in."""
+        parts = name[len(cls.PREFIX):].split(':')
+        return int(parts[0]), int(parts[1]) if len(parts) > 1 else 7919, parts[2] if len(parts) > 2 else '640_480_color'
+
+    @classmethod
+    def link_anno_path_of(cls, name: str) -> str:
+        """Where the set of that name keeps its annotations (under the output folder, by the name with every default filled in);
+        nothing is rendered."""
+        n, seed, preset = cls.parse_name(name)
+        return os.path.join(Paths().OUTPUT, f'{cls.PREFIX}{n}:{seed}:{preset}'.replace(':', '_'), 'link_annotations')
 
     @classmethod
     def from_name(cls, name: str, device: int = 0):
-        parts = name[len(cls.PREFIX):].split(':')
-        return cls(int(parts[0]), parts[2] if len(parts) > 2 else '640_480_color', seed=int(parts[1]) if len(parts) > 1 else 7919, device=device)
+        n, seed, preset = cls.parse_name(name)
+        return cls(n, preset, seed=seed, device=device)
 
     def frame(self, i: int):
         with self._lock:

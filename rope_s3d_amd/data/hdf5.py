@@ -379,7 +379,17 @@ class H5File:
 # ------------------------------------------------------------------------------------------------ writer
 def _write_attr(loc: int, name: str, value):
     h = lib()
-    if isinstance(value, str):
+    if isinstance(value, (list, tuple)) and value and all(isinstance(v, bytes) for v in value):
+        # a 1-d array of fixed-length byte strings (h5py's layout of np.array([b'...', ...]), as Keras writes its name lists)
+        n = max(len(v) for v in value) or 1
+        tid = h.H5Tcopy(_glob('H5T_C_S1_g'))
+        h.H5Tset_size(tid, n)
+        buf = b''.join(v.ljust(n, b'\0') for v in value)
+        sid = h.H5Screate_simple(1, (_HSZ * 1)(len(value)), None)
+        aid = h.H5Acreate2(loc, name.encode(), tid, sid, 0, 0)
+        rc = h.H5Awrite(aid, tid, C.c_char_p(buf))
+        h.H5Tclose(tid)
+    elif isinstance(value, str):
         tid = h.H5Tcopy(_glob('H5T_C_S1_g'))
         h.H5Tset_size(tid, H5T_VARIABLE)
         h.H5Tset_cset(tid, H5T_CSET_UTF8)
@@ -460,9 +470,10 @@ def write_h5_dataset(path: str, og_img, depthmaps, angles, camera_pose, color_in
     return path
 
 
-def write_arrays(path: str, arrays: dict, attrs: dict = None, gzip=None) -> str:
+def write_arrays(path: str, arrays: dict, attrs: dict = None, gzip=None, group_attrs: dict = None) -> str:
     """A plain HDF5 file of named arrays ({'group/sub/name': ndarray}); groups are created as needed.  gzip: one level for every
-    array, or {name: level} for some of them (the others stored uncompressed)."""
+    array, or {name: level} for some of them (the others stored uncompressed).  group_attrs: {group path: {name: value}} for
+    groups the arrays made; a value may be a list of byte strings."""
     h = lib()
     if os.path.exists(path):
         os.remove(path)
@@ -474,6 +485,15 @@ def write_arrays(path: str, arrays: dict, attrs: dict = None, gzip=None) -> str:
             _write_attr(fid, k, v)
         for name, data in arrays.items():
             _write_array(fid, name, np.asarray(data), gzip.get(name) if isinstance(gzip, dict) else gzip)
+        for g, ga in (group_attrs or {}).items():
+            gid = h.H5Gopen2(fid, g.encode(), 0)
+            if gid < 0:
+                raise IOError(f"{path}: no group '{g}'")
+            try:
+                for k, v in ga.items():
+                    _write_attr(gid, k, v)
+            finally:
+                h.H5Gclose(gid)
     finally:
         h.H5Fclose(fid)
     return path

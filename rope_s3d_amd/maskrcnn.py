@@ -687,14 +687,15 @@ _KERAS_VARS = {'conv': (('weight', 'kernel'), ('bias', 'bias')), 'deconv': (('we
                'bn': (('weight', 'gamma'), ('bias', 'beta'), ('running_mean', 'moving_mean'), ('running_var', 'moving_variance'))}
 
 
-def load_matterport_weights(path: str, num_classes: int = 7) -> dict:
+def load_matterport_weights(path: str, num_classes: int = 7, exclude=()) -> dict:
     """A Keras `save_weights` HDF5 file of Matterport's Mask R-CNN (what PixelLib trains and loads: predict.py:96-98,
     train.py:49) -> state_dict of `MaskRCNN(num_classes)`.
 
     Keras keeps every variable as a dataset `<layer>/<scope>/<var>:0`, possibly below a `model_weights` group and, for
     the RPN, below the nested `rpn_model`; only the last two path components identify a variable, so the file is walked
     and indexed by `<scope>/<var>`.  Missing layers and shape mismatches (e.g. a head trained for another class count)
-    raise with the layer's name."""
+    raise with the layer's name.  `exclude`: Keras layer names not read (PixelLib's head exclusion when the base model was
+    trained for another class count); those keep the fresh initialisation of `MaskRCNN(num_classes)`."""
     try:
         import h5py
         f, found = h5py.File(path, 'r'), {}
@@ -714,6 +715,9 @@ def load_matterport_weights(path: str, num_classes: int = 7) -> dict:
     ref = MaskRCNN(num_classes).state_dict()
     out = {k: v for k, v in ref.items() if k.endswith('num_batches_tracked')}
     for prefix, (layer, kind) in matterport_layer_map(num_classes).items():
+        if layer in exclude:
+            out.update({f'{prefix}.{tname}': ref[f'{prefix}.{tname}'] for tname, _ in _KERAS_VARS[kind]})
+            continue
         for tname, kname in _KERAS_VARS[kind]:
             key = f'{layer}/{kname}'
             if key not in index:
@@ -730,6 +734,50 @@ def load_matterport_weights(path: str, num_classes: int = 7) -> dict:
     missing = set(ref) - set(out)
     assert not missing, missing
     return out
+
+
+def torch_to_keras(kind: str, var: str, value: np.ndarray) -> np.ndarray:
+    """The inverse of `keras_to_torch`."""
+    if var == 'kernel':
+        return np.ascontiguousarray(value.T if kind == 'dense' else value.transpose(2, 3, 1, 0))
+    return np.ascontiguousarray(value)
+
+
+# root attributes Keras' save_weights writes beside layer_names.  keras_version matters to the reader: Keras' HDF5 loader takes a
+# file without it for a Keras 1 file and converts its kernels (preprocess_weights_for_loading), which would transpose
+# mrcnn_mask_deconv's square kernel unnoticed.  2.4.0 is the tf.keras of the TF 2 releases PixelLib runs on.
+KERAS_VERSION, KERAS_BACKEND = '2.4.0', 'tensorflow'
+
+
+def save_matterport_weights(state_dict: dict, path: str, num_classes: int = 7) -> str:
+    """A `MaskRCNN(num_classes)` state_dict as Keras `save_weights` writes Matterport's model, the inverse of
+    `load_matterport_weights`: root attributes `layer_names`, `keras_version` and `backend`, per layer group an attribute
+    `weight_names`, datasets `<layer>/<layer>/<var>:0` (float32) and the RPN's three layers below the nested `rpn_model` group.
+    Layers without weights are not listed.  Written with h5py when it is importable, else with data/hdf5.py."""
+    groups = {}                                                   # Keras layer group -> [(weight name, value)]
+    for prefix, (layer, kind) in matterport_layer_map(num_classes).items():
+        group = 'rpn_model' if prefix.startswith('rpn.') else layer
+        for tname, kname in _KERAS_VARS[kind]:
+            v = state_dict[f'{prefix}.{tname}'].detach().cpu().float().numpy()
+            groups.setdefault(group, []).append((f'{layer}/{kname}:0', torch_to_keras(kind, kname, v)))
+    names = list(groups)
+    try:
+        import h5py
+        with h5py.File(path, 'w') as f:
+            f.attrs['layer_names'] = np.array([n.encode() for n in names])
+            f.attrs['backend'] = KERAS_BACKEND.encode()
+            f.attrs['keras_version'] = KERAS_VERSION.encode()
+            for g in names:
+                grp = f.create_group(g)
+                grp.attrs['weight_names'] = np.array([w.encode() for w, _ in groups[g]])
+                for w, v in groups[g]:
+                    grp.create_dataset(w, data=v)
+    except ImportError:
+        from .data.hdf5 import write_arrays
+        write_arrays(path, {f'{g}/{w}': v for g in names for w, v in groups[g]},
+                     attrs={'layer_names': [n.encode() for n in names], 'backend': KERAS_BACKEND, 'keras_version': KERAS_VERSION},
+                     group_attrs={g: {'weight_names': [w.encode() for w, _ in groups[g]]} for g in names})
+    return path
 
 
 class MaskRCNNSegmenter:

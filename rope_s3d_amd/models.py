@@ -2,19 +2,23 @@
 Predictor.__init__ as `ModelManager().dynamicLoad(dataset=model_ds)`, predict.py:94-98).
 
 Every trained model is a folder `<MODELS>/<id>/` holding `ModelData.json` (id, dataset, sizes, classes, date trained)
-and its Keras checkpoints `*.<epoch>-<loss>.h5`.  This is the read side only: the reference's manager also prunes old
+and its Keras checkpoints `*.<epoch>-<loss>.h5`.  Besides `allocateNew` (a new folder for training) this is the read side: the reference's manager also prunes old
 checkpoints, deletes empty folders and rewrites an index file whenever it is constructed; selecting a model for
 prediction has no business deleting anything, so none of that is done here."""
 import json
 import logging
 import os
+import random
+import string
 from datetime import datetime
+from typing import List
 
 import numpy as np
 
 from .config import Paths
 
 MODELDATA_FILE_NAME = 'ModelData.json'      # constants.py:37
+MODEL_NAME_LENGTH = 4                       # constants.py
 
 _FIELDS = {'id': '', 'dataset': '', 'dataset_size': 0, 'train_size': 0, 'valid_size': 0, 'classes': [], 'epochs_trained': 0,
            'date_trained': '', 'benchmarks': []}
@@ -69,6 +73,31 @@ class ModelManager:
                 data.epochs_trained = max([_epoch_of(x) for x in files if x.endswith('.h5')] + [0])
                 self.info[data.id] = data
         self.num_total = len(self.info)
+
+    def allocateNew(self, dataset: str, classes: List[str], name: str = None) -> str:
+        """A new model folder `<MODELS>/<name>/` with its ModelData.json (models.py:136-178): `name` defaults to a fresh random
+        string of upper-case letters; the train / valid sizes are the file pairs of the dataset's annotation split.  -> the folder."""
+        if name is None:
+            while True:
+                name = ''.join(random.choice(string.ascii_uppercase) for _ in range(MODEL_NAME_LENGTH))
+                if name not in self.info:
+                    break
+        folder = os.path.join(self.dir, name)
+        os.makedirs(folder)
+        from .data.dataset import Dataset, SyntheticDataset
+        if dataset.startswith(SyntheticDataset.PREFIX):          # nothing rendered: the name holds the frame count
+            length = SyntheticDataset.parse_name(dataset)[0]
+            anno = SyntheticDataset.link_anno_path_of(dataset)
+        else:
+            ds = Dataset(dataset)
+            length, anno = ds.length, ds.link_anno_path
+        size = lambda sub: len(os.listdir(os.path.join(anno, sub))) // 2 if os.path.isdir(os.path.join(anno, sub)) else 0
+        md = {'id': name, 'dataset': dataset, 'dataset_size': int(length), 'train_size': size('train'), 'valid_size': size('test'),
+              'classes': list(classes), 'epochs_trained': 0, 'date_trained': str(datetime.now()), 'benchmarks': []}
+        with open(os.path.join(folder, MODELDATA_FILE_NAME), 'w') as f:
+            json.dump(md, f, indent=4)
+        self.update()
+        return folder
 
     def loadByID(self, id: str) -> str:
         """The last checkpoint (by name, i.e. by epoch) of a model (models.py:180-190)."""
