@@ -1,7 +1,9 @@
 """Builds librope_hip.so (gfx950) in-tree with hipcc.  Cross-compiles without a GPU."""
 import os
+import re
 import shutil
 import subprocess
+import tempfile
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB_PATH = os.path.join(_CSRC, 'librope_hip.so')
@@ -58,6 +60,56 @@ def build(force: bool = False, verbose: bool = False, out_name: str = 'librope_h
     with open(os.path.join(_CSRC, out_name) + '.id', 'w') as f:         # beside the library (git-ignored like it): needs_build reads it
         f.write(build_id + '\n')
     return os.path.join(_CSRC, out_name)
+
+
+# Template arguments of raster_score_kernel / raster_queue_kernel<LOSS, MODE, CLIP> by value (include/rope_s3d.h, rope_kernels.h)
+LOSS_NAMES = ('DEPTH', 'FULL', 'LOOKUP', 'TSWEEP', 'CAMFULL')
+MODE_NAMES = ('SCORE', 'DUMP', 'COVER', 'LAYER', 'TABLE', 'SPLIT', 'SPLIT_GEO')
+_REMARK = '-Rpass-analysis=kernel-resource-usage'
+_FIELDS = {'VGPRs': 'vgprs', 'AGPRs': 'agprs', 'TotalSGPRs': 'sgprs', 'VGPRs Spill': 'vgpr_spills', 'SGPRs Spill': 'sgpr_spills',
+           'ScratchSize [bytes/lane]': 'scratch_bytes', 'Occupancy [waves/SIMD]': 'occupancy', 'LDS Size [bytes/block]': 'lds_bytes'}
+
+
+def parse_resource_remarks(text: str) -> list:
+    """The compiler's kernel-resource-usage remarks -> one record per kernel, in the order reported.  The template arguments are
+    read off the Itanium-mangled name, where they stand as literals (raster_queue_kernelILi4ELi0ELb1EE = <4, 0, true>): that
+    needs no demangler, which not every ROCm tree ships."""
+    records, cur = [], None
+    for line in text.splitlines():
+        m = re.search(r'remark:\s+(.*?)\s*\[' + re.escape(_REMARK) + r'\]', line)
+        if not m:
+            continue
+        key, _, value = m.group(1).partition(': ')
+        if key == 'Function Name':
+            t = re.match(r'_ZN4rope\d+(\w+?)ILi(\d+)ELi(\d+)ELb([01])EE', value)
+            n = re.match(r'_ZN4rope\d+([A-Za-z_]\w*?kernel)', value)
+            cur = {'symbol': value, 'kernel': t.group(1) if t else (n.group(1) if n else value), 'loss': None, 'mode': None, 'clip': None}
+            if t:
+                cur.update(loss=LOSS_NAMES[int(t.group(2))], mode=MODE_NAMES[int(t.group(3))], clip=t.group(4) == '1')
+            records.append(cur)
+        elif cur is not None and key in _FIELDS:
+            cur[_FIELDS[key]] = int(value)
+    return records
+
+
+def resource_usage() -> list:
+    """What the compiler says every kernel of rope_kernels.hip needs in the shipped build: a device-only compile with HIPCC_FLAGS
+    (and ROPE_HIPCC_EXTRA, so that a variant is judged by the same rule) plus the resource-usage remarks, into a temporary
+    directory — librope_hip.so is neither read nor written.  -> records {symbol, kernel, loss, mode, clip (None outside the raster
+    templates), vgprs, agprs, sgprs, vgpr_spills, sgpr_spills, scratch_bytes (per lane), occupancy (waves/SIMD), lds_bytes}."""
+    hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    extra = os.environ.get('ROPE_HIPCC_EXTRA', '').split()
+    flags = [f for f in HIPCC_FLAGS if f != '-shared']
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = [hipcc] + flags + [f'-DROPE_BUILD_ID="{source_hash()}"'] + extra + ['--cuda-device-only', '-c', _REMARK, 'rope_kernels.hip',
+                                                                                 '-o', os.path.join(tmp, 'rope_kernels.device.o')]
+        r = subprocess.run(cmd, cwd=_CSRC, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"{' '.join(cmd)} failed ({r.returncode}):\n{r.stderr[-4000:]}")
+    records = parse_resource_remarks(r.stderr)
+    if not records:
+        raise RuntimeError(f"{hipcc} printed no {_REMARK} remarks")
+    return records
 
 
 if __name__ == '__main__':

@@ -20,14 +20,19 @@ namespace rope {
 #define ROPE_MIN_WAVES_PER_SIMD 6
 #endif
 #ifndef ROPE_MIN_WAVES_FULL
-#define ROPE_MIN_WAVES_FULL 6               // the link counts are packed fields (score_pixel): fits 80 VGPRs without spills
+#define ROPE_MIN_WAVES_FULL 6               // the link counts are packed fields (score_pixel): raster_score_kernel fits 80 VGPRs without scratch
 #endif
+// At 6 waves per SIMD every raster_score_kernel instantiation compiles without scratch; the plain raster_queue_kernel ones do not:
+// 12-43 VGPRs spilled into 52-176 B of scratch per lane, and raster_queue_kernel<CAMFULL, SCORE, plain> 218 VGPRs into 204 B
+// (profiles/kernel_resources_gfx950.txt).  tests/test_kernel_resources.py pins those numbers at build time, and
+// tests/test_gpu_instantiations.py holds every queue kernel to its scratch-free raster_score_kernel twin (STRATEGY_NO_QUEUE).
 // The instantiations that can clip at the near plane: ONE workgroup per CU (3 waves per SIMD, up to 168 VGPRs), so that they
 // compile without scratch.  At 6 waves per SIMD (80 VGPRs) they spill 65-69 VGPRs and 61-63 SGPRs into 200-216 bytes of scratch
 // per lane, and the layer-queue kernel of that build, raster_queue_kernel<DEPTH, LAYER, CLIP>, gave sums that differed from run
 // to run on a scene without a single triangle near the plane (round 3: tools/dbg_clip.py, profiles/r03_clip_fault.txt; same
 // source, no scratch: deterministic and bit-equal to the plain kernels).  They are the rare path — a camera within the robot's
-// reach of the near plane — and correctness there is worth more than occupancy.
+// reach of the near plane — and correctness there is worth more than occupancy.  Three of the nine CLIP queue kernels need 166-168
+// of the 168 VGPRs: tests/test_kernel_resources.py fails as soon as one of them uses scratch again.
 #ifndef ROPE_MIN_WAVES_CLIP
 #define ROPE_MIN_WAVES_CLIP 3
 #endif
