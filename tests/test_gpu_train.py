@@ -117,7 +117,8 @@ def _boxes_all_levels(K, seed=0):
 
 def test_roi_align_f32_forward_and_backward():
     """Forward: bit-equal to maskrcnn._roi_align's tensor formulation on float32 rows (the same IEEE operations in the same
-    order).  Backward: within relative 1e-5 of autograd through that formulation (atomic adds sum in another order)."""
+    order).  Backward: within relative 1e-5 of autograd through that formulation (atomic adds sum in another order); the tight
+    per-element bound, other channel counts and non-square levels are in tests/test_gpu_train_kernels.py."""
     from rope_s3d_amd import maskrcnn as mr
     from rope_s3d_amd import training as tr
     torch.cuda.init()
