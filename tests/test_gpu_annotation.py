@@ -83,6 +83,27 @@ def test_masks_equal_host_dilation(preset, ds):
     assert seen == 0b111111                                   # every link's bit was drawn somewhere
 
 
+@pytest.mark.parametrize('W,H', [(131, 37), (126, 45)])
+def test_masks_at_widths_off_a_multiple_of_four(W, H):
+    """Sizes no preset produces (rope_set_camera admits any): at W % 4 != 0 the label planes are stored byte by byte and the last
+    word of a row is partial; pad 64 is the tallest halo."""
+    from rope_s3d_amd.projection import Intrinsics, view_matrix
+    e, _, _ = make_engine('640_480_color', 1)
+    it = Intrinsics('640_480_color')
+    dx, dy = 640 / W, 480 / H                                 # the preset's whole view on W x H pixels that are not square
+    P = np.zeros((4, 4))
+    P[0, 0], P[1, 1] = 2 * it.fx / dx / W, 2 * it.fy / dy / H
+    P[0, 2], P[1, 2] = 1 - 2 * it.cx / dx / W, 2 * it.cy / dy / H - 1
+    P[2, 2], P[2, 3], P[3, 2] = (ZFAR + ZNEAR) / (ZNEAR - ZFAR), 2 * ZFAR * ZNEAR / (ZNEAR - ZFAR), -1
+    e.set_camera(P @ view_matrix(np.asarray(DEFAULT_CAMERA_POSE, float)), W, H, ZNEAR, ZFAR)
+    assert (e.W, e.H) == (W, H) and W % 4
+    q = slu_poses(5, 9)
+    seen = 0
+    for pad in (3, 64):
+        seen |= np.bitwise_or.reduce(check(e, q, 6, np.arange(6), pad), axis=None)
+    assert seen == 0b111111
+
+
 def test_chunk_boundary_fullsize():
     """160 poses at 1280x720 need two chunks (256 MiB for the id and label planes of each pose)."""
     e, intr, _ = make_engine('1280_720_color', 1)
