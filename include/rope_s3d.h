@@ -339,6 +339,34 @@ int rope_lookup_score_targets(rope_ctx *ctx, int32_t *best_idx, double *best_sco
 int rope_stage_targets(rope_ctx *ctx, int n_frames, const uint64_t *tq, const float *t32, const float *t32_tsweep, const uint8_t *link_flags);
 int rope_commit_targets(rope_ctx *ctx);
 
+/* The staged set filled ON THE DEVICE from instance masks that are there already (a segmenter on the same GPU): per frame what
+ * rope_prepare_segmented computes at f == 1 — the merge of a link's instances, both body masks erode7(dilate8(.)), the masked depth,
+ * the packing and the flags — by kernels enqueued on `stream`, the caller's (for example the one the segmenter ran on), with no
+ * host synchronisation in the call.  Down-sampling stays with the caller (rope_downsample_even).
+ *   n_total, slot0, n_frames   the staged set holds n_total frames; this call fills slots slot0 .. slot0 + n_frames - 1.  The call
+ *                with slot0 == 0 starts and sizes a set; the others must name the same n_total and want_tsweep.  The set is
+ *                complete, and rope_commit_targets takes it, once every slot has been filled.
+ *   depth_dev    n_frames planes H x W (the image size of rope_set_camera), float32 (depth_kind 1) or float64 (2), DEVICE
+ *   masks_dev    K_total = inst_first[n_frames] planes H x W of bytes, non-zero = inside the instance (a torch.bool tensor
+ *                (K, H, W)), DEVICE; may be NULL when K_total == 0
+ *   inst_first   n_frames + 1 offsets into the planes: frame i owns planes inst_first[i] .. inst_first[i + 1] - 1, HOST
+ *   link_of      K_total link indices, -1 for an instance that is none of the rendered links (it still widens the body), HOST
+ *   n_lookup_links  links 0 .. n_lookup_links - 1 make up the lookup plane's body;  want_tsweep: also the TensorSweep plane
+ * rope_commit_targets waits for every stream such a call used since the last commit before it swaps the sets.  Like
+ * rope_stage_targets the call touches nothing the evaluation calls use and may run on another thread.  ROPE_E_ARG for a null
+ * pointer where instances exist, slots outside the set, a non-monotone inst_first, link_of outside -1 .. n_links - 1,
+ * n_lookup_links outside 0 .. n_links, an unknown depth_kind, or a changed n_total in mid-set.  A refused call changes nothing:
+ * a staging that waits for its commit still does, a set half filled can be continued.  A call that goes through writes the staged
+ * planes, so it withdraws any staging that was complete (also one of rope_stage_targets): rope_commit_targets answers ROPE_E_ARG
+ * until every slot of the set has been filled. */
+int rope_stage_targets_segmented(rope_ctx *ctx, int n_total, int slot0, int n_frames, const void *depth_dev, int depth_kind,
+                                 const uint8_t *masks_dev, const int32_t *inst_first, const int32_t *link_of, int n_lookup_links,
+                                 int want_tsweep, void *stream);
+
+/* The resident set of targets (rope_set_targets / rope_commit_targets) back to the host, for tests: n_frames planes each and
+ * n_frames x 8 flag bytes; any pointer may be NULL. */
+int rope_debug_targets(rope_ctx *ctx, uint64_t *tq, float *t32, float *t32_tsweep, uint8_t *flags);
+
 /* rope_predict for the n_frames resident targets of rope_set_targets, in lockstep: the same stage list, limits and camera for all of
  * them (args as rope_predict; lookup_angles_live must be NULL — the table aliasing makes frames depend on their order — and so must
  * on_eval).  A frame

@@ -54,8 +54,9 @@ def run(args):
             from rope_s3d_amd.maskrcnn import load_matterport_weights
             sd = load_matterport_weights(args.weights) if args.weights.endswith('.h5') else torch.load(args.weights, map_location='cpu')
         from rope_s3d_amd.maskrcnn import BatchAheadSegmenter
-        kwargs['segmenter'] = BatchAheadSegmenter(MaskRCNNSegmenter(7, device=f'cuda:{gpu}', state_dict=sd,
-                                                                    min_confidence=0.7 if sd is not None else 0.0), batch=8)
+        net = MaskRCNNSegmenter(7, device=f'cuda:{gpu}', state_dict=sd, min_confidence=0.7 if sd is not None else 0.0)
+        # -device_targets: the Predictor asks the network itself, in sub-batches, and builds the targets where its masks are
+        kwargs['segmenter'] = net if getattr(args, 'device_targets', False) else BatchAheadSegmenter(net, batch=8)
     elif getattr(args, 'segmenter', None) == 'color':
         # colour-coded frames through the SEGMENTATION path (_segmentLoad: instance merge, dilate 8 / erode 7 body mask) with
         # exact masks in place of the network's: the whole of configs[2] minus the network's own errors
@@ -66,6 +67,8 @@ def run(args):
         kwargs['color_dict'] = ds.attrs['color_dict']         # link masks are read from the colour render
     if getattr(args, 'lookup_divisions', None):                # default: the reference's size rule (simulation/lookup.py)
         kwargs['lookup_divisions'] = int(args.lookup_divisions)
+    if getattr(args, 'device_targets', False):
+        kwargs['device_targets'] = True
     am = Predictor(ds_factor=args.ds_factor, camera_pose=ds.camera_pose[0], preview=False, base_intrin=ds.intrinsics,
                    do_angles=args.angs, model_ds=args.dataset, device=gpu, **kwargs)
     # Frames are independent (predict_dataset.py:43-44 is a plain loop; fresh state per frame, predict.py:144-148): ONE Predictor
@@ -144,5 +147,8 @@ if __name__ == "__main__":
                              "one Predictor walking -batch frames in lockstep.")
     parser.add_argument('-batch', type=int, default=None,
                         help="Frames that walk the stage list in lockstep (one device batch per step over all of them); default: by frame size, 16..1024; 1: frame after frame.")
+    parser.add_argument('-device_targets', action='store_true',
+                        help="With -segmenter maskrcnn: the network's masks stay on the GPU and the targets are built there "
+                             "(Predictor(device_targets=True)); other segmenters do not offer that and run as without the flag.")
     parser.add_argument('-weights', type=str, default=None, help="weights for -segmenter maskrcnn: the reference's trained Keras .h5 or a torch state_dict (random weights otherwise).")
     run(parser.parse_args())

@@ -176,6 +176,17 @@ struct rope_ctx {
     int staged_n = 0, staged_W = 0, staged_H = 0;
     std::string stage_err;                  // rope_stage_targets may run beside an evaluation: its own message
     bool staged_t32 = false, staged_ts = false;
+    // rope_stage_targets_segmented: the staged set filled slot by slot by kernels on the CALLER's streams.  One event per call,
+    // which rope_commit_targets waits for; the calls' small tables (plane offsets, link codes) go up through a page-locked block
+    // that is only ever appended to while a set is being filled, so no call waits for the one before it.
+    std::vector<hipEvent_t> stage_events;
+    unsigned long long *s_counts = nullptr;   // per staged frame: n_mask, n_depth per link
+    int s_counts_cap = 0;
+    int32_t *h_meta = nullptr, *d_meta = nullptr;
+    size_t meta_cap = 0, meta_used = 0;       // int32 words
+    std::vector<uint8_t> seg_filled;          // per slot of the set being filled
+    int seg_n_total = 0, seg_n_filled = 0;    // seg_n_total 0: no set is being filled
+    bool seg_ts = false;
     int tg_crop[4][4] = {};
     int32_t *d_frame_of = nullptr, *h_frame_of = nullptr, *d_frame_of_host = nullptr;   // rows' frame indices: device copy / mapped host memory (small batches)
     int frame_of_cap = 0;
@@ -371,12 +382,14 @@ extern "C" void rope_destroy(rope_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    for (hipEvent_t e : c->stage_events) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
+    c->stage_events.clear();
     void *ptrs[] = {c->d_header, c->d_tris, c->d_verts, c->d_joint_fixed, c->d_joint_axes, c->d_PV, c->d_tq, c->d_t32,
                     c->d_cand, c->d_err, c->d_best_err, c->d_mvp, c->d_bounds, c->d_mask_lo, c->d_mask_hi, c->d_layer_of, c->d_layer_rep, c->d_layers, c->d_layer_sums, c->d_parent_of, c->d_parent_rep, c->d_parents, c->d_table, c->d_tcount, c->d_toff, c->d_tused, c->d_tgoff, c->d_tgval, c->d_ttotal, c->d_zero_total, c->d_tsums, c->d_terr, c->d_qitems, c->d_tile_tris, c->d_tile_tris_lo, c->d_qctr, c->d_touched, c->d_gtile, c->d_aabb, c->d_sums, c->d_best_idx,
                     c->d_rdepth, c->d_rids, c->d_rmask, c->d_rboxes, c->d_cover, c->d_ftq, c->d_ftl, c->d_ftotal, c->d_fempty, c->d_ft32, c->d_vstage, c->d_empty[0], c->d_empty[1], c->d_empty[2], c->d_empty[3],
                     c->d_total[0], c->d_total[1], c->d_total[2], c->d_total[3], c->d_fts32, c->d_fflags, c->d_tg_total[0], c->d_tg_total[1], c->d_tg_total[2],
                     c->d_tg_total[3], c->d_tg_empty, c->d_frame_of, c->d_tg_t32c, c->d_tg_ltotal, c->d_tg_scores, c->d_tg_best, c->d_t32ts, c->d_tc,
-                    c->s_ftq, c->s_ft32, c->s_fts32, c->s_fflags};
+                    c->s_ftq, c->s_ft32, c->s_fts32, c->s_fflags, c->s_counts, c->d_meta};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -387,6 +400,7 @@ extern "C" void rope_destroy(rope_ctx *c)
     if (c->h_vsums) (void)hipHostFree(c->h_vsums);
     if (c->h_copy) (void)hipHostFree(c->h_copy);
     if (c->h_copy2) (void)hipHostFree(c->h_copy2);
+    if (c->h_meta) (void)hipHostFree(c->h_meta);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1911,6 +1925,18 @@ extern "C" int rope_set_targets(rope_ctx *c, int n_frames, const uint64_t *tq, c
     return ROPE_OK;
 }
 
+// waits for everything rope_stage_targets_segmented enqueued on its callers' streams
+static int drain_stage_events(rope_ctx *c)
+{
+    int rc = ROPE_OK;
+    for (hipEvent_t e : c->stage_events) {
+        if (hipEventSynchronize(e) != hipSuccess) rc = ROPE_E_HIP;
+        (void)hipEventDestroy(e);
+    }
+    c->stage_events.clear();
+    return rc;
+}
+
 // The same targets as rope_set_targets, but into the context's SECOND set of planes and on a stream of its own: returns once the
 // copies are enqueued (page-locked sources, rope_host_alloc) — the resident set stays in use meanwhile, from this or another thread
 // (this call touches nothing the evaluation calls use).  The host buffers belong to the copy until rope_commit_targets returns.
@@ -1925,6 +1951,8 @@ extern "C" int rope_stage_targets(rope_ctx *c, int n_frames, const uint64_t *tq,
     if (hipSetDevice(c->device) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets: hipSetDevice failed");
     if (!c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets: no stream");
     if (hipStreamSynchronize(c->copy_stream) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets: the upload stream failed");
+    if (drain_stage_events(c)) return fail(ROPE_E_HIP, "rope_stage_targets: a staging kernel failed");     // of a set left unfinished
+    c->seg_n_total = 0;
     c->staged_n = 0;
     const int W = c->fp.W, H = c->fp.H;
     const size_t plane = (size_t)W * H, n = plane * (size_t)n_frames;
@@ -1956,6 +1984,133 @@ extern "C" int rope_stage_targets(rope_ctx *c, int n_frames, const uint64_t *tq,
     return ROPE_OK;
 }
 
+// The staged set filled on the DEVICE, slots slot0 .. slot0 + n_frames - 1 of n_total: the segmentation path's targets from instance
+// masks that are in HBM already (rope_targets.hip: what rope_prepare_segmented computes per frame at f == 1).  The kernels go onto
+// `stream`, the caller's, behind the work that produced the masks; the call does not wait for them — rope_commit_targets does.
+extern "C" int rope_stage_targets_segmented(rope_ctx *c, int n_total, int slot0, int n_frames, const void *depth_dev, int depth_kind,
+                                            const uint8_t *masks_dev, const int32_t *inst_first, const int32_t *link_of, int n_lookup_links,
+                                            int want_tsweep, void *stream)
+{
+    if (!c) return ROPE_E_ARG;
+    auto fail = [&](int code, const char *msg) { c->stage_err = msg; return code; };
+    c->stage_err.clear();
+    // the arguments first: a refused call changes nothing, neither a staging that waits for its commit nor a set half filled
+    if (!c->have_camera || !c->have_robot) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: robot and camera must be set first");
+    if (n_total < 1 || n_total > 65535 || n_frames < 1 || slot0 < 0 || slot0 > n_total || n_frames > n_total - slot0)
+        return fail(ROPE_E_ARG, "rope_stage_targets_segmented: need 1 <= n_total <= 65535 and slots slot0 .. slot0 + n_frames - 1 inside it");
+    if (depth_kind != 1 && depth_kind != 2) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: depth_kind is 1 (float32) or 2 (float64)");
+    if (!depth_dev || !inst_first) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: depth_dev and inst_first are required");
+    if (n_lookup_links < 0 || n_lookup_links > c->n_links) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: n_lookup_links outside 0 .. n_links");
+    if (inst_first[0] < 0) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: inst_first not monotone");
+    for (int i = 0; i < n_frames; i++)
+        if (inst_first[i + 1] < inst_first[i]) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: inst_first not monotone");
+    const int K = inst_first[n_frames];
+    if (K > 0 && (!masks_dev || !link_of)) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: instances without masks_dev / link_of");
+    for (int k = 0; k < K; k++)
+        if (link_of[k] < -1 || link_of[k] >= c->n_links) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: link_of outside -1 .. n_links - 1");
+    const int W = c->fp.W, H = c->fp.H;
+    const bool ts = want_tsweep != 0;
+    if (slot0 > 0 && (c->seg_n_total != n_total || c->seg_ts != ts || c->staged_W != W || c->staged_H != H))
+        return fail(ROPE_E_ARG, "rope_stage_targets_segmented: n_total, want_tsweep or the image size changed in mid-set (slot0 == 0 starts a set)");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: hipSetDevice failed");
+    c->staged_n = 0;                              // the staged planes are written from here on: complete again when every slot is filled
+    const size_t plane = (size_t)W * H;
+    if (slot0 == 0) {                             // a new set: sized here, once
+        c->seg_n_total = 0;
+        if (c->copy_stream && hipStreamSynchronize(c->copy_stream) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: the upload stream failed");
+        if (drain_stage_events(c)) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: a staging kernel failed");   // of a set left unfinished
+        const size_t n = plane * (size_t)n_total;
+        bool ok = true;
+        auto grow = [&](auto **p, size_t &cap, size_t want) {
+            if (want <= cap) return;
+            cap = 0;
+            if (realloc_dev(p, want) != hipSuccess) { ok = false; return; }
+            cap = want;
+        };
+        grow(&c->s_ftq, c->s_frames_cap, n);
+        grow(&c->s_ft32, c->s_t32_cap, n);
+        if (ts) grow(&c->s_fts32, c->s_fts_cap, n);
+        if (n_total > c->s_fflags_cap) {
+            c->s_fflags_cap = 0;
+            if (realloc_dev(&c->s_fflags, (size_t)n_total) == hipSuccess) c->s_fflags_cap = n_total; else ok = false;
+        }
+        if (n_total > c->s_counts_cap) {
+            c->s_counts_cap = 0;
+            if (realloc_dev(&c->s_counts, (size_t)n_total * 2 * ROPE_MAX_LINKS) == hipSuccess) c->s_counts_cap = n_total; else ok = false;
+        }
+        if (!ok) { (void)hipGetLastError(); return fail(ROPE_E_NOMEM, "rope_stage_targets_segmented: out of device memory"); }
+        c->meta_used = 0;
+        c->seg_filled.assign((size_t)n_total, 0);
+        c->seg_n_filled = 0;
+        c->seg_ts = ts;
+        c->staged_W = W; c->staged_H = H;
+        c->seg_n_total = n_total;
+    }
+    // this call's tables, appended: plane offsets | links present per frame | code per plane
+    const size_t need = 2 * (size_t)n_frames + 1 + (size_t)K;
+    if (c->meta_used + need > c->meta_cap) {      // the kernels in flight read the old block: wait for them, then start a larger one
+        if (drain_stage_events(c)) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: a staging kernel failed");
+        const size_t cap = std::max<size_t>(std::max<size_t>(2 * c->meta_cap, need), 4096);
+        c->meta_cap = c->meta_used = 0;
+        if (c->h_meta) { (void)hipHostFree(c->h_meta); c->h_meta = nullptr; }
+        if (hipHostMalloc((void **)&c->h_meta, cap * sizeof(int32_t), hipHostMallocDefault) != hipSuccess || realloc_dev(&c->d_meta, cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ROPE_E_NOMEM, "rope_stage_targets_segmented: out of memory");
+        }
+        c->meta_cap = cap;
+    }
+    int32_t *m = c->h_meta + c->meta_used;
+    for (int i = 0; i <= n_frames; i++) m[i] = inst_first[i];
+    for (int i = 0; i < n_frames; i++) {
+        int present = 0;
+        for (int k = inst_first[i]; k < inst_first[i + 1]; k++)
+            if (link_of[k] >= 0) present |= 1 << link_of[k];
+        m[n_frames + 1 + i] = present;
+    }
+    for (int k = 0; k < K; k++)
+        m[2 * n_frames + 1 + k] = 0x200 | (link_of[k] >= 0 ? (1 << link_of[k]) | (link_of[k] < n_lookup_links ? 0x100 : 0) : 0);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int32_t *meta_dev = c->d_meta + c->meta_used;
+    if (hipMemcpyAsync(c->d_meta + c->meta_used, m, need * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(ROPE_E_HIP, "rope_stage_targets_segmented: hipMemcpyAsync failed");
+    c->meta_used += need;
+    const size_t o = plane * (size_t)slot0;
+    hipEvent_t done = nullptr;
+    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: no event");
+    c->stage_events.push_back(done);              // recorded or not, the next wait gets rid of it
+    if (launch_segmented_targets(st, H, W, n_frames, depth_dev, depth_kind, masks_dev, meta_dev, c->n_links, c->s_ftq + o, c->s_ft32 + o,
+                                 ts ? c->s_fts32 + o : nullptr, c->s_counts + (size_t)slot0 * 2 * ROPE_MAX_LINKS, c->s_fflags + slot0) != hipSuccess ||
+        hipEventRecord(done, st) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ROPE_E_HIP, "rope_stage_targets_segmented: the launch failed");
+    }
+    for (int i = slot0; i < slot0 + n_frames; i++)
+        if (!c->seg_filled[i]) { c->seg_filled[i] = 1; c->seg_n_filled++; }
+    if (c->seg_n_filled == n_total) {
+        c->staged_t32 = true;
+        c->staged_ts = ts;
+        c->staged_n = n_total;
+    }
+    return ROPE_OK;
+}
+
+// The resident set of targets back to the host, for tests: tq / t32 / t32_tsweep n_targets planes, flags n_targets x 8 bytes; any
+// may be NULL.
+extern "C" int rope_debug_targets(rope_ctx *c, uint64_t *tq, float *t32, float *t32_tsweep, uint8_t *flags)
+{
+    if (!c) return ROPE_E_ARG;
+    if (c->n_targets < 1) ARG_FAIL(c, "rope_debug_targets: no targets set (rope_set_targets / rope_commit_targets)");
+    if ((t32 && !c->targets_t32) || (t32_tsweep && !c->targets_ts)) ARG_FAIL(c, "rope_debug_targets: the resident set has no such float32 planes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->fp.W * c->fp.H * (size_t)c->n_targets;
+    int rc = ROPE_OK;
+    if (tq) rc = copy_d2h_staged(c, tq, c->d_ftq, n * sizeof(uint64_t));
+    if (!rc && t32) rc = copy_d2h_staged(c, t32, c->d_ft32, n * sizeof(float));
+    if (!rc && t32_tsweep) rc = copy_d2h_staged(c, t32_tsweep, c->d_fts32, n * sizeof(float));
+    if (!rc && flags) rc = copy_d2h_staged(c, flags, c->d_fflags, 8 * (size_t)c->n_targets);
+    return rc;
+}
+
 // The staged set becomes the resident one (and the resident planes the next staging space): waits for the upload and for the
 // context's own stream, then swaps.
 extern "C" int rope_commit_targets(rope_ctx *c)
@@ -1964,7 +2119,9 @@ extern "C" int rope_commit_targets(rope_ctx *c)
     if (c->staged_n < 1) { c->err = c->stage_err.empty() ? "rope_commit_targets: nothing staged (rope_stage_targets)" : c->stage_err; return ROPE_E_ARG; }
     if (c->staged_W != c->fp.W || c->staged_H != c->fp.H) { c->staged_n = 0; ARG_FAIL(c, "rope_commit_targets: the image size changed since rope_stage_targets"); }
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+    if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+    if (drain_stage_events(c)) { c->staged_n = 0; c->seg_n_total = 0; c->err = "rope_commit_targets: a staging kernel failed"; return ROPE_E_HIP; }
+    c->seg_n_total = 0;                           // the set is taken: a later rope_stage_targets_segmented starts at slot 0
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const int n_frames = c->staged_n;
     c->staged_n = 0;

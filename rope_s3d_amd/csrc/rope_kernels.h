@@ -220,4 +220,15 @@ constexpr int ROPE_MASK_MAX_PAD = 64;
 hipError_t launch_masks(hipStream_t st, const uint8_t *ids, int n, int H, int W, const uint8_t *lut, int pad, uint8_t *masks,
                         int32_t *boxes);
 
+// rope_targets.hip: the segmentation path's targets of n_frames frames from device-resident instance masks, what
+// rope_prepare_segmented computes per frame at f == 1.  depth: n_frames planes H x W (kind 1 float32 / 2 float64); masks: instance
+// planes H x W, non-zero = set; meta (device, int32): n_frames + 1 plane offsets, then per frame the bits of the links that have an
+// instance, then per plane its link bit | 0x100 (a lookup link) | 0x200; counts: n_frames x 2 x ROPE_MAX_LINKS words of scratch
+// (n_mask, n_depth per link; cleared here); ts may be null.  One workgroup per tile of this size and frame.
+#define ROPE_TARGET_TILE_W 64
+#define ROPE_TARGET_TILE_H 32
+hipError_t launch_segmented_targets(hipStream_t st, int H, int W, int n_frames, const void *depth, int depth_kind, const uint8_t *masks,
+                                    const int32_t *meta, int n_links, uint64_t *tq, float *t32, float *ts, unsigned long long *counts,
+                                    LinkFlags *flags);
+
 }  // namespace rope

@@ -26,7 +26,9 @@ ABI_SYMBOLS = (
     'rope_seg_rpn_targets', 'rope_seg_roi_targets', 'rope_seg_roi_align_float', 'rope_seg_roi_align_backward',
     'rope_set_target_tsweep', 'rope_set_targets', 'rope_stage_targets', 'rope_commit_targets', 'rope_eval_targets', 'rope_lookup_score_targets', 'rope_predict_batch',
     'rope_prepare_synthetic', 'rope_host_alloc', 'rope_host_free', 'rope_build_id', 'rope_camera_matrix', 'rope_lookup_grid', 'rope_crop_divisions',
-    'rope_prepare_segmented')
+    'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets')
+
+TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
 
 STAGE_LOOKUP, STAGE_DESCENT, STAGE_SFLIP, STAGE_ISWEEP, STAGE_TSWEEP = 0, 1, 2, 3, 4
@@ -142,6 +144,8 @@ def load_library(path: str = None):
     lib.rope_set_targets.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_stage_targets.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_commit_targets.argtypes = [vp]
+    lib.rope_stage_targets_segmented.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, vp]
+    lib.rope_debug_targets.argtypes = [vp, vp, vp, vp, vp]
     lib.rope_eval_targets.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.rope_lookup_score_targets.argtypes = [vp, vp, vp, vp]
     lib.rope_predict_batch.argtypes = [vp, C.POINTER(PredictArgs), i32, vp, vp, C.POINTER(C.c_int64)]
@@ -394,6 +398,48 @@ class Engine:
         self._check(self._lib.rope_commit_targets(self._ctx), 'rope_commit_targets')
         self.n_targets = self._staged[0] if getattr(self, '_staged', None) else 0
         self._staged = None
+
+    def stage_targets_segmented(self, depth_t, masks_t, inst_first, link_of, n_lookup: int, n_total: int, slot0: int = 0,
+                                want_tsweep: bool = False):
+        """rope_stage_targets_segmented: slots slot0 .. slot0 + B - 1 of a staged set of n_total frames, built on the device from
+        torch tensors that are there already — depth_t (B, H, W) float32 / float64, masks_t (K_total, H, W) bool or uint8 (instance
+        planes, frame-major; None when K_total == 0) — by kernels on torch's current stream, with no wait for them: they run behind
+        whatever produced the masks.  inst_first: B + 1 plane offsets, link_of: K_total link indices (-1: none of the rendered links).
+        The tensors are kept alive until commit_targets()."""
+        import torch
+        kind = {torch.float32: 1, torch.float64: 2}.get(depth_t.dtype)
+        if kind is None or depth_t.dim() != 3 or tuple(depth_t.shape[1:]) != (self.H, self.W) or not depth_t.is_contiguous():
+            raise ValueError(f"depth planes must be contiguous (B, {self.H}, {self.W}) float32 / float64, got {tuple(depth_t.shape)} {depth_t.dtype}")
+        if depth_t.device.type != 'cuda' or depth_t.device.index != self.device:
+            raise ValueError(f"depth planes must be on cuda:{self.device}, got {depth_t.device}")
+        first = np.ascontiguousarray(inst_first, np.int32).reshape(-1)
+        links = np.ascontiguousarray(link_of, np.int32).reshape(-1)
+        if len(first) != depth_t.shape[0] + 1 or (len(first) and len(links) != first[-1]):
+            raise ValueError("inst_first holds one offset per frame and one more; link_of one entry per instance plane")
+        masks_ptr = None
+        if masks_t is not None and masks_t.numel():
+            if masks_t.dtype not in (torch.bool, torch.uint8) or masks_t.dim() != 3 or tuple(masks_t.shape[1:]) != (self.H, self.W) \
+                    or not masks_t.is_contiguous() or masks_t.device != depth_t.device or masks_t.shape[0] < len(links):
+                raise ValueError(f"instance planes must be contiguous (K, {self.H}, {self.W}) bool / uint8 beside the depth, K >= {len(links)}")
+            masks_ptr = C.c_void_p(masks_t.data_ptr())
+        if slot0 == 0 or getattr(self, '_staged', None) is None or not isinstance(self._staged[1], list):
+            self._staged = (int(n_total), [])
+        self._staged[1].append((depth_t, masks_t))
+        rc = self._lib.rope_stage_targets_segmented(self._ctx, int(n_total), int(slot0), int(depth_t.shape[0]), C.c_void_p(depth_t.data_ptr()), kind,
+                                                    masks_ptr, _p(first), _p(links) if len(links) else None, int(n_lookup), int(bool(want_tsweep)),
+                                                    C.c_void_p(torch.cuda.current_stream(depth_t.device).cuda_stream))
+        if rc:
+            raise EngineError(f"rope_stage_targets_segmented failed ({rc})")
+
+    def debug_targets(self, want_tsweep: bool = False):
+        """rope_debug_targets: the resident set back on the host -> (tq (N,H,W) uint64, t32 (N,H,W) float32, tsweep planes or None,
+        flags (N,8) uint8), for tests."""
+        n = self.n_targets
+        tq, t32 = np.empty((n, self.H, self.W), np.uint64), np.empty((n, self.H, self.W), np.float32)
+        ts = np.empty((n, self.H, self.W), np.float32) if want_tsweep else None
+        flags = np.empty((n, 8), np.uint8)
+        self._check(self._lib.rope_debug_targets(self._ctx, _p(tq), _p(t32), _p(ts), _p(flags)), 'rope_debug_targets')
+        return tq, t32, ts, flags
 
     def eval_targets(self, cand, frame_of, n_render: int, loss: int, crop=None) -> np.ndarray:
         """Row i of `cand` scored against the resident target frame_of[i] -> errors (R,)."""

@@ -430,13 +430,17 @@ class MaskRCNN(nn.Module):
         return self.detect_batch([image_rgb])[0]
 
     @torch.no_grad()
-    def detect_batch(self, images):
+    def detect_batch(self, images, on_device: bool = False):
         """Several frames of one size at once: the convolutional trunk (backbone, FPN, RPN heads — the dense contraction)
         runs on the whole batch, proposals / RoIAlign / heads / un-moulding then per frame.  Same results per frame as
-        `detect` up to the batch-size dependence of the convolution algorithms the library picks."""
+        `detect` up to the batch-size dependence of the convolution algorithms the library picks.
+        on_device: the masks stay where they were computed, per frame a (K, H, W) bool tensor on the images' device (instance-major
+        planes, what Engine.stage_targets_segmented takes) instead of (H, W, K) in host memory; class ids and scores as ever, and
+        as a fourth item (all frames' planes as one (K_total, H, W) tensor, this frame's first plane in it), or None when no frame
+        has an instance."""
         x, geo = self._mould(images)
         feats_all, probs, deltas = self._trunk_replayed(x)
-        return self._detect(feats_all, probs, deltas, *geo)
+        return self._detect(feats_all, probs, deltas, *geo, on_device=on_device)
 
     def _mould(self, images):
         """resize_image(mode='square') + mold_image of a batch -> (B, 3, size, size) in the weights' dtype, and the geometry to undo it."""
@@ -453,7 +457,7 @@ class MaskRCNN(nn.Module):
         return x.to(wdt).contiguous(), (H, W, scale, top, left, nh, nw)
 
     @torch.no_grad()
-    def detect_batches(self, batches):
+    def detect_batches(self, batches, on_device: bool = False):
         """`detect_batch` of every batch of an iterable, in order (a generator).  On the GPU the trunk of batch i+1 is put on a
         second stream before the box steps of batch i start: those steps are many short launches and a few waits of the host
         for the device, which leave the GPU idle most of the time — the next trunk runs in those gaps.  Same operations on the
@@ -463,9 +467,9 @@ class MaskRCNN(nn.Module):
         if first is None:
             return
         if first[0].device.type != 'cuda':
-            yield self.detect_batch(first)
+            yield self.detect_batch(first, on_device)
             for b in it:
-                yield self.detect_batch(b)
+                yield self.detect_batch(b, on_device)
             return
         if not hasattr(self, '_side'):
             self._side = torch.cuda.Stream(first[0].device)
@@ -489,7 +493,7 @@ class MaskRCNN(nn.Module):
             main.wait_event(done)
             for t in (*feats, probs, deltas):
                 t.record_stream(main)
-            return self._detect(feats, probs, deltas, *geo)
+            return self._detect(feats, probs, deltas, *geo, on_device=on_device)
 
         token = start(first)
         for b in it:
@@ -542,7 +546,7 @@ class MaskRCNN(nn.Module):
         graph.replay()
         return static_out
 
-    def _detect(self, feats, probs, deltas, H, W, scale, top, left, nh, nw):
+    def _detect(self, feats, probs, deltas, H, W, scale, top, left, nh, nw, on_device: bool = False):
         """Proposal layer, pyramid RoIAlign, classifier head, detection layer, mask head and un-moulding for all B frames
         of the batch together: every step works on the concatenation of the frames' boxes with a frame index beside
         them; only the final split of the masks is per frame."""
@@ -572,9 +576,10 @@ class MaskRCNN(nn.Module):
         refined = torch.stack([refined[:, 0].clamp(nwin[0], nwin[2]), refined[:, 1].clamp(nwin[1], nwin[3]),
                                refined[:, 2].clamp(nwin[0], nwin[2]), refined[:, 3].clamp(nwin[1], nwin[3])], 1)
         cand = ((cls_id > 0) & (score >= self.min_conf)).nonzero().squeeze(1)
-        empty = (torch.zeros(0, dtype=torch.long), torch.zeros(0), torch.zeros((H, W, 0), dtype=torch.bool))
+        empty = (torch.zeros(0, dtype=torch.long), torch.zeros(0),
+                 torch.zeros((0, H, W), dtype=torch.bool, device=dev) if on_device else torch.zeros((H, W, 0), dtype=torch.bool))
         if cand.numel() == 0:
-            return [empty] * B
+            return [empty + (None,)] * B if on_device else [empty] * B
         # per-class NMS of every frame in one pass (refine_detections_graph): suppression only inside (frame, class) groups
         grp = frame[cand] * self.num_classes + cls_id[cand]
         kept = _nms_batched(refined[cand][None], score[cand][None], DETECTION_NMS_THRESHOLD, len(cand), groups=grp[None])[0]
@@ -629,6 +634,13 @@ class MaskRCNN(nn.Module):
                               roi_frame=frame, cls_prob=cls_prob, box_delta=box_delta, refined=refined, sel=sel_all, ok=ok, det_boxes=det_boxes_all,
                               det_cls=det_cls, det_score=det_score, det_frame=det_frame, mask28=m, px=px, resized=val, window=window,
                               feats=feats, geometry=(H, W, scale, top, left, nh, nw))
+        if on_device:                # the planes stay put: slices of one (K_total, H, W) tensor, which goes along with where the slice starts
+            det_cls, det_score, counts = det_cls.cpu(), det_score.cpu(), torch.bincount(det_frame, minlength=B).cpu().tolist()
+            out, at = [], 0
+            for n in counts:
+                out.append((det_cls[at:at + n], det_score[at:at + n], masks[at:at + n], (masks, at)))
+                at += n
+            return out
         if dev.type == 'cuda':                                              # one transfer for the whole batch, through pinned memory
             host = torch.empty(masks.shape, dtype=torch.bool, pin_memory=True)
             host.copy_(masks, non_blocking=True)
@@ -818,6 +830,24 @@ class MaskRCNNSegmenter:
         the current group's box steps (MaskRCNN.detect_batches)."""
         for out in self.net.detect_batches(self._upload(g) for g in groups):
             yield self._results(out)
+
+    def batch_device(self, frames) -> list:
+        """`batch` with the masks left on the GPU: per frame {'class_ids', 'scores'} as host arrays and 'masks_device', a
+        (K, H, W) bool tensor on the network's device — for Predictor(device_targets=True), which builds the targets there."""
+        return self._results_device(self.net.detect_batch(self._upload(frames), on_device=True))
+
+    @staticmethod
+    def _results_device(out):
+        """'masks_stacked': (the planes of all frames of the pass as one (K_total, H, W) tensor, this frame's first plane in it) or
+        None — so that a caller who wants them together need not copy them together."""
+        return [{'class_ids': cls.numpy(), 'scores': score.numpy(), 'masks_device': masks, 'masks_stacked': stacked}
+                for cls, score, masks, stacked in out]
+
+    def batches_device(self, groups):
+        """`batch_device` of every group of frames of an iterable, in order (a generator), the next group's trunk overlapping
+        the current group's box steps as in `batches`."""
+        for out in self.net.detect_batches((self._upload(g) for g in groups), on_device=True):
+            yield self._results_device(out)
 
     def _upload(self, frames):
         return [torch.from_numpy(np.ascontiguousarray(f[..., ::-1])).to(self.device) for f in frames]

@@ -148,7 +148,8 @@ class Predictor:
                  segmenter: Optional[Callable] = None,
                  lookup_divisions=None,
                  lookup_table_budget: int = 32 << 30,
-                 reference_table_aliasing: bool = False):
+                 reference_table_aliasing: bool = False,
+                 device_targets: bool = False):
         """Reference parameters as in predict.py:38-70.  Extra keyword-only arguments:
 
         device            HIP device ordinal of the engine context
@@ -164,7 +165,12 @@ class Predictor:
                           (until the camera pose changes: _loadLookup reloads the table).  Default False: every frame starts
                           from the grid itself, frames are independent — which is what sharding over GPUs needs.  With True,
                           use ONE Predictor and feed it the frames in the reference's order.
+        device_targets    run_many on the segmentation path with a segmenter that offers `batch_device(frames)` (MaskRCNNSegmenter:
+                          the instance masks stay on the GPU): the targets are built there as well (rope_stage_targets_segmented)
+                          instead of on the host from a copy of the masks.  Same planes, bit for bit, hence the same angles.
+                          Without such a segmenter, and in run() / prepare(), the flag changes nothing.
         """
+        self.device_targets = bool(device_targets)
         self.ds_factor, self.preview = ds_factor, preview
         if preview:                       # headless: frames go to .viz.frame and, with save_to, an uncompressed AVI
             from .viz import ProjectionViz
@@ -467,6 +473,121 @@ class Predictor:
         self.trace = self.traces[-1]
         return angles
 
+    @staticmethod
+    def _groups(n: int, camera_poses, batch: int) -> list:
+        """[lo, hi) runs of consecutive frames with the same camera pose, at most `batch` of them each."""
+        groups, lo = [], 0
+        while lo < n:
+            hi = lo + 1
+            while hi < n and hi - lo < batch and (camera_poses is None or np.array_equal(camera_poses[hi], camera_poses[lo])):
+                hi += 1
+            groups.append((lo, hi))
+            lo = hi
+        return groups
+
+    SEG_BATCH = 8      # device_targets: frames per pass of the segmenter (batch_device) and per rope_stage_targets_segmented call
+
+    @staticmethod
+    def _stacked(results):
+        """The (K_i, H, W) mask tensors of a sub-batch's frames as one (sum K_i, H, W) tensor: the segmenter's own, when it says
+        that the frames' planes lie in one in frame order ('masks_stacked', MaskRCNNSegmenter.batch_device), a copy otherwise;
+        None when no frame has an instance."""
+        import torch
+        where = [r.get('masks_stacked') for r in results]
+        if all(w is not None and w[0] is where[0][0] for w in where):
+            at = where[0][1]
+            for r, w in zip(results, where):
+                if w[1] != at:
+                    break
+                at += r['masks_device'].shape[0]
+            else:
+                return where[0][0][where[0][1]:at] if at > where[0][1] else None
+        planes = [r['masks_device'] for r in results if r['masks_device'].shape[0]]
+        return torch.cat(planes).contiguous() if planes else None
+
+    def _device_targets_apply(self, target_depths) -> bool:
+        """device_targets is on, the segmenter leaves its masks on the GPU, and the frames are what that path takes."""
+        if not self.device_targets or self.synthetic or self.seg is None or not hasattr(self.seg, 'batch_device'):
+            return False
+        f = int(self.ds_factor)
+        if f < 1 or (f > 1 and f % 2):
+            return False
+        H, W = self.intrinsics.height, self.intrinsics.width
+        d0 = np.asarray(target_depths[0])
+        return d0.dtype in (np.float32, np.float64) and \
+            all(np.asarray(d).dtype == d0.dtype and np.asarray(d).shape == (H * f, W * f) for d in target_depths)
+
+    def _run_many_device(self, target_colors, target_depths, camera_poses, batch: int) -> np.ndarray:
+        """_run_many_batched with the targets built on the GPU.  Worker threads down-sample a group's colour and depth on the host
+        (the reduced depth is what travels, in page-locked memory); the staging thread runs the segmenter over the group in
+        sub-batches of SEG_BATCH frames, in order, and hands each sub-batch's masks — still on the device — with its depth planes
+        to rope_stage_targets_segmented, which fills the sub-batch's slots of the engine's second set of planes on the same
+        stream; all of it while the group before is on the GPU."""
+        import torch
+        from concurrent.futures import ThreadPoolExecutor
+        from ..engine import pinned_empty
+        from ..utils import cpu_budget
+        n = len(target_colors)
+        out = np.zeros((n, 6))
+        groups = self._groups(n, camera_poses, batch)
+        self._setStages()
+        want_ts = self._has_tsweep()
+        H, W, f = self.intrinsics.height, self.intrinsics.width, int(self.ds_factor)
+        dtype = np.asarray(target_depths[0]).dtype
+        device = torch.device('cuda', self.engine.device)
+        link_of_class = [self.link_names.index(c) if c in self.link_names else -1 for c in self.classes]
+        cap = min(batch, n)
+        depth_sets = [pinned_empty((cap, H, W), dtype) for _ in range(min(2, len(groups)))]   # two, taken in turn
+
+        def shrink(depths, colors, j0, j1, lo_):
+            for j in range(j0, j1):
+                colors[j] = self._downsample(target_colors[lo_ + j], f)
+                depths[j] = self._downsample(np.asarray(target_depths[lo_ + j]), f)
+
+        workers = max(1, min(self.PREPARE_WORKERS, cpu_budget() - 1))
+        with ThreadPoolExecutor(max_workers=workers) as pool, ThreadPoolExecutor(max_workers=1) as stager:
+            def submit(k):
+                lo_, hi_ = groups[k]
+                b = hi_ - lo_
+                depths, colors = depth_sets[k & 1][:b], [None] * b
+                step = max(1, -(-b // (4 * workers)))
+                return depths, colors, [pool.submit(shrink, depths, colors, j0, min(j0 + step, b), lo_) for j0 in range(0, b, step)]
+
+            def stage(filled):
+                depths, colors, jobs = filled
+                for j in jobs:
+                    j.result()
+                b = len(colors)
+                subs = [(j0, min(j0 + self.SEG_BATCH, b)) for j0 in range(0, b, self.SEG_BATCH)]
+                with torch.cuda.device(device):
+                    # a segmenter that can work ahead (batches_device: the next sub-batch's trunk beside this one's box steps) does
+                    several = getattr(self.seg, 'batches_device', None) or (lambda gs: (self.seg.batch_device(g) for g in gs))
+                    for (j0, j1), results in zip(subs, several(colors[j0:j1] for j0, j1 in subs)):
+                        first, link_of = [0], []
+                        for r in results:
+                            link_of += [link_of_class[c] for c in r['class_ids']]
+                            first.append(len(link_of))
+                        masks_t = self._stacked(results)
+                        depth_t = torch.from_numpy(depths[j0:j1]).to(device, non_blocking=True)
+                        self.engine.stage_targets_segmented(depth_t, masks_t, first, link_of, LOOKUP_NUM_RENDERED, b, j0, want_ts)
+
+            filled = {0: submit(0)}
+            staging = stager.submit(stage, filled[0])
+            if len(groups) > 1:
+                filled[1] = submit(1)
+            for k, (lo, hi) in enumerate(groups):
+                staging.result()
+                self.engine.commit_targets()            # waits for the staging kernels: group k resident, its host depth planes free again
+                del filled[k]
+                if k + 2 < len(groups):
+                    filled[k + 2] = submit(k + 2)
+                if camera_poses is not None and np.any(np.asarray(camera_poses[lo]) != self.camera_pose):
+                    self.changeCameraPose(camera_poses[lo])     # before the staging thread touches the context again
+                if k + 1 < len(groups):
+                    staging = stager.submit(stage, filled[k + 1])
+                out[lo:hi] = self._run_resident(hi - lo)
+        return out
+
     def _run_many_batched(self, target_colors, target_depths, camera_poses, batch: int) -> np.ndarray:
         """run_many in groups of up to `batch` consecutive frames under one camera pose.  Worker threads prepare a group's frames
         straight into the slots of its stacked planes (host work only: down-sampling, masks, packing — the library's one-pass form
@@ -474,15 +595,11 @@ class Predictor:
         while the group before it is on the GPU."""
         from concurrent.futures import ThreadPoolExecutor
         from ..utils import cpu_budget
+        if self._device_targets_apply(target_depths):
+            return self._run_many_device(target_colors, target_depths, camera_poses, batch)
         n = len(target_colors)
         out = np.zeros((n, 6))
-        groups, lo = [], 0
-        while lo < n:                                   # consecutive frames with the same camera pose, at most `batch` of them
-            hi = lo + 1
-            while hi < n and hi - lo < batch and (camera_poses is None or np.array_equal(camera_poses[hi], camera_poses[lo])):
-                hi += 1
-            groups.append((lo, hi))
-            lo = hi
+        groups = self._groups(n, camera_poses, batch)
         self._setStages()
         want_ts = self._has_tsweep()
         H, W = self.intrinsics.height, self.intrinsics.width
