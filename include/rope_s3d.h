@@ -203,6 +203,12 @@ int rope_render(rope_ctx *ctx, const double *q, int n_render, float *depth, uint
 int rope_render_batch(rope_ctx *ctx, const double *q, const double *PV, int N, int n_render, const int32_t *crop,
                       float *depth, uint8_t *ids);
 
+/* rope_render_batch for the whole frame with the N planes written to the CALLER's device memory (float32 depth, uint8 ids; one of
+ * them may be NULL) instead of host memory: a synthetic run's frames stay on the GPU.  Chunks, limits and the effect on the
+ * per-candidate buffers as rope_render_batch; only the destination of the copy-out differs.  The planes are complete when the call
+ * returns. */
+int rope_render_batch_device(rope_ctx *ctx, const double *q, const double *PV, int N, int n_render, float *depth_dev, uint8_t *ids_dev);
+
 /* N poses to per-pixel label bit planes.  Replaces, per frame of AutomaticAnnotator.run, Renderer.render + Annotator._mask_color
  * for every label (annotation.py:117-127,163-176): bit b of masks[p][y][x] is set when any pixel of label b lies within the
  * pad x pad window anchored at (pad/2, pad/2) around (x, y), which is cv2.dilate(mask_b, ones((pad, pad))).
@@ -362,6 +368,36 @@ int rope_commit_targets(rope_ctx *ctx);
 int rope_stage_targets_segmented(rope_ctx *ctx, int n_total, int slot0, int n_frames, const void *depth_dev, int depth_kind,
                                  const uint8_t *masks_dev, const int32_t *inst_first, const int32_t *link_of, int n_lookup_links,
                                  int want_tsweep, void *stream);
+
+/* The staged set filled on the device from full-size RENDERS that are there already (rope_render_batch_device): per frame what
+ * rope_prepare_synthetic writes for the colour plane blue_of_id[ids] and float32 depth (kind 1) — the four-tap down-sampling by f
+ * (OpenCV's fixed-point rounding for the colour, float32 for the depth; f = 1 passes through), the masks blue == link_blue[l], the
+ * lookup depth over the first n_lookup_links links, the packing, the flags and, when asked, the TensorSweep plane.
+ *   depth_dev, ids_dev   n_frames planes H0 x W0, float32 metres and uint8 link ids, DEVICE
+ *   f                    1 or even; H0 / f x W0 / f must be the image size of rope_set_camera, else ROPE_E_ARG
+ *   blue_of_id           256 bytes: channel 0 of the colour an id is drawn in (Renderer's table; 255 = background), HOST
+ *   link_blue            n_links (<= 6) channel-0 values, as rope_prepare_synthetic takes them, HOST
+ * Slots (n_total, slot0, n_frames), completion, rope_commit_targets, threading and refusals are those of
+ * rope_stage_targets_segmented; the two calls fill the same staged set. */
+int rope_stage_targets_synthetic(rope_ctx *ctx, int n_total, int slot0, int n_frames, const float *depth_dev, const uint8_t *ids_dev,
+                                 int H0, int W0, int f, const uint8_t *blue_of_id, const int32_t *link_blue, int n_links,
+                                 int n_lookup_links, int want_tsweep, void *stream);
+
+/* Depth holes of synthetic frames (NoiseMaker.holes, noise.py:12-24) on the device, by an integer contract.
+ * The reference thresholds eight Gaussian fields per frame, dilates them by 3, 6, .. and closes their union with a 20 x 20 box;
+ * of each field only one bit per pixel matters, and that bit is drawn directly: the same distribution, another stream (the
+ * reference's is unseeded).
+ * rope_hole_thresholds: host only.  Dilation j has size d = 3 (j + 1) < max_size; its bit is set with probability
+ *   p = erfc((1 - thresh_factor / d) / (sigma sqrt 2)), and T_out[j] = floor(p 2^32) (0xFFFFFFFF when p reaches 1).  *n gets the
+ *   number of dilations (at most 10, d at most 32); T_out may be NULL.
+ * rope_depth_holes: in place on N float32 planes H x W in DEVICE memory, on `stream`; needs no context, runs on the current device.
+ *   Seed bit of pixel i = y W + x of plane m for dilation j: word (j & 3) of Philox4x32-10 with key (seed low 32, seed high 32)
+ *   and counter (i, frame0 + m, j >> 2, 0), compared as word < T[j].  hole = close_connection(OR_j dilate_d[j](seed_j)) with
+ *   cv2's box windows (anchor k / 2, borders ignored); depth becomes 0 where hole is set.  T, d: n_d values each, HOST;
+ *   d[j] and connection 1 .. 32. */
+int rope_hole_thresholds(double sigma, double thresh_factor, int max_size, uint32_t *T_out, int *n);
+int rope_depth_holes(float *depth_dev, int N, int H, int W, uint32_t frame0, uint64_t seed, const uint32_t *T, const int32_t *d, int n_d,
+                     int connection, void *stream);
 
 /* The resident set of targets (rope_set_targets / rope_commit_targets) back to the host, for tests: n_frames planes each and
  * n_frames x 8 flag bytes; any pointer may be NULL. */

@@ -1431,27 +1431,28 @@ static int copy_d2h_out(rope_ctx *c, void *dst, const void *src, size_t bytes)
 // device bytes of output planes one chunk of rope_render_batch may hold
 static constexpr size_t RENDER_BATCH_BUDGET = (size_t)256 << 20;
 
-extern "C" int rope_render_batch(rope_ctx *c, const double *q, const double *PV, int N, int n_render, const int32_t *crop,
-                                 float *depth, uint8_t *ids)
+// rope_render_batch and rope_render_batch_device: `to_device` says where depth and ids point, and so how a chunk's planes leave
+static int render_batch(rope_ctx *c, const double *q, const double *PV, int N, int n_render, const int32_t *crop, float *depth, uint8_t *ids,
+                        bool to_device)
 {
-    if (!c) return ROPE_E_ARG;
-    if (!q) ARG_FAIL(c, "rope_render_batch: null joint vectors");
-    if (N < 1) ARG_FAIL(c, "rope_render_batch: need N >= 1");
-    if (!depth && !ids) ARG_FAIL(c, "rope_render_batch: no output (depth and ids both null)");
-    if (!c->have_robot || !c->have_camera) ARG_FAIL(c, "rope_render_batch: robot and camera must be set first");
-    if (n_render < 1 || n_render > c->n_links) ARG_FAIL(c, "rope_render_batch: n_render out of range");
+#define RB_FAIL(msg) ARG_FAIL(c, to_device ? "rope_render_batch_device: " msg : "rope_render_batch: " msg)      // the entry the caller used
+    if (!q) RB_FAIL("null joint vectors");
+    if (N < 1) RB_FAIL("need N >= 1");
+    if (!depth && !ids) RB_FAIL("no output (depth and ids both null)");
+    if (!c->have_robot || !c->have_camera) RB_FAIL("robot and camera must be set first");
+    if (n_render < 1 || n_render > c->n_links) RB_FAIL("n_render out of range");
     FrameParams fp = c->fp;
     if (crop) {
         if (crop[0] < 0 || crop[1] >= fp.H || crop[0] > crop[1] || crop[2] < 0 || crop[3] >= fp.W || crop[2] > crop[3])
-            ARG_FAIL(c, "rope_render_batch: crop outside the image");
+            RB_FAIL("crop outside the image");
         fp.r0 = crop[0]; fp.r1 = crop[1]; fp.c0 = crop[2]; fp.c1 = crop[3];
     }
     for (size_t i = 0; i < 6 * (size_t)N; i++)
-        if (!std::isfinite(q[i]) || std::fabs(q[i]) > 1.0e4) ARG_FAIL(c, "rope_render_batch: joint angle not finite or |q| > 1e4 rad");
+        if (!std::isfinite(q[i]) || std::fabs(q[i]) > 1.0e4) RB_FAIL("joint angle not finite or |q| > 1e4 rad");
     bool clip = use_clip(c);
     if (PV) {
         for (size_t i = 0; i < 16 * (size_t)N; i++)
-            if (!std::isfinite(PV[i])) ARG_FAIL(c, "rope_render_batch: non-finite view matrix");
+            if (!std::isfinite(PV[i])) RB_FAIL("non-finite view matrix");
         clip = c->strategy & STRATEGY_CLIP_KERNELS;                // the call's cameras decide, not the context's
         for (int i = 0; i < N && !clip; i++) clip = near_plane_in_reach(c, PV + 16 * (size_t)i);
     }
@@ -1511,12 +1512,33 @@ extern "C" int rope_render_batch(rope_ctx *c, const double *q, const double *PV,
         a.depth_out = depth ? c->d_rdepth : nullptr;
         a.ids_out = ids ? c->d_rids : nullptr;
         HIP_TRY(c, launch_raster(MODE_DUMP, ROPE_LOSS_DEPTH, n, c->stream, fp, c->rp, a, clip));
+        if (to_device) {                                      // in stream order: the next chunk's clearing comes after these copies
+            if (depth) HIP_TRY(c, hipMemcpyAsync(depth + (size_t)lo * px, c->d_rdepth, (size_t)n * px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            if (ids) HIP_TRY(c, hipMemcpyAsync(ids + (size_t)lo * px, c->d_rids, (size_t)n * px, hipMemcpyDeviceToDevice, c->stream));
+            continue;
+        }
         if (depth) { rc = copy_d2h_out(c, depth + (size_t)lo * px, c->d_rdepth, (size_t)n * px * sizeof(float)); if (rc) return rc; }
         if (ids) { rc = copy_d2h_out(c, ids + (size_t)lo * px, c->d_rids, (size_t)n * px); if (rc) return rc; }
     }
+    if (to_device) HIP_TRY(c, hipStreamSynchronize(c->stream));      // the planes are the caller's, on any stream, when the call returns
     c->C = 0;
     c->last_n_render = n_render;
     return ROPE_OK;
+}
+#undef RB_FAIL
+
+extern "C" int rope_render_batch(rope_ctx *c, const double *q, const double *PV, int N, int n_render, const int32_t *crop,
+                                 float *depth, uint8_t *ids)
+{
+    if (!c) return ROPE_E_ARG;
+    return render_batch(c, q, PV, N, n_render, crop, depth, ids, false);
+}
+
+// The whole frame of N poses into the CALLER's device memory: rope_render_batch with another destination for the copy-out
+extern "C" int rope_render_batch_device(rope_ctx *c, const double *q, const double *PV, int N, int n_render, float *depth_dev, uint8_t *ids_dev)
+{
+    if (!c) return ROPE_E_ARG;
+    return render_batch(c, q, PV, N, n_render, nullptr, depth_dev, ids_dev, true);
 }
 
 // rope_render_batch's chunks, each drawn into id planes only and then turned into label planes on the device (rope_masks.hip):
@@ -1984,6 +2006,62 @@ extern "C" int rope_stage_targets(rope_ctx *c, int n_frames, const uint64_t *tq,
     return ROPE_OK;
 }
 
+// What a call that fills slots of the staged set ON THE DEVICE starts with, its arguments checked: a call with slot0 > 0 must go on
+// with the set as it was started; the staged planes are written from here on, so a complete staging is withdrawn; slot0 == 0 sizes
+// a new set of n_total frames.  `who` names the caller in the messages.
+static int stage_slots_begin(rope_ctx *c, const char *who, int n_total, int slot0, bool ts)
+{
+    auto fail = [&](int code, const char *msg) { c->stage_err = std::string(who) + msg; return code; };
+    const int W = c->fp.W, H = c->fp.H;
+    if (slot0 > 0 && (c->seg_n_total != n_total || c->seg_ts != ts || c->staged_W != W || c->staged_H != H))
+        return fail(ROPE_E_ARG, ": n_total, want_tsweep or the image size changed in mid-set (slot0 == 0 starts a set)");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(ROPE_E_HIP, ": hipSetDevice failed");
+    c->staged_n = 0;                              // the staged planes are written from here on: complete again when every slot is filled
+    if (slot0 != 0) return ROPE_OK;
+    c->seg_n_total = 0;                           // a new set: sized here, once
+    if (c->copy_stream && hipStreamSynchronize(c->copy_stream) != hipSuccess) return fail(ROPE_E_HIP, ": the upload stream failed");
+    if (drain_stage_events(c)) return fail(ROPE_E_HIP, ": a staging kernel failed");   // of a set left unfinished
+    const size_t n = (size_t)W * H * (size_t)n_total;
+    bool ok = true;
+    auto grow = [&](auto **p, size_t &cap, size_t want) {
+        if (want <= cap) return;
+        cap = 0;
+        if (realloc_dev(p, want) != hipSuccess) { ok = false; return; }
+        cap = want;
+    };
+    grow(&c->s_ftq, c->s_frames_cap, n);
+    grow(&c->s_ft32, c->s_t32_cap, n);
+    if (ts) grow(&c->s_fts32, c->s_fts_cap, n);
+    if (n_total > c->s_fflags_cap) {
+        c->s_fflags_cap = 0;
+        if (realloc_dev(&c->s_fflags, (size_t)n_total) == hipSuccess) c->s_fflags_cap = n_total; else ok = false;
+    }
+    if (n_total > c->s_counts_cap) {
+        c->s_counts_cap = 0;
+        if (realloc_dev(&c->s_counts, (size_t)n_total * 2 * ROPE_MAX_LINKS) == hipSuccess) c->s_counts_cap = n_total; else ok = false;
+    }
+    if (!ok) { (void)hipGetLastError(); return fail(ROPE_E_NOMEM, ": out of device memory"); }
+    c->meta_used = 0;
+    c->seg_filled.assign((size_t)n_total, 0);
+    c->seg_n_filled = 0;
+    c->seg_ts = ts;
+    c->staged_W = W; c->staged_H = H;
+    c->seg_n_total = n_total;
+    return ROPE_OK;
+}
+
+// ... and ends with, its kernels enqueued: the slots are marked, and the set is complete once every one of them has been filled
+static void stage_slots_filled(rope_ctx *c, int n_total, int slot0, int n_frames, bool ts)
+{
+    for (int i = slot0; i < slot0 + n_frames; i++)
+        if (!c->seg_filled[i]) { c->seg_filled[i] = 1; c->seg_n_filled++; }
+    if (c->seg_n_filled == n_total) {
+        c->staged_t32 = true;
+        c->staged_ts = ts;
+        c->staged_n = n_total;
+    }
+}
+
 // The staged set filled on the DEVICE, slots slot0 .. slot0 + n_frames - 1 of n_total: the segmentation path's targets from instance
 // masks that are in HBM already (rope_targets.hip: what rope_prepare_segmented computes per frame at f == 1).  The kernels go onto
 // `stream`, the caller's, behind the work that produced the masks; the call does not wait for them — rope_commit_targets does.
@@ -2008,44 +2086,10 @@ extern "C" int rope_stage_targets_segmented(rope_ctx *c, int n_total, int slot0,
     if (K > 0 && (!masks_dev || !link_of)) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: instances without masks_dev / link_of");
     for (int k = 0; k < K; k++)
         if (link_of[k] < -1 || link_of[k] >= c->n_links) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: link_of outside -1 .. n_links - 1");
-    const int W = c->fp.W, H = c->fp.H;
     const bool ts = want_tsweep != 0;
-    if (slot0 > 0 && (c->seg_n_total != n_total || c->seg_ts != ts || c->staged_W != W || c->staged_H != H))
-        return fail(ROPE_E_ARG, "rope_stage_targets_segmented: n_total, want_tsweep or the image size changed in mid-set (slot0 == 0 starts a set)");
-    if (hipSetDevice(c->device) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: hipSetDevice failed");
-    c->staged_n = 0;                              // the staged planes are written from here on: complete again when every slot is filled
+    if (int rc = stage_slots_begin(c, "rope_stage_targets_segmented", n_total, slot0, ts)) return rc;
+    const int W = c->fp.W, H = c->fp.H;
     const size_t plane = (size_t)W * H;
-    if (slot0 == 0) {                             // a new set: sized here, once
-        c->seg_n_total = 0;
-        if (c->copy_stream && hipStreamSynchronize(c->copy_stream) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: the upload stream failed");
-        if (drain_stage_events(c)) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: a staging kernel failed");   // of a set left unfinished
-        const size_t n = plane * (size_t)n_total;
-        bool ok = true;
-        auto grow = [&](auto **p, size_t &cap, size_t want) {
-            if (want <= cap) return;
-            cap = 0;
-            if (realloc_dev(p, want) != hipSuccess) { ok = false; return; }
-            cap = want;
-        };
-        grow(&c->s_ftq, c->s_frames_cap, n);
-        grow(&c->s_ft32, c->s_t32_cap, n);
-        if (ts) grow(&c->s_fts32, c->s_fts_cap, n);
-        if (n_total > c->s_fflags_cap) {
-            c->s_fflags_cap = 0;
-            if (realloc_dev(&c->s_fflags, (size_t)n_total) == hipSuccess) c->s_fflags_cap = n_total; else ok = false;
-        }
-        if (n_total > c->s_counts_cap) {
-            c->s_counts_cap = 0;
-            if (realloc_dev(&c->s_counts, (size_t)n_total * 2 * ROPE_MAX_LINKS) == hipSuccess) c->s_counts_cap = n_total; else ok = false;
-        }
-        if (!ok) { (void)hipGetLastError(); return fail(ROPE_E_NOMEM, "rope_stage_targets_segmented: out of device memory"); }
-        c->meta_used = 0;
-        c->seg_filled.assign((size_t)n_total, 0);
-        c->seg_n_filled = 0;
-        c->seg_ts = ts;
-        c->staged_W = W; c->staged_H = H;
-        c->seg_n_total = n_total;
-    }
     // this call's tables, appended: plane offsets | links present per frame | code per plane
     const size_t need = 2 * (size_t)n_frames + 1 + (size_t)K;
     if (c->meta_used + need > c->meta_cap) {      // the kernels in flight read the old block: wait for them, then start a larger one
@@ -2084,12 +2128,79 @@ extern "C" int rope_stage_targets_segmented(rope_ctx *c, int n_total, int slot0,
         (void)hipGetLastError();
         return fail(ROPE_E_HIP, "rope_stage_targets_segmented: the launch failed");
     }
-    for (int i = slot0; i < slot0 + n_frames; i++)
-        if (!c->seg_filled[i]) { c->seg_filled[i] = 1; c->seg_n_filled++; }
-    if (c->seg_n_filled == n_total) {
-        c->staged_t32 = true;
-        c->staged_ts = ts;
-        c->staged_n = n_total;
+    stage_slots_filled(c, n_total, slot0, n_frames, ts);
+    return ROPE_OK;
+}
+
+// The same slots filled from full-size renders that are in HBM already (rope_synth.hip: what rope_prepare_synthetic computes per
+// frame for the colour plane blue_of_id[ids] and float32 depth, the down-sampling included).  Slots, completion, commit, threading
+// and refusals are those of rope_stage_targets_segmented.
+extern "C" int rope_stage_targets_synthetic(rope_ctx *c, int n_total, int slot0, int n_frames, const float *depth_dev, const uint8_t *ids_dev,
+                                            int H0, int W0, int f, const uint8_t *blue_of_id, const int32_t *link_blue, int n_links,
+                                            int n_lookup_links, int want_tsweep, void *stream)
+{
+    if (!c) return ROPE_E_ARG;
+    auto fail = [&](int code, const char *msg) { c->stage_err = msg; return code; };
+    c->stage_err.clear();
+    // the arguments first: a refused call changes nothing, neither a staging that waits for its commit nor a set half filled
+    if (!c->have_camera || !c->have_robot) return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: robot and camera must be set first");
+    if (n_total < 1 || n_total > 65535 || n_frames < 1 || slot0 < 0 || slot0 > n_total || n_frames > n_total - slot0)
+        return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: need 1 <= n_total <= 65535 and slots slot0 .. slot0 + n_frames - 1 inside it");
+    if (!depth_dev || !ids_dev || !blue_of_id || !link_blue) return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: depth_dev, ids_dev, blue_of_id and link_blue are required");
+    if (n_links < 1 || n_links > ROPE_MAX_LINKS || n_lookup_links < 0 || n_lookup_links > n_links)
+        return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: need 1 <= n_links <= 6 and n_lookup_links inside 0 .. n_links");
+    if (H0 < 1 || W0 < 1 || f < 1 || (f > 1 && (f & 1)) || H0 % f || W0 % f || H0 / f != c->fp.H || W0 / f != c->fp.W)
+        return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: f is 1 or even, and H0 / f x W0 / f must be the image size of rope_set_camera");
+    const bool ts = want_tsweep != 0;
+    if (int rc = stage_slots_begin(c, "rope_stage_targets_synthetic", n_total, slot0, ts)) return rc;
+    const size_t plane = (size_t)c->fp.W * c->fp.H, o = plane * (size_t)slot0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipEvent_t done = nullptr;
+    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets_synthetic: no event");
+    c->stage_events.push_back(done);              // recorded or not, the next wait gets rid of it
+    if (launch_synthetic_targets(st, H0, W0, f, n_frames, depth_dev, ids_dev, blue_of_id, link_blue, n_links, n_lookup_links, c->s_ftq + o,
+                                 c->s_ft32 + o, ts ? c->s_fts32 + o : nullptr, c->s_counts + (size_t)slot0 * 2 * ROPE_MAX_LINKS,
+                                 c->s_fflags + slot0) != hipSuccess ||
+        hipEventRecord(done, st) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ROPE_E_HIP, "rope_stage_targets_synthetic: the launch failed");
+    }
+    stage_slots_filled(c, n_total, slot0, n_frames, ts);
+    return ROPE_OK;
+}
+
+// Host only: the thresholds of the depth holes' seed bits.  Dilation j has size d = 3 (j + 1) < max_size (np.arange(3, max_size, 3),
+// noise.py:16); a pixel is a seed of it when |N(0, std)| >= 1 - thresh_factor / d, with probability p = erfc(thresh / (std sqrt 2));
+// T = floor(p 2^32), the whole range when p reaches 1.  Every step one IEEE double operation, erfc and sqrt from libm.
+extern "C" int rope_hole_thresholds(double sigma, double thresh_factor, int max_size, uint32_t *T_out, int *n_out)
+{
+    if (!n_out || !(sigma > 0.0) || !std::isfinite(sigma) || !std::isfinite(thresh_factor)) return ROPE_E_ARG;
+    const int n = max_size > 3 ? (max_size - 1) / 3 : 0;
+    if (n > ROPE_HOLE_MAX_DILATIONS || 3 * n > ROPE_HOLE_MAX_WINDOW) return ROPE_E_ARG;
+    *n_out = n;
+    if (!T_out) return ROPE_OK;
+    for (int j = 0; j < n; j++) {
+        const double d = 3.0 * (j + 1);
+        const double thresh = 1.0 - thresh_factor / d;
+        const double p = std::erfc(thresh / (sigma * std::sqrt(2.0)));
+        const double t = std::floor(p * 4294967296.0);
+        T_out[j] = t >= 4294967295.0 ? 0xFFFFFFFFu : (t > 0.0 ? (uint32_t)t : 0u);
+    }
+    return ROPE_OK;
+}
+
+// Depth holes in place on N float32 planes that are in HBM (rope_synth.hip), on the caller's stream; no context, the current device.
+extern "C" int rope_depth_holes(float *depth_dev, int N, int H, int W, uint32_t frame0, uint64_t seed, const uint32_t *T, const int32_t *d,
+                                int n_d, int connection, void *stream)
+{
+    if (!depth_dev || N < 1 || N > 65535 || H < 1 || W < 1 || n_d < 0 || n_d > ROPE_HOLE_MAX_DILATIONS || (n_d > 0 && (!T || !d)) ||
+        connection < 1 || connection > ROPE_HOLE_MAX_WINDOW || (uint64_t)H * (uint64_t)W > 0xFFFFFFFFull || (H + 63) / 64 > 65535)
+        return ROPE_E_ARG;
+    for (int j = 0; j < n_d; j++)
+        if (d[j] < 1 || d[j] > ROPE_HOLE_MAX_WINDOW) return ROPE_E_ARG;
+    if (launch_depth_holes(static_cast<hipStream_t>(stream), depth_dev, N, H, W, frame0, seed, T, d, n_d, connection) != hipSuccess) {
+        (void)hipGetLastError();
+        return ROPE_E_HIP;
     }
     return ROPE_OK;
 }

@@ -231,4 +231,18 @@ hipError_t launch_segmented_targets(hipStream_t st, int H, int W, int n_frames, 
                                     const int32_t *meta, int n_links, uint64_t *tq, float *t32, float *ts, unsigned long long *counts,
                                     LinkFlags *flags);
 
+// rope_synth.hip: the synthetic path kept on the device.
+// launch_depth_holes: the holes of NoiseMaker.holes by the integer contract of DESIGN.md §3a, in place on N float32 planes H x W.
+// T, d: n_d thresholds and dilation sizes (host); the bits of plane i are those of frame frame0 + i.  One launch, no scratch.
+#define ROPE_HOLE_MAX_WINDOW 32
+#define ROPE_HOLE_MAX_DILATIONS 16
+hipError_t launch_depth_holes(hipStream_t st, float *depth, int N, int H, int W, uint32_t frame0, uint64_t seed, const uint32_t *T,
+                              const int32_t *d, int n_d, int connection);
+// launch_synthetic_targets: what rope_prepare_synthetic computes per frame for the colour plane blue_of_id[ids] and float32 depth,
+// n_frames full-size planes H0 x W0 -> planes H0 / f x W0 / f.  blue_of_id (256 bytes) and link_blue (n_links) are host tables;
+// counts: n_frames x 2 x ROPE_MAX_LINKS words of scratch (n_mask, n_depth per link; cleared here); ts may be null.
+hipError_t launch_synthetic_targets(hipStream_t st, int H0, int W0, int f, int n_frames, const float *depth, const uint8_t *ids,
+                                    const uint8_t *blue_of_id, const int32_t *link_blue, int n_links, int n_lookup_links, uint64_t *tq,
+                                    float *t32, float *ts, unsigned long long *counts, LinkFlags *flags);
+
 }  // namespace rope

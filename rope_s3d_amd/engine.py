@@ -26,7 +26,8 @@ ABI_SYMBOLS = (
     'rope_seg_rpn_targets', 'rope_seg_roi_targets', 'rope_seg_roi_align_float', 'rope_seg_roi_align_backward',
     'rope_set_target_tsweep', 'rope_set_targets', 'rope_stage_targets', 'rope_commit_targets', 'rope_eval_targets', 'rope_lookup_score_targets', 'rope_predict_batch',
     'rope_prepare_synthetic', 'rope_host_alloc', 'rope_host_free', 'rope_build_id', 'rope_camera_matrix', 'rope_lookup_grid', 'rope_crop_divisions',
-    'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets')
+    'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets',
+    'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -146,6 +147,10 @@ def load_library(path: str = None):
     lib.rope_commit_targets.argtypes = [vp]
     lib.rope_stage_targets_segmented.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, vp]
     lib.rope_debug_targets.argtypes = [vp, vp, vp, vp, vp]
+    lib.rope_render_batch_device.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    lib.rope_stage_targets_synthetic.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp]
+    lib.rope_hole_thresholds.argtypes = [dbl, dbl, i32, vp, C.POINTER(i32)]
+    lib.rope_depth_holes.argtypes = [vp, i32, i32, i32, C.c_uint32, C.c_uint64, vp, vp, i32, i32, vp]
     lib.rope_eval_targets.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.rope_lookup_score_targets.argtypes = [vp, vp, vp, vp]
     lib.rope_predict_batch.argtypes = [vp, C.POINTER(PredictArgs), i32, vp, vp, C.POINTER(C.c_int64)]
@@ -274,6 +279,20 @@ def prepare_segmented(depth: np.ndarray, f: int, masks: np.ndarray, link_of, n_l
     rc = load_library().rope_prepare_segmented(C.c_void_p(depth.ctypes.data), kind, depth.strides[0], H0, W0, int(f), _p(m), m.shape[2], _p(lo),
                                                int(n_links), int(n_lookup_links), _p(tq), _p(lookup_f32), _p(tgt_depth), _p(flags))
     return rc == 0
+
+
+def hole_thresholds(std: float = .22, thresh_factor: float = 1, max_size: int = 25):
+    """rope_hole_thresholds (host code, no GPU): the dilation sizes d = np.arange(3, max_size, 3) of NoiseMaker.holes and, per size,
+    T = floor(P(|N(0, std)| >= 1 - thresh_factor / d) * 2^32), the threshold its seed bits are drawn against.
+    -> (d int32 (n,), T uint32 (n,))."""
+    lib = load_library()
+    n = C.c_int(0)
+    if lib.rope_hole_thresholds(float(std), float(thresh_factor), int(max_size), None, C.byref(n)) != 0:
+        raise EngineError(f"rope_hole_thresholds: std {std} must be positive and max_size {max_size} at most 33")
+    T = np.zeros(n.value, np.uint32)
+    if lib.rope_hole_thresholds(float(std), float(thresh_factor), int(max_size), _p(T), C.byref(n)) != 0:
+        raise EngineError("rope_hole_thresholds failed")
+    return np.arange(3, 3 * n.value + 1, 3, dtype=np.int32), T
 
 
 class Engine:
@@ -430,6 +449,58 @@ class Engine:
                                                     C.c_void_p(torch.cuda.current_stream(depth_t.device).cuda_stream))
         if rc:
             raise EngineError(f"rope_stage_targets_segmented failed ({rc})")
+
+    def stage_targets_synthetic(self, depth_t, ids_t, f: int, blue_of_id, link_blue, n_lookup: int, n_total: int, slot0: int = 0,
+                                want_tsweep: bool = False):
+        """rope_stage_targets_synthetic: slots slot0 .. slot0 + B - 1 of a staged set of n_total frames, built on the device from
+        full-size renders that are there already — depth_t (B, H0, W0) float32 and ids_t (B, H0, W0) uint8 torch tensors
+        (render_batch_device), H0 / f x W0 / f this engine's image size — by kernels on torch's current stream: per frame what
+        prepare_synthetic gives for the colour plane blue_of_id[ids].  blue_of_id: 256 channel-0 values, link_blue: one per link.
+        The tensors are kept alive until commit_targets()."""
+        import torch
+        if depth_t.dtype != torch.float32 or ids_t.dtype != torch.uint8 or depth_t.dim() != 3 or depth_t.shape != ids_t.shape \
+                or not depth_t.is_contiguous() or not ids_t.is_contiguous():
+            raise ValueError(f"need contiguous (B, H0, W0) float32 depth and uint8 id planes, got {tuple(depth_t.shape)} {depth_t.dtype} and "
+                             f"{tuple(ids_t.shape)} {ids_t.dtype}")
+        if depth_t.device.type != 'cuda' or depth_t.device.index != self.device or ids_t.device != depth_t.device:
+            raise ValueError(f"the planes must be on cuda:{self.device}, got {depth_t.device} and {ids_t.device}")
+        lut = np.ascontiguousarray(blue_of_id, np.uint8).reshape(-1)
+        lb = np.ascontiguousarray(link_blue, np.int32).reshape(-1)
+        if len(lut) != 256:
+            raise ValueError("blue_of_id holds one channel-0 value per id: 256 bytes")
+        if slot0 == 0 or getattr(self, '_staged', None) is None or not isinstance(self._staged[1], list):
+            self._staged = (int(n_total), [])
+        self._staged[1].append((depth_t, ids_t))
+        rc = self._lib.rope_stage_targets_synthetic(self._ctx, int(n_total), int(slot0), int(depth_t.shape[0]), C.c_void_p(depth_t.data_ptr()),
+                                                    C.c_void_p(ids_t.data_ptr()), int(depth_t.shape[1]), int(depth_t.shape[2]), int(f), _p(lut), _p(lb),
+                                                    len(lb), int(n_lookup), int(bool(want_tsweep)),
+                                                    C.c_void_p(torch.cuda.current_stream(depth_t.device).cuda_stream))
+        if rc:
+            raise EngineError(f"rope_stage_targets_synthetic failed ({rc})")
+
+    def depth_holes(self, depth_t, seed: int, frame0: int = 0, std: float = .22, thresh_factor: float = 1, max_size: int = 25,
+                    connection_factor: int = 20):
+        """rope_depth_holes: NoiseMaker.holes' holes punched into depth_t, (N, H, W) or (H, W) float32 on this engine's device, in
+        place, by a kernel on torch's current stream.  Plane m takes the bits of frame frame0 + m of the 64-bit `seed`: the holes
+        of a frame do not depend on how a run is cut into calls.  The distribution is the reference's, the stream its own
+        (tests/holes_ref.py is the same contract in numpy)."""
+        import torch
+        if depth_t.dtype != torch.float32 or depth_t.dim() not in (2, 3) or not depth_t.is_contiguous():
+            raise ValueError(f"depth planes must be contiguous (N, H, W) float32, got {tuple(depth_t.shape)} {depth_t.dtype}")
+        if depth_t.device.type != 'cuda' or depth_t.device.index != self.device:
+            raise ValueError(f"depth planes must be on cuda:{self.device}, got {depth_t.device}")
+        d, T = hole_thresholds(std, thresh_factor, max_size)
+        H, W = depth_t.shape[-2:]
+        N = depth_t.shape[0] if depth_t.dim() == 3 else 1
+        if N == 0:
+            return depth_t
+        with torch.cuda.device(depth_t.device):
+            rc = self._lib.rope_depth_holes(C.c_void_p(depth_t.data_ptr()), int(N), int(H), int(W), int(frame0) & 0xFFFFFFFF,
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, _p(T), _p(d), len(d), int(connection_factor),
+                                            C.c_void_p(torch.cuda.current_stream(depth_t.device).cuda_stream))
+        if rc:
+            raise EngineError(f"rope_depth_holes failed ({rc}): N <= 65535 planes, dilations and connection_factor at most 32")
+        return depth_t
 
     def debug_targets(self, want_tsweep: bool = False):
         """rope_debug_targets: the resident set back on the host -> (tq (N,H,W) uint64, t32 (N,H,W) float32, tsweep planes or None,
@@ -590,6 +661,28 @@ class Engine:
         if N == 0:
             return d, i
         self._check(self._lib.rope_render_batch(self._ctx, _p(q), _p(PV), N, int(n_render), _p(crop_arr), _p(d), _p(i)), 'rope_render_batch')
+        return d, i
+
+    def render_batch_device(self, q, n_render: int = 6, PV=None):
+        """rope_render_batch_device: render_batch for the whole frame with the planes left on the GPU
+        -> (depth (N, H, W) float32, ids (N, H, W) uint8) torch tensors on this engine's device, complete on return."""
+        import torch
+        q = np.ascontiguousarray(q, np.float64).reshape(-1, 6)
+        N = len(q)
+        if PV is not None:
+            PV = np.ascontiguousarray(PV, np.float64).reshape(-1, 16)
+            if len(PV) != N:
+                raise ValueError(f"render_batch_device: {len(PV)} view matrices for {N} poses")
+        device = torch.device('cuda', self.device)
+        d = torch.empty((N, self.H, self.W), dtype=torch.float32, device=device)
+        i = torch.empty((N, self.H, self.W), dtype=torch.uint8, device=device)
+        if N == 0:
+            return d, i
+        # fresh tensors may be memory that earlier work has not finished with: torch's allocator hands a freed block back to the
+        # stream it was allocated on, in that stream's order, so that stream alone is waited for (the context draws on its own)
+        torch.cuda.current_stream(device).synchronize()
+        self._check(self._lib.rope_render_batch_device(self._ctx, _p(q), _p(PV), N, int(n_render), C.c_void_p(d.data_ptr()),
+                                                       C.c_void_p(i.data_ptr())), 'rope_render_batch_device')
         return d, i
 
     def render_masks(self, q, n_render: int, label_of_link, pad: int, PV=None):

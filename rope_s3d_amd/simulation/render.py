@@ -155,6 +155,18 @@ class Renderer:
         angles = np.asarray(angles, dtype=np.float64).reshape(-1, 6)
         return self.engine.render_batch(angles, self._n_render, self._views(camera_poses, len(angles)), crop)
 
+    def render_ids_batch_device(self, angles):
+        """render_ids_batch under the renderer's own camera with the planes left on the GPU (rope_render_batch_device)
+        -> (depths float32 (N, H, W), link ids uint8 (N, H, W)) as torch tensors on the engine's device."""
+        angles = np.asarray(angles, dtype=np.float64).reshape(-1, 6)
+        return self.engine.render_batch_device(angles, self._n_render)
+
+    @property
+    def blue_of_id(self) -> np.ndarray:
+        """Channel 0 of the colour every link id is drawn in (256 bytes, the background's included): render()'s colour image has
+        blue_of_id[ids] as its first channel."""
+        return np.ascontiguousarray(self._lut[:, 0])
+
     def render_batch(self, angles, camera_poses=None):
         """-> (colours uint8 (N, H, W, 3), depths float32 (N, H, W)): render() for every pose (and camera pose) in one batch."""
         depth, ids = self.render_ids_batch(angles, camera_poses)
