@@ -11,10 +11,13 @@
 #include <string>
 #include <vector>
 
+#include "rope_buffers.h"
 #include "rope_kernels.h"
 
 using namespace rope;
 
+// Every buffer the context owns is a DevBuf / PinnedBuf member (rope_buffers.h): the pointer and its size travel together, and
+// what is not released earlier goes with the context.  Plain pointers below own nothing.
 struct rope_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -23,9 +26,9 @@ struct rope_ctx {
     // robot
     bool have_robot = false;
     RobotParams rp{};
-    uint32_t *d_header = nullptr, *d_tris = nullptr;
-    float *d_verts = nullptr, *d_aabb = nullptr;
-    double *d_joint_fixed = nullptr, *d_joint_axes = nullptr;
+    DevBuf<uint32_t> d_header, d_tris;
+    DevBuf<float> d_verts, d_aabb;
+    DevBuf<double> d_joint_fixed, d_joint_axes;
     int n_links = 0, n_meshlets = 0;
     double reach = 0.0;                     // no point of any link, at any joint angles, is farther than this from the base frame's origin
     double h_PV[16] = {};                   // host copy of the camera matrix (the near-plane test below)
@@ -34,26 +37,25 @@ struct rope_ctx {
     // camera
     bool have_camera = false;
     FrameParams fp{};
-    double *d_PV = nullptr;
+    DevBuf<double> d_PV;
     int n_tiles = 0;
 
     // target
     bool have_target = false;
-    uint64_t *d_tq = nullptr;
-    float *d_t32 = nullptr;
+    DevBuf<uint64_t> d_tq;
+    DevBuf<float> d_t32;
     bool have_t32 = false;
     LinkFlags lf{};
     uint64_t target_version = 0;
     // per loss: empty-tile sums and their frame total, valid for (target_version, crop)
-    uint64_t *d_empty[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t *d_total[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevBuf<uint64_t> d_empty[4], d_total[4];
     uint64_t empty_version[4] = {0, 0, 0, 0};
     int empty_crop[4][4] = {};
 
-    // candidates + results
+    // candidates + results: one group of per-candidate buffers, all sized for `cap` rows by ensure_capacity
     int C = 0, cap = 0;
-    double *d_cand = nullptr, *d_err = nullptr, *d_best_err = nullptr;
-    double *h_stage = nullptr;             // pinned staging: candidates up, errors + best down
+    DevBuf<double> d_cand, d_err, d_best_err;
+    PinnedBuf<double> h_stage;             // pinned staging: candidates up, errors + best down
     // small batches: the finalize kernel writes errors + best straight into mapped pinned host memory (no copy command)
     static constexpr int HOST_ERR_ROWS = 256;
     // lockstep batches (rope_eval_targets): a step's rows — 2 to 26 per frame, hundreds of frames — go up, and their errors come
@@ -61,43 +63,37 @@ struct rope_ctx {
     // commands it would otherwise queue (rows, frame indices, errors: 20-30 us of stream time each between 100 us of kernels)
     // were a fifth of the device's time in a lockstep run
     static constexpr int TARGET_HOST_ROWS = 16384;
-    double *h_err = nullptr, *d_err_host = nullptr;   // host pointer and its device alias
+    PinnedBuf<double> h_err{true};         // mapped: the device writes through dev()
     // small batches: the candidates stay in mapped host memory and the FK kernel reads them from there — no copy command
     // in front of the first launch of a latency-bound chain
-    double *h_cand = nullptr, *d_cand_host = nullptr;
-    const double *cand_dev = nullptr;                  // where the resident candidates are: d_cand or d_cand_host
+    PinnedBuf<double> h_cand{true};
+    const double *cand_dev = nullptr;      // where the resident candidates are: d_cand or h_cand.dev()
     bool err_on_host = false;
     // rope_eval_views / rope_lookup_score reuse C and the per-candidate buffers for rows of their own: after them the
     // resident candidates (and the results of the last eval) are gone until rope_candidates_upload / the next eval
     bool cand_valid = false, results_valid = false;
-    float *d_mvp = nullptr;
-    short4 *d_bounds = nullptr;
-    uint32_t *d_mask_lo = nullptr, *d_mask_hi = nullptr;
+    DevBuf<float> d_mvp;
+    DevBuf<short4> d_bounds;
+    DevBuf<uint32_t> d_mask_lo, d_mask_hi;
     int mask_words = 0;
     // shared upstream layers: candidates with bit-identical (q0, q1) have identical links 0..2
     int n_layers = 0;
-    int32_t *d_layer_of = nullptr, *d_layer_rep = nullptr;
-    uint32_t *d_layers = nullptr;
-    uint64_t *d_layer_sums = nullptr;
-    size_t layers_cap = 0;                 // keys allocated in d_layers
+    DevBuf<int32_t> d_layer_of, d_layer_rep;
+    DevBuf<uint32_t> d_layers;             // keys
+    DevBuf<uint64_t> d_layer_sums;
     // second level of sharing: layers with bit-identical q0 have identical links 0..1 ("parents")
     int n_parents = 0;
-    int32_t *d_parent_of = nullptr, *d_parent_rep = nullptr;   // layer -> parent; parent -> representative candidate
-    uint32_t *d_parents = nullptr;
-    size_t parents_cap = 0;
-    int parent_idx_cap = 0;
-    int layer_rep_cap = 0;
-    uint64_t *d_sums = nullptr;
-    int32_t *d_best_idx = nullptr;
+    DevBuf<int32_t> d_parent_of, d_parent_rep;   // layer -> parent; parent -> representative candidate
+    DevBuf<uint32_t> d_parents;
+    DevBuf<uint64_t> d_sums;
+    DevBuf<int32_t> d_best_idx;
     int last_n_render = 0;
 
     // small batches: per-candidate tiles in global memory that split workgroups merge into
-    int *d_touched = nullptr;              // MODE_SPLIT_GEO: per (candidate, tile) the number of the pass that last drew into it
-    size_t touched_cap = 0;
+    DevBuf<int> d_touched;                 // MODE_SPLIT_GEO: per (candidate, tile) the number of the pass that last drew into it
     int pass_id = 0;
     bool mvp_valid = false;                // d_mvp holds the resident candidates' matrices (not after a pass that kept them in LDS)
-    uint32_t *d_gtile = nullptr;
-    size_t gtile_cap = 0;
+    DevBuf<uint32_t> d_gtile;
     bool gtile_dirty = true;
     // MODE_SPLIT: busy workgroups aimed at per launch (one generation: 2 per CU), fewest / most per (tile, candidate), and the
     // workgroups per launch of the scoring pass that follows.  Measured at 160x90, 640x360 and 640x480 (tools/r02_split_tune.sh).
@@ -106,48 +102,41 @@ struct rope_ctx {
     int layer_min_wg = 64;                 // fewest busy workgroups of a shared-layer launch for it to pay in a small batch (layers_pay)
     int strategy = 0;                          // STRATEGY_* bits (rope_set_strategy): launch structure only, never a result
     // large batches: queue of the (candidate, tile) pairs with something to draw, worked off by a grid that just fills the chip
-    uint32_t *d_qitems = nullptr, *d_tile_tris = nullptr, *d_tile_tris_lo = nullptr;
+    DevBuf<uint32_t> d_qitems, d_tile_tris, d_tile_tris_lo;
     size_t q_segment = 0;
     bool q_weighted = false;
-    int *d_qctr = nullptr;                     // [0] pairs queued, [1] next pair to hand out; cleared by fk_mvp_kernel
+    DevBuf<int> d_qctr;                        // [0] pairs queued, [1] next pair to hand out; cleared by fk_mvp_kernel
     int n_cu = 256;
 
     // stored lookup table (cropped sqrt-depth of a pose grid)
-    float *d_table = nullptr;                  // dense rows while a table is built (freed once it is packed)
-    size_t table_cap = 0;
+    DevBuf<float> d_table;                     // dense rows while a table is built (released once it is packed)
     // the stored table (rope_lookup_build): per row d_tcount groups of four samples from d_toff on — d_tgoff: where in the crop,
     // d_tgval: the four values
-    uint32_t *d_tcount = nullptr, *d_tgoff = nullptr;
-    unsigned long long *d_toff = nullptr, *d_tused = nullptr;
-    float4 *d_tgval = nullptr;
-    uint64_t *d_ttotal = nullptr;
-    float *d_tc = nullptr;                  // rope_lookup_score: the cropped target, rows padded to whole groups (table_crop_words)
-    size_t tc_cap = 0;
-    size_t trow_cap = 0;
+    DevBuf<uint32_t> d_tcount, d_tgoff;
+    DevBuf<unsigned long long> d_toff, d_tused;
+    DevBuf<float4> d_tgval;
+    DevBuf<uint64_t> d_ttotal;
+    DevBuf<float> d_tc;                     // rope_lookup_score: the cropped target, rows padded to whole groups (table_crop_words)
     int table_C = 0, table_crop[4] = {0, 0, 0, 0};
     size_t table_groups = 0;                   // groups the stored table holds
-    uint64_t *d_zero_total = nullptr;
+    DevBuf<uint64_t> d_zero_total;
     // scores of the table's rows: buffers of their own (a grid may hold more rows than one candidate batch)
-    uint64_t *d_tsums = nullptr;
-    double *d_terr = nullptr;
-    int tscore_cap = 0;
+    DevBuf<uint64_t> d_tsums;
+    DevBuf<double> d_terr;
 
     // camera-pose path: frames (joint vector + target planes each) scored under candidate views
     int n_frames = 0;
     bool frames_t32 = false, frames_tl = false;
     std::vector<double> h_fq;               // n_frames x 6
-    uint64_t *d_ftq = nullptr, *d_ftl = nullptr, *d_ftotal = nullptr, *d_fempty = nullptr;
-    float *d_ft32 = nullptr;
+    DevBuf<uint64_t> d_ftq, d_ftl, d_ftotal, d_fempty;
+    DevBuf<float> d_ft32;
     // one pinned host block and its device twin per rope_eval_views call: candidates | view matrices | view index | frame index
-    unsigned char *h_vstage = nullptr, *d_vstage = nullptr;
-    size_t vstage_cap = 0;
-    const double *dv_cand = nullptr, *dv_PV = nullptr;
+    PinnedBuf<unsigned char> h_vstage;
+    DevBuf<unsigned char> d_vstage;
+    const double *dv_cand = nullptr, *dv_PV = nullptr;                  // into d_vstage (dv_PV: or d_PV)
     const int32_t *dv_view_of = nullptr, *dv_frame_of = nullptr;
-    uint64_t *h_vsums = nullptr;            // pinned: K x N x 23 sums, then N x 23 totals
-    unsigned char *h_copy = nullptr;        // pinned: staging of pageable host buffers on their way up (copy_h2d_staged)
-    size_t vsums_cap = 0;
-    size_t frames_cap = 0, frames_tl_cap = 0, frames_t32_cap = 0;
-    int ftotal_cap = 0;
+    PinnedBuf<uint64_t> h_vsums;            // K x N x 23 sums, then N x 23 totals
+    PinnedBuf<unsigned char> h_copy;        // staging of pageable host buffers on their way up (copy_h2d_staged)
     bool ftotal_valid[5] = {false, false, false, false, false};   // per loss kind: d_ftotal[loss] holds the frames' "nothing rendered" totals
 
     // batched prediction (rope_set_targets / rope_eval_targets / rope_lookup_score_targets): the targets of n_targets frames.  The
@@ -155,24 +144,18 @@ struct rope_ctx {
     // kind unsets the other.
     int n_targets = 0;
     bool targets_t32 = false, targets_ts = false;
-    float *d_fts32 = nullptr;               // TensorSweep planes (the whole target depth as float32), when given
-    size_t fts_cap = 0;
-    LinkFlags *d_fflags = nullptr;          // per frame
-    int fflags_cap = 0;
-    uint64_t *d_tg_total[4] = {nullptr, nullptr, nullptr, nullptr};   // per loss: n_targets x SUM_WORDS "nothing rendered" totals
-    uint64_t *d_tg_empty = nullptr;         // scratch: n_targets x n_tiles x SUM_WORDS
-    int tg_total_cap = 0;
-    size_t tg_empty_cap = 0;
+    DevBuf<float> d_fts32;                  // TensorSweep planes (the whole target depth as float32), when given
+    DevBuf<LinkFlags> d_fflags;             // per frame
+    DevBuf<uint64_t> d_tg_total[4];         // per loss: n_targets x SUM_WORDS "nothing rendered" totals
+    DevBuf<uint64_t> d_tg_empty;            // scratch: n_targets x n_tiles x SUM_WORDS
     bool tg_total_valid[4] = {false, false, false, false};
     // rope_stage_targets / rope_commit_targets: the NEXT set of targets, uploaded on a stream of its own while the resident set is
     // in use; committing swaps the two sets of planes
     hipStream_t copy_stream = nullptr;
-    unsigned char *h_copy2 = nullptr;       // pinned block for pageable sources on the upload stream
-    uint64_t *s_ftq = nullptr;
-    float *s_ft32 = nullptr, *s_fts32 = nullptr;
-    LinkFlags *s_fflags = nullptr;
-    size_t s_frames_cap = 0, s_t32_cap = 0, s_fts_cap = 0;
-    int s_fflags_cap = 0;
+    PinnedBuf<unsigned char> h_copy2;       // pinned block for pageable sources on the upload stream
+    DevBuf<uint64_t> s_ftq;
+    DevBuf<float> s_ft32, s_fts32;
+    DevBuf<LinkFlags> s_fflags;
     int staged_n = 0, staged_W = 0, staged_H = 0;
     std::string stage_err;                  // rope_stage_targets may run beside an evaluation: its own message
     bool staged_t32 = false, staged_ts = false;
@@ -180,37 +163,32 @@ struct rope_ctx {
     // which rope_commit_targets waits for; the calls' small tables (plane offsets, link codes) go up through a page-locked block
     // that is only ever appended to while a set is being filled, so no call waits for the one before it.
     std::vector<hipEvent_t> stage_events;
-    unsigned long long *s_counts = nullptr;   // per staged frame: n_mask, n_depth per link
-    int s_counts_cap = 0;
-    int32_t *h_meta = nullptr, *d_meta = nullptr;
-    size_t meta_cap = 0, meta_used = 0;       // int32 words
+    DevBuf<unsigned long long> s_counts;      // per staged frame: n_mask, n_depth per link
+    PinnedBuf<int32_t> h_meta;
+    DevBuf<int32_t> d_meta;                   // as large as h_meta
+    size_t meta_used = 0;                     // int32 words
     std::vector<uint8_t> seg_filled;          // per slot of the set being filled
     int seg_n_total = 0, seg_n_filled = 0;    // seg_n_total 0: no set is being filled
     bool seg_ts = false;
     int tg_crop[4][4] = {};
-    int32_t *d_frame_of = nullptr, *h_frame_of = nullptr, *d_frame_of_host = nullptr;   // rows' frame indices: device copy / mapped host memory (small batches)
-    int frame_of_cap = 0;
-    const int32_t *frame_of_dev = nullptr;
+    DevBuf<int32_t> d_frame_of;               // rows' frame indices: device copy / mapped host memory (small batches)
+    PinnedBuf<int32_t> h_frame_of{true};
+    const int32_t *frame_of_dev = nullptr;    // d_frame_of or h_frame_of.dev()
     // the stored lookup table against all targets
-    float *d_tg_t32c = nullptr;
-    uint64_t *d_tg_ltotal = nullptr;
-    double *d_tg_scores = nullptr, *d_tg_best = nullptr;
-    size_t tg_t32c_cap = 0, tg_scores_cap = 0;
-    int tg_best_cap = 0;
+    DevBuf<float> d_tg_t32c;
+    DevBuf<uint64_t> d_tg_ltotal;
+    DevBuf<double> d_tg_scores, d_tg_best;
     // single target: the float32 plane ROPE_LOSS_TSWEEP reads when it is not the lookup plane (rope_set_target_tsweep)
-    float *d_t32ts = nullptr;
+    DevBuf<float> d_t32ts;
     bool have_t32ts = false;
 
     // rope_coverage's plane
-    uint8_t *d_cover = nullptr;
-    // rope_render_batch: the output planes of one chunk of poses (elements allocated)
-    float *d_rdepth = nullptr;
-    uint8_t *d_rids = nullptr;
-    size_t rdepth_cap = 0, rids_cap = 0;
-    // rope_render_masks: one chunk's label planes and boxes (elements allocated)
-    uint8_t *d_rmask = nullptr;
-    int32_t *d_rboxes = nullptr;
-    size_t rmask_cap = 0, rboxes_cap = 0;
+    DevBuf<uint8_t> d_cover;
+    // the chunked render path (render_chunks): the output planes of one chunk of poses — depth and ids for rope_render_batch, ids,
+    // label planes and boxes for rope_render_masks
+    DevBuf<float> d_rdepth;
+    DevBuf<uint8_t> d_rids, d_rmask;
+    DevBuf<int32_t> d_rboxes;
 };
 
 // ---- roctx ranges (the reference times its stages with utils.Timer / FancyTimer, robotpose/utils.py:122-180).
@@ -245,7 +223,7 @@ struct RopeRange {
 
 #define HIP_TRY(ctx, expr)                                                                     \
     do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
+        hipError_t e_ = static_cast<hipError_t>(expr);                                                              \
         if (e_ != hipSuccess) {                                                                \
             (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                    \
             return ROPE_E_HIP;                                                                 \
@@ -258,11 +236,31 @@ struct RopeRange {
         return ROPE_E_ARG;      \
     } while (0)
 
-template <typename T>
-static hipError_t realloc_dev(T **p, size_t n)
+// what rope_buffers.h allocates with
+int rope_dev_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+int rope_dev_free(void *p) { return hipFree(p); }
+int rope_pinned_free(void *p) { return hipHostFree(p); }
+int rope_pinned_alloc(void **p, size_t bytes, void **dev_alias)
 {
-    if (*p) { hipError_t e = hipFree(*p); *p = nullptr; if (e != hipSuccess) return e; }
-    return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T));
+    hipError_t e = hipHostMalloc(p, bytes, dev_alias ? hipHostMallocMapped : hipHostMallocDefault);
+    if (e != hipSuccess || !dev_alias) return e;
+    e = hipHostGetDevicePointer(dev_alias, *p, 0);
+    if (e != hipSuccess) { (void)hipHostFree(*p); *p = nullptr; }
+    return e;
+}
+
+// Grow-or-keep for buffers that work in flight on the context's stream may still use: (buffer, elements) pairs; when one of
+// them is too small the stream is waited for, once, and every one is grown.  Nothing happens, and nothing is waited for, otherwise.
+static bool any_short() { return false; }
+template <typename B, typename... R> static bool any_short(const B &b, size_t n, const R &...r) { return n > b.cap() || any_short(r...); }
+static int grow_each() { return 0; }
+template <typename B, typename... R> static int grow_each(B &b, size_t n, R &...r) { const int e = b.grow(n); return e ? e : grow_each(r...); }
+template <typename... A> static int sync_grow(rope_ctx *c, A &&...a)
+{
+    if (!any_short(a...)) return ROPE_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, grow_each(a...));
+    return ROPE_OK;
 }
 
 static thread_local std::string g_create_err;
@@ -296,18 +294,9 @@ extern "C" int rope_create(rope_ctx **out, int device)
         delete c;
         return ROPE_E_HIP;
     }
-    if (hipHostMalloc((void **)&c->h_err, (rope_ctx::TARGET_HOST_ROWS + 2) * sizeof(double), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&c->d_err_host, c->h_err, 0) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_cand, 6 * rope_ctx::TARGET_HOST_ROWS * sizeof(double), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&c->d_cand_host, c->h_cand, 0) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_frame_of, rope_ctx::TARGET_HOST_ROWS * sizeof(int32_t), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&c->d_frame_of_host, c->h_frame_of, 0) != hipSuccess ||
-        hipMalloc((void **)&c->d_best_idx, sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void **)&c->d_qctr, 2 * QUEUE_COUNTERS * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&c->d_best_err, sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&c->d_PV, 16 * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&c->d_joint_fixed, 72 * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&c->d_joint_axes, 18 * sizeof(double)) != hipSuccess) {
+    if (c->h_err.reset(rope_ctx::TARGET_HOST_ROWS + 2) || c->h_cand.reset(6 * rope_ctx::TARGET_HOST_ROWS) ||
+        c->h_frame_of.reset(rope_ctx::TARGET_HOST_ROWS) || c->d_best_idx.reset(1) || c->d_qctr.reset(2 * QUEUE_COUNTERS) ||
+        c->d_best_err.reset(1) || c->d_PV.reset(16) || c->d_joint_fixed.reset(72) || c->d_joint_axes.reset(18)) {
         g_create_err = "hipMalloc failed";
         delete c;
         return ROPE_E_NOMEM;
@@ -339,20 +328,20 @@ extern "C" void rope_host_free(void *p)
 
 // `stream` / `block` / `err`: the context's own stream, pinned block and message by default; rope_stage_targets, which may run beside
 // an evaluation on another thread, passes the upload stream and a block and a message of its own
-static int copy_h2d_on(hipStream_t stream, unsigned char **block, std::string &err, void *dst, const void *src, size_t bytes)
+static int copy_h2d_on(hipStream_t stream, PinnedBuf<unsigned char> &block, std::string &err, void *dst, const void *src, size_t bytes)
 {
     constexpr size_t CHUNK = 8u << 20;
     auto failed = [&](hipError_t e, const char *what) { if (e != hipSuccess) err = std::string(what) + ": " + hipGetErrorString(e); return e != hipSuccess; };
     if (bytes >= (64u << 10) && is_pinned_host(src))       // already page-locked: one copy at the link's rate, no staging; the caller synchronises
         return failed(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync (host to device)") ? ROPE_E_HIP : ROPE_OK;
-    if (!*block && failed(hipHostMalloc((void **)block, 2 * CHUNK, hipHostMallocDefault), "hipHostMalloc (copy block)")) return ROPE_E_HIP;   // two halves, alternating
+    if (failed(static_cast<hipError_t>(block.grow(2 * CHUNK)), "hipHostMalloc (copy block)")) return ROPE_E_HIP;   // two halves, alternating
     int half = 0;
     for (size_t off = 0; off < bytes; off += CHUNK, half ^= 1) {
         const size_t n = std::min(CHUNK, bytes - off);
         // the half about to be overwritten is free again
         if ((off >= 2 * CHUNK || off == 0) && failed(hipStreamSynchronize(stream), "hipStreamSynchronize (copy block)")) return ROPE_E_HIP;
-        std::memcpy(*block + half * CHUNK, static_cast<const unsigned char *>(src) + off, n);
-        if (failed(hipMemcpyAsync(static_cast<unsigned char *>(dst) + off, *block + half * CHUNK, n, hipMemcpyHostToDevice, stream), "hipMemcpyAsync (host to device)"))
+        std::memcpy(block + half * CHUNK, static_cast<const unsigned char *>(src) + off, n);
+        if (failed(hipMemcpyAsync(static_cast<unsigned char *>(dst) + off, block + half * CHUNK, n, hipMemcpyHostToDevice, stream), "hipMemcpyAsync (host to device)"))
             return ROPE_E_HIP;
     }
     return ROPE_OK;
@@ -360,13 +349,13 @@ static int copy_h2d_on(hipStream_t stream, unsigned char **block, std::string &e
 
 static int copy_h2d_staged(rope_ctx *c, void *dst, const void *src, size_t bytes)
 {
-    return copy_h2d_on(c->stream, &c->h_copy, c->err, dst, src, bytes);
+    return copy_h2d_on(c->stream, c->h_copy, c->err, dst, src, bytes);
 }
 
 static int copy_d2h_staged(rope_ctx *c, void *dst, const void *src, size_t bytes)
 {
     constexpr size_t CHUNK = 8u << 20;
-    if (!c->h_copy) HIP_TRY(c, hipHostMalloc((void **)&c->h_copy, 2 * CHUNK, hipHostMallocDefault));
+    HIP_TRY(c, c->h_copy.grow(2 * CHUNK));
     for (size_t off = 0; off < bytes; off += 2 * CHUNK) {
         const size_t n = std::min(2 * CHUNK, bytes - off);
         HIP_TRY(c, hipMemcpyAsync(c->h_copy, static_cast<const unsigned char *>(src) + off, n, hipMemcpyDeviceToHost, c->stream));
@@ -384,26 +373,10 @@ extern "C" void rope_destroy(rope_ctx *c)
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     for (hipEvent_t e : c->stage_events) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
     c->stage_events.clear();
-    void *ptrs[] = {c->d_header, c->d_tris, c->d_verts, c->d_joint_fixed, c->d_joint_axes, c->d_PV, c->d_tq, c->d_t32,
-                    c->d_cand, c->d_err, c->d_best_err, c->d_mvp, c->d_bounds, c->d_mask_lo, c->d_mask_hi, c->d_layer_of, c->d_layer_rep, c->d_layers, c->d_layer_sums, c->d_parent_of, c->d_parent_rep, c->d_parents, c->d_table, c->d_tcount, c->d_toff, c->d_tused, c->d_tgoff, c->d_tgval, c->d_ttotal, c->d_zero_total, c->d_tsums, c->d_terr, c->d_qitems, c->d_tile_tris, c->d_tile_tris_lo, c->d_qctr, c->d_touched, c->d_gtile, c->d_aabb, c->d_sums, c->d_best_idx,
-                    c->d_rdepth, c->d_rids, c->d_rmask, c->d_rboxes, c->d_cover, c->d_ftq, c->d_ftl, c->d_ftotal, c->d_fempty, c->d_ft32, c->d_vstage, c->d_empty[0], c->d_empty[1], c->d_empty[2], c->d_empty[3],
-                    c->d_total[0], c->d_total[1], c->d_total[2], c->d_total[3], c->d_fts32, c->d_fflags, c->d_tg_total[0], c->d_tg_total[1], c->d_tg_total[2],
-                    c->d_tg_total[3], c->d_tg_empty, c->d_frame_of, c->d_tg_t32c, c->d_tg_ltotal, c->d_tg_scores, c->d_tg_best, c->d_t32ts, c->d_tc,
-                    c->s_ftq, c->s_ft32, c->s_fts32, c->s_fflags, c->s_counts, c->d_meta};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_err) (void)hipHostFree(c->h_err);
-    if (c->h_cand) (void)hipHostFree(c->h_cand);
-    if (c->h_frame_of) (void)hipHostFree(c->h_frame_of);
-    if (c->h_vstage) (void)hipHostFree(c->h_vstage);
-    if (c->h_vsums) (void)hipHostFree(c->h_vsums);
-    if (c->h_copy) (void)hipHostFree(c->h_copy);
-    if (c->h_copy2) (void)hipHostFree(c->h_copy2);
-    if (c->h_meta) (void)hipHostFree(c->h_meta);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    const hipStream_t stream = c->stream, copy_stream = c->copy_stream;
+    delete c;                                     // every buffer goes with it: before the streams, as ever
+    if (copy_stream) (void)hipStreamDestroy(copy_stream);
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 #ifndef ROPE_BUILD_ID
@@ -475,10 +448,10 @@ extern "C" int rope_set_robot(rope_ctx *c, const uint32_t *ml_header, int n_mesh
     }
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, realloc_dev(&c->d_header, 8 * (size_t)n_meshlets));
-    HIP_TRY(c, realloc_dev(&c->d_verts, 3 * (size_t)n_ml_verts));
-    HIP_TRY(c, realloc_dev(&c->d_tris, (size_t)n_ml_tris));
-    HIP_TRY(c, realloc_dev(&c->d_aabb, 8 * (size_t)n_meshlets));
+    HIP_TRY(c, c->d_header.reset(8 * (size_t)n_meshlets));
+    HIP_TRY(c, c->d_verts.reset(3 * (size_t)n_ml_verts));
+    HIP_TRY(c, c->d_tris.reset((size_t)n_ml_tris));
+    HIP_TRY(c, c->d_aabb.reset(8 * (size_t)n_meshlets));
     HIP_TRY(c, hipMemcpyAsync(c->d_aabb, aabb.data(), 32 * (size_t)n_meshlets, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_header, ml_header, 32 * (size_t)n_meshlets, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_verts, ml_verts, 12 * (size_t)n_ml_verts, hipMemcpyHostToDevice, c->stream));
@@ -530,13 +503,13 @@ extern "C" int rope_set_camera(rope_ctx *c, const double *PV, int W, int H, doub
         c->C = 0;
         c->cand_valid = c->results_valid = false;
         const size_t n = (size_t)W * H;
-        HIP_TRY(c, realloc_dev(&c->d_tq, n));
-        HIP_TRY(c, realloc_dev(&c->d_t32, n));
-        HIP_TRY(c, realloc_dev(&c->d_t32ts, n));
-        HIP_TRY(c, realloc_dev(&c->d_cover, n));
+        HIP_TRY(c, c->d_tq.reset(n));
+        HIP_TRY(c, c->d_t32.reset(n));
+        HIP_TRY(c, c->d_t32ts.reset(n));
+        HIP_TRY(c, c->d_cover.reset(n));
         for (int k = 0; k < 4; k++) {
-            HIP_TRY(c, realloc_dev(&c->d_empty[k], (size_t)n_tiles * ROPE_SUM_WORDS));
-            HIP_TRY(c, realloc_dev(&c->d_total[k], (size_t)ROPE_SUM_WORDS));
+            HIP_TRY(c, c->d_empty[k].reset((size_t)n_tiles * ROPE_SUM_WORDS));
+            HIP_TRY(c, c->d_total[k].reset((size_t)ROPE_SUM_WORDS));
             c->empty_version[k] = 0;
         }
     }
@@ -962,28 +935,27 @@ static int ensure_capacity(rope_ctx *c, int C)
     if (C <= c->cap) return ROPE_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     int cap = C < 64 ? 64 : C;
-    HIP_TRY(c, realloc_dev(&c->d_cand, 6 * (size_t)cap));
-    HIP_TRY(c, realloc_dev(&c->d_err, (size_t)cap + 2));      // errors, then best error and best index
-    if (c->h_stage) { (void)hipHostFree(c->h_stage); c->h_stage = nullptr; }
-    HIP_TRY(c, hipHostMalloc((void **)&c->h_stage, ((size_t)cap * 6 + 2) * sizeof(double), hipHostMallocDefault));
-    HIP_TRY(c, realloc_dev(&c->d_mvp, (size_t)cap * ROPE_MAX_LINKS * 16));
+    HIP_TRY(c, c->d_cand.reset(6 * (size_t)cap));
+    HIP_TRY(c, c->d_err.reset((size_t)cap + 2));              // errors, then best error and best index
+    HIP_TRY(c, c->h_stage.reset((size_t)cap * 6 + 2));
+    HIP_TRY(c, c->d_mvp.reset((size_t)cap * ROPE_MAX_LINKS * 16));
     if (!c->have_robot || !c->have_camera) ARG_FAIL(c, "candidates: robot and camera must be set first");
-    HIP_TRY(c, realloc_dev(&c->d_bounds, (size_t)cap * c->n_meshlets));
-    HIP_TRY(c, realloc_dev(&c->d_mask_lo, (size_t)cap * c->mask_words));
-    HIP_TRY(c, realloc_dev(&c->d_mask_hi, (size_t)cap * c->mask_words));
-    HIP_TRY(c, realloc_dev(&c->d_layer_of, (size_t)cap));
-    HIP_TRY(c, realloc_dev(&c->d_sums, (size_t)cap * ROPE_SUM_WORDS));
+    HIP_TRY(c, c->d_bounds.reset((size_t)cap * c->n_meshlets));
+    HIP_TRY(c, c->d_mask_lo.reset((size_t)cap * c->mask_words));
+    HIP_TRY(c, c->d_mask_hi.reset((size_t)cap * c->mask_words));
+    HIP_TRY(c, c->d_layer_of.reset((size_t)cap));
+    HIP_TRY(c, c->d_sums.reset((size_t)cap * ROPE_SUM_WORDS));
     // raster queue: QUEUE_CLASSES segments (pairs by weight, heaviest first) and the per-(candidate, tile) weights, when the frame
     // has few enough tiles for the weights and the segments stay small; otherwise one segment, pairs in candidate order
     const size_t seg = (size_t)cap * c->mask_words * 32;
     c->q_weighted = c->n_tiles <= QUEUE_WEIGHT_TILES && 2 * seg * QUEUE_CLASSES * sizeof(uint32_t) <= ((size_t)512 << 20);
     c->q_segment = c->q_weighted ? seg : 0;
-    HIP_TRY(c, realloc_dev(&c->d_qitems, c->q_weighted ? 2 * seg * QUEUE_CLASSES : seg));      // weighted: the scoring queue, then the layer queue
-    if (c->d_tile_tris) { (void)hipFree(c->d_tile_tris); c->d_tile_tris = nullptr; }
-    if (c->d_tile_tris_lo) { (void)hipFree(c->d_tile_tris_lo); c->d_tile_tris_lo = nullptr; }
+    HIP_TRY(c, c->d_qitems.reset(c->q_weighted ? 2 * seg * QUEUE_CLASSES : seg));      // weighted: the scoring queue, then the layer queue
+    c->d_tile_tris.release();
+    c->d_tile_tris_lo.release();
     if (c->q_weighted) {
-        HIP_TRY(c, realloc_dev(&c->d_tile_tris, (size_t)cap * c->n_tiles));
-        HIP_TRY(c, realloc_dev(&c->d_tile_tris_lo, (size_t)cap * c->n_tiles));
+        HIP_TRY(c, c->d_tile_tris.reset((size_t)cap * c->n_tiles));
+        HIP_TRY(c, c->d_tile_tris_lo.reset((size_t)cap * c->n_tiles));
     }
     c->cap = cap;
     return ROPE_OK;
@@ -1010,19 +982,15 @@ static int upload_candidates(rope_ctx *c, const double *cand, int C, bool group,
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // the staging buffer may still feed an earlier copy
     if (C <= (frame_of ? rope_ctx::TARGET_HOST_ROWS : rope_ctx::HOST_ERR_ROWS)) {            // nothing is in flight (synchronised above): the kernels of the next pass read it in place
         std::memcpy(c->h_cand, cand, 6 * (size_t)C * sizeof(double));
-        c->cand_dev = c->d_cand_host;
-        if (frame_of) { std::memcpy(c->h_frame_of, frame_of, (size_t)C * sizeof(int32_t)); c->frame_of_dev = c->d_frame_of_host; }
+        c->cand_dev = c->h_cand.dev();
+        if (frame_of) { std::memcpy(c->h_frame_of, frame_of, (size_t)C * sizeof(int32_t)); c->frame_of_dev = c->h_frame_of.dev(); }
     } else {
         std::memcpy(c->h_stage, cand, 6 * (size_t)C * sizeof(double));
         HIP_TRY(c, hipMemcpyAsync(c->d_cand, c->h_stage, 6 * (size_t)C * sizeof(double), hipMemcpyHostToDevice, c->stream));
         c->cand_dev = c->d_cand;
         if (frame_of) {
-            if (C > c->frame_of_cap) {
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                c->frame_of_cap = 0;
-                HIP_TRY(c, realloc_dev(&c->d_frame_of, (size_t)std::max(C, 1024)));
-                c->frame_of_cap = std::max(C, 1024);
-            }
+            rc = sync_grow(c, c->d_frame_of, (size_t)std::max(C, 1024));
+            if (rc) return rc;
             // pageable source: the copy has read it when the call returns
             HIP_TRY(c, hipMemcpyAsync(c->d_frame_of, frame_of, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             c->frame_of_dev = c->d_frame_of;
@@ -1058,20 +1026,13 @@ static int upload_candidates(rope_ctx *c, const double *cand, int C, bool group,
         c->n_layers = (int)layer_rep.size();
         c->n_parents = (int)parent_rep.size();
         if (c->n_layers * 4 <= C) {                // same rule as want_layers(): only then are the arrays read
-            if (c->n_layers > c->layer_rep_cap) {
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                HIP_TRY(c, realloc_dev(&c->d_layer_rep, (size_t)c->n_layers));
-                c->layer_rep_cap = c->n_layers;
-            }
+            rc = sync_grow(c, c->d_layer_rep, (size_t)c->n_layers);
+            if (rc) return rc;
             HIP_TRY(c, hipMemcpyAsync(c->d_layer_of, layer_of.data(), (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             HIP_TRY(c, hipMemcpyAsync(c->d_layer_rep, layer_rep.data(), layer_rep.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             if (c->n_parents * 4 <= c->n_layers) {     // same rule one level up (want_parents())
-                if (c->n_layers > c->parent_idx_cap) {
-                    HIP_TRY(c, hipStreamSynchronize(c->stream));
-                    HIP_TRY(c, realloc_dev(&c->d_parent_of, (size_t)c->n_layers));
-                    HIP_TRY(c, realloc_dev(&c->d_parent_rep, (size_t)c->n_layers));
-                    c->parent_idx_cap = c->n_layers;
-                }
+                rc = sync_grow(c, c->d_parent_of, (size_t)c->n_layers, c->d_parent_rep, (size_t)c->n_layers);
+                if (rc) return rc;
                 HIP_TRY(c, hipMemcpyAsync(c->d_parent_of, parent_of.data(), parent_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
                 HIP_TRY(c, hipMemcpyAsync(c->d_parent_rep, parent_rep.data(), parent_rep.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             }
@@ -1132,12 +1093,7 @@ static bool layers_pay(const rope_ctx *c)
 static int ensure_layers(rope_ctx *c)
 {
     size_t need = (size_t)c->n_layers * c->n_tiles * (TILE_W * TILE_H);
-    if (need <= c->layers_cap) return ROPE_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, realloc_dev(&c->d_layers, need));
-    HIP_TRY(c, realloc_dev(&c->d_layer_sums, (size_t)c->n_layers * c->n_tiles * ROPE_SUM_WORDS));
-    c->layers_cap = need;
-    return ROPE_OK;
+    return sync_grow(c, c->d_layers, need, c->d_layer_sums, (size_t)c->n_layers * c->n_tiles * ROPE_SUM_WORDS);
 }
 
 static bool want_parents(const rope_ctx *c) { return c->n_parents * 4 <= c->n_layers; }
@@ -1159,11 +1115,7 @@ static int enqueue_layers(rope_ctx *c, RasterArgs la, int loss, int n_shared, co
     la.cand_of_row = c->d_layer_rep; la.layers = c->d_layers;
     if (use_parents(c, n_shared)) {
         const size_t need = (size_t)c->n_parents * c->n_tiles * (TILE_W * TILE_H);
-        if (need > c->parents_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            HIP_TRY(c, realloc_dev(&c->d_parents, need));
-            c->parents_cap = need;
-        }
+        if (int rc = sync_grow(c, c->d_parents, need)) return rc;
         RasterArgs pa = la;
         pa.l_begin = 0; pa.l_end = 2; pa.cand_of_row = c->d_parent_rep; pa.layers = c->d_parents; pa.layer_sums = nullptr;
         HIP_TRY(c, launch_raster(MODE_LAYER, loss, c->n_parents, c->stream, fp, c->rp, pa, use_clip(c)));
@@ -1256,30 +1208,26 @@ static int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &
     RasterArgs a = base_args(c, n_render);
     if (split > 1) {
         const size_t need = (size_t)c->C * c->n_tiles * (TILE_W * TILE_H);
-        if (need > c->gtile_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            HIP_TRY(c, realloc_dev(&c->d_gtile, need));
-            c->gtile_cap = need;
+        if (need > c->d_gtile.cap()) {
+            if (int rc = sync_grow(c, c->d_gtile, need)) return rc;
             c->gtile_dirty = true;
         }
         // the scoring kernel hands the buffer back "empty"; clear it only when new, after a failed pass, or when a
         // profiling flag may have skipped that kernel's work
-        if (c->gtile_dirty || ROPE_SKIP(fp, ~0)) HIP_TRY(c, hipMemsetAsync(c->d_gtile, 0xFF, c->gtile_cap * sizeof(uint32_t), c->stream));
+        if (c->gtile_dirty || ROPE_SKIP(fp, ~0)) HIP_TRY(c, hipMemsetAsync(c->d_gtile, 0xFF, c->d_gtile.cap() * sizeof(uint32_t), c->stream));
         c->gtile_dirty = true;
         RasterArgs sa = a;
         sa.split = split; sa.gtile = c->d_gtile;
         if (geo) {
-            if ((size_t)c->C * c->n_tiles > c->touched_cap) {
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                HIP_TRY(c, realloc_dev(&c->d_touched, (size_t)256 * c->n_tiles));
+            if ((size_t)c->C * c->n_tiles > c->d_touched.cap()) {      // C <= geo_rows <= 256: room for any such batch at once
+                if (int rc = sync_grow(c, c->d_touched, (size_t)256 * c->n_tiles)) return rc;
                 HIP_TRY(c, hipMemsetAsync(c->d_touched, 0, (size_t)256 * c->n_tiles * sizeof(int), c->stream));     // ordered with the kernels that stamp it
-                c->touched_cap = (size_t)256 * c->n_tiles;
             }
             sa.cand_q = c->cand_dev; sa.joint_fixed = c->d_joint_fixed; sa.joint_axes = c->d_joint_axes; sa.PV = c->d_PV;
             sa.sums = c->d_sums;
             sa.touched = c->d_touched;
             if (c->pass_id == 0x7FFFFFFF) {                 // the stamp wraps after 2^31 passes: start over on a clean array
-                HIP_TRY(c, hipMemsetAsync(c->d_touched, 0, c->touched_cap * sizeof(int), c->stream));
+                HIP_TRY(c, hipMemsetAsync(c->d_touched, 0, c->d_touched.cap() * sizeof(int), c->stream));
                 c->pass_id = 0;
             }
             sa.pass_id = ++c->pass_id;
@@ -1320,10 +1268,10 @@ static int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &
     c->err_on_host = c->C <= (targets ? rope_ctx::TARGET_HOST_ROWS : rope_ctx::HOST_ERR_ROWS);
     if (targets)                                   // every row against its own frame's totals and link flags; no argmin (rows of many frames)
         HIP_TRY(c, launch_finalize_frames(c->stream, c->d_sums, c->d_tg_total[loss], c->frame_of_dev, c->d_fflags, c->C, loss, n_render, n_pix,
-                                          c->err_on_host ? c->d_err_host : c->d_err));
+                                          c->err_on_host ? c->h_err.dev() : c->d_err.get()));
     else
         HIP_TRY(c, launch_finalize(c->stream, c->d_sums, c->d_total[loss], c->C, loss, n_render, n_pix, c->lf,
-                                   c->err_on_host ? c->d_err_host : c->d_err));
+                                   c->err_on_host ? c->h_err.dev() : c->d_err.get()));
     if (ev) HIP_TRY(c, hipEventRecord(ev[4], c->stream));
     c->last_n_render = n_render;
     c->results_valid = true;
@@ -1356,7 +1304,7 @@ extern "C" int rope_results_download(rope_ctx *c, double *err_out, uint64_t *sum
     if (c->C < 1 || !c->results_valid) ARG_FAIL(c, "rope_results_download: nothing evaluated (results do not survive rope_eval_views / rope_lookup_score / a new upload)");
     HIP_TRY(c, hipSetDevice(c->device));
     // one copy brings the errors, the best error and the best index (pinned staging)
-    const double *res = c->err_on_host ? c->h_err : c->h_stage;
+    const double *res = c->err_on_host ? c->h_err.get() : c->h_stage.get();
     if (!c->err_on_host) HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_err, ((size_t)c->C + 2) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (sums_out) HIP_TRY(c, hipMemcpyAsync(sums_out, c->d_sums, (size_t)c->C * ROPE_SUM_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1431,60 +1379,58 @@ static int copy_d2h_out(rope_ctx *c, void *dst, const void *src, size_t bytes)
 // device bytes of output planes one chunk of rope_render_batch may hold
 static constexpr size_t RENDER_BATCH_BUDGET = (size_t)256 << 20;
 
-// rope_render_batch and rope_render_batch_device: `to_device` says where depth and ids point, and so how a chunk's planes leave
-static int render_batch(rope_ctx *c, const double *q, const double *PV, int N, int n_render, const int32_t *crop, float *depth, uint8_t *ids,
-                        bool to_device)
+// What an entry of the chunked render path asks for.  A chunk's planes: depth -> d_rdepth (cleared to 0), ids -> d_rids (to 0xFF),
+// labels -> d_rmask and d_rboxes (the boxes to 0xFF).
+struct RenderAsk {
+    const char *entry;                  // the entry's name, for the messages
+    const int32_t *crop;                // rows and columns to draw, or nullptr: the whole frame
+    bool depth, ids, labels;
+    const uint8_t *lut;                 // a 256-byte id -> label table that rides in the staging block, or nullptr
+};
+
+// rope_render_batch, rope_render_batch_device and rope_render_masks: N poses drawn chunk by chunk into the planes the entry asks
+// for.  own_checks() -> a message or nullptr: the entry's own arguments, checked where they always were (n_render is known good);
+// after(lo, n, px, lut_dev) -> code: what follows the raster launch of poses lo .. lo + n - 1 and takes the results away.
+template <typename Checks, typename After>
+static int render_chunks(rope_ctx *c, const RenderAsk &ask, const double *q, const double *PV, int N, int n_render, Checks own_checks, After after)
 {
-#define RB_FAIL(msg) ARG_FAIL(c, to_device ? "rope_render_batch_device: " msg : "rope_render_batch: " msg)      // the entry the caller used
-    if (!q) RB_FAIL("null joint vectors");
-    if (N < 1) RB_FAIL("need N >= 1");
-    if (!depth && !ids) RB_FAIL("no output (depth and ids both null)");
-    if (!c->have_robot || !c->have_camera) RB_FAIL("robot and camera must be set first");
-    if (n_render < 1 || n_render > c->n_links) RB_FAIL("n_render out of range");
+#define RC_FAIL(msg) do { c->err = std::string(ask.entry) + ": " msg; return ROPE_E_ARG; } while (0)
+    if (N < 1) RC_FAIL("need N >= 1");
+    if (!ask.depth && !ask.ids && !ask.labels) RC_FAIL("no output (depth and ids both null)");
+    if (!c->have_robot || !c->have_camera) RC_FAIL("robot and camera must be set first");
+    if (n_render < 1 || n_render > c->n_links) RC_FAIL("n_render out of range");
     FrameParams fp = c->fp;
-    if (crop) {
+    if (const int32_t *crop = ask.crop) {
         if (crop[0] < 0 || crop[1] >= fp.H || crop[0] > crop[1] || crop[2] < 0 || crop[3] >= fp.W || crop[2] > crop[3])
-            RB_FAIL("crop outside the image");
+            RC_FAIL("crop outside the image");
         fp.r0 = crop[0]; fp.r1 = crop[1]; fp.c0 = crop[2]; fp.c1 = crop[3];
     }
+    if (const char *msg = own_checks()) ARG_FAIL(c, msg);
     for (size_t i = 0; i < 6 * (size_t)N; i++)
-        if (!std::isfinite(q[i]) || std::fabs(q[i]) > 1.0e4) RB_FAIL("joint angle not finite or |q| > 1e4 rad");
+        if (!std::isfinite(q[i]) || std::fabs(q[i]) > 1.0e4) RC_FAIL("joint angle not finite or |q| > 1e4 rad");
     bool clip = use_clip(c);
     if (PV) {
         for (size_t i = 0; i < 16 * (size_t)N; i++)
-            if (!std::isfinite(PV[i])) RB_FAIL("non-finite view matrix");
+            if (!std::isfinite(PV[i])) RC_FAIL("non-finite view matrix");
         clip = c->strategy & STRATEGY_CLIP_KERNELS;                // the call's cameras decide, not the context's
         for (int i = 0; i < N && !clip; i++) clip = near_plane_in_reach(c, PV + 16 * (size_t)i);
     }
+#undef RC_FAIL
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t px = (size_t)(fp.r1 - fp.r0 + 1) * (size_t)(fp.c1 - fp.c0 + 1);
-    const size_t per_pose = px * ((depth ? sizeof(float) : 0) + (ids ? 1 : 0));
+    const size_t per_pose = px * ((ask.depth ? sizeof(float) : 0) + (ask.ids ? 1 : 0) + (ask.labels ? 1 : 0));
     const int chunk = (int)std::min<size_t>({(size_t)N, (size_t)MAX_ROWS, std::max<size_t>(1, RENDER_BATCH_BUDGET / per_pose)});
     int rc = ensure_capacity(c, chunk);
     if (rc) return rc;
-    if (depth && (size_t)chunk * px > c->rdepth_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->rdepth_cap = 0;
-        HIP_TRY(c, realloc_dev(&c->d_rdepth, (size_t)chunk * px));
-        c->rdepth_cap = (size_t)chunk * px;
-    }
-    if (ids && (size_t)chunk * px > c->rids_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->rids_cap = 0;
-        HIP_TRY(c, realloc_dev(&c->d_rids, (size_t)chunk * px));
-        c->rids_cap = (size_t)chunk * px;
-    }
-    // the rows of a chunk go up in one block, as rope_eval_views sends its own: joint vectors | view matrices | view index
+    if (ask.depth && (rc = sync_grow(c, c->d_rdepth, (size_t)chunk * px))) return rc;
+    if (ask.ids && (rc = sync_grow(c, c->d_rids, (size_t)chunk * px))) return rc;
+    if (ask.labels && ((rc = sync_grow(c, c->d_rmask, (size_t)chunk * px)) || (rc = sync_grow(c, c->d_rboxes, (size_t)chunk * 32)))) return rc;
+    // the rows of a chunk go up in one block, as rope_eval_views sends its own: joint vectors | view matrices | view index | the table
     const size_t off_pv = 6 * (size_t)chunk * sizeof(double), off_vo = off_pv + (PV ? 16 * (size_t)chunk * sizeof(double) : 0),
-                 bytes = off_vo + (PV ? (size_t)chunk * sizeof(int32_t) : 0);
-    if (bytes > c->vstage_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->h_vstage) { (void)hipHostFree(c->h_vstage); c->h_vstage = nullptr; }
-        c->vstage_cap = 0;
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_vstage, bytes, hipHostMallocDefault));
-        HIP_TRY(c, realloc_dev(&c->d_vstage, bytes));
-        c->vstage_cap = bytes;
-    }
+                 end_vo = off_vo + (PV ? (size_t)chunk * sizeof(int32_t) : 0), off_lut = (end_vo + 15) & ~(size_t)15,
+                 bytes = ask.lut ? off_lut + 256 : end_vo;
+    rc = sync_grow(c, c->h_vstage, bytes, c->d_vstage, bytes);
+    if (rc) return rc;
     // the per-candidate buffers hold render rows from here on (rope_eval_views does the same)
     c->cand_valid = c->results_valid = false;
     c->cand_dev = nullptr;
@@ -1498,34 +1444,50 @@ static int render_batch(rope_ctx *c, const double *q, const double *PV, int N, i
             int32_t *vo = reinterpret_cast<int32_t *>(c->h_vstage + off_vo);
             for (int i = 0; i < n; i++) vo[i] = i;
         }
+        if (ask.lut) std::memcpy(c->h_vstage + off_lut, ask.lut, 256);
         HIP_TRY(c, hipMemcpyAsync(c->d_vstage, c->h_vstage, bytes, hipMemcpyHostToDevice, c->stream));
-        c->dv_cand = reinterpret_cast<const double *>(c->d_vstage);
-        c->dv_PV = PV ? reinterpret_cast<const double *>(c->d_vstage + off_pv) : c->d_PV;
+        c->dv_cand = reinterpret_cast<const double *>(c->d_vstage.get());
+        c->dv_PV = PV ? reinterpret_cast<const double *>(c->d_vstage + off_pv) : c->d_PV.get();
         c->dv_view_of = PV ? reinterpret_cast<const int32_t *>(c->d_vstage + off_vo) : nullptr;
         c->C = n;
         c->n_layers = n;                                      // nothing shared: every row draws all its links
         rc = enqueue_geometry(c, n_render, 0, fp, true);
         if (rc) return rc;
-        if (depth) HIP_TRY(c, hipMemsetAsync(c->d_rdepth, 0, (size_t)n * px * sizeof(float), c->stream));
-        if (ids) HIP_TRY(c, hipMemsetAsync(c->d_rids, 0xFF, (size_t)n * px, c->stream));
+        if (ask.depth) HIP_TRY(c, hipMemsetAsync(c->d_rdepth, 0, (size_t)n * px * sizeof(float), c->stream));
+        if (ask.ids) HIP_TRY(c, hipMemsetAsync(c->d_rids, 0xFF, (size_t)n * px, c->stream));
+        if (ask.labels) HIP_TRY(c, hipMemsetAsync(c->d_rboxes, 0xFF, (size_t)n * 32 * sizeof(int32_t), c->stream));
         RasterArgs a = base_args(c, n_render);
-        a.depth_out = depth ? c->d_rdepth : nullptr;
-        a.ids_out = ids ? c->d_rids : nullptr;
+        a.depth_out = ask.depth ? c->d_rdepth.get() : nullptr;
+        a.ids_out = ask.ids ? c->d_rids.get() : nullptr;
         HIP_TRY(c, launch_raster(MODE_DUMP, ROPE_LOSS_DEPTH, n, c->stream, fp, c->rp, a, clip));
-        if (to_device) {                                      // in stream order: the next chunk's clearing comes after these copies
-            if (depth) HIP_TRY(c, hipMemcpyAsync(depth + (size_t)lo * px, c->d_rdepth, (size_t)n * px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            if (ids) HIP_TRY(c, hipMemcpyAsync(ids + (size_t)lo * px, c->d_rids, (size_t)n * px, hipMemcpyDeviceToDevice, c->stream));
-            continue;
-        }
-        if (depth) { rc = copy_d2h_out(c, depth + (size_t)lo * px, c->d_rdepth, (size_t)n * px * sizeof(float)); if (rc) return rc; }
-        if (ids) { rc = copy_d2h_out(c, ids + (size_t)lo * px, c->d_rids, (size_t)n * px); if (rc) return rc; }
+        rc = after(lo, n, px, ask.lut ? c->d_vstage + off_lut : nullptr);
+        if (rc) return rc;
     }
-    if (to_device) HIP_TRY(c, hipStreamSynchronize(c->stream));      // the planes are the caller's, on any stream, when the call returns
     c->C = 0;
     c->last_n_render = n_render;
     return ROPE_OK;
 }
-#undef RB_FAIL
+
+// rope_render_batch and rope_render_batch_device: `to_device` says where depth and ids point, and so how a chunk's planes leave
+static int render_batch(rope_ctx *c, const double *q, const double *PV, int N, int n_render, const int32_t *crop, float *depth, uint8_t *ids,
+                        bool to_device)
+{
+    const RenderAsk ask{to_device ? "rope_render_batch_device" : "rope_render_batch", crop, depth != nullptr, ids != nullptr, false, nullptr};
+    if (!q) ARG_FAIL(c, std::string(ask.entry) + ": null joint vectors");
+    const int rc = render_chunks(c, ask, q, PV, N, n_render, [] { return (const char *)nullptr; }, [&](int lo, int n, size_t px, const uint8_t *) -> int {
+        if (to_device) {                                      // in stream order: the next chunk's clearing comes after these copies
+            if (depth) HIP_TRY(c, hipMemcpyAsync(depth + (size_t)lo * px, c->d_rdepth, (size_t)n * px * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            if (ids) HIP_TRY(c, hipMemcpyAsync(ids + (size_t)lo * px, c->d_rids, (size_t)n * px, hipMemcpyDeviceToDevice, c->stream));
+            return ROPE_OK;
+        }
+        int rc = ROPE_OK;
+        if (depth) rc = copy_d2h_out(c, depth + (size_t)lo * px, c->d_rdepth, (size_t)n * px * sizeof(float));
+        if (!rc && ids) rc = copy_d2h_out(c, ids + (size_t)lo * px, c->d_rids, (size_t)n * px);
+        return rc;
+    });
+    if (!rc && to_device) HIP_TRY(c, hipStreamSynchronize(c->stream));      // the planes are the caller's, on any stream, when the call returns
+    return rc;
+}
 
 extern "C" int rope_render_batch(rope_ctx *c, const double *q, const double *PV, int N, int n_render, const int32_t *crop,
                                  float *depth, uint8_t *ids)
@@ -1548,96 +1510,23 @@ extern "C" int rope_render_masks(rope_ctx *c, const double *q, const double *PV,
 {
     if (!c) return ROPE_E_ARG;
     if (!q || !label_of_link || !masks) ARG_FAIL(c, "rope_render_masks: null pointer");
-    if (N < 1) ARG_FAIL(c, "rope_render_masks: need N >= 1");
-    if (!c->have_robot || !c->have_camera) ARG_FAIL(c, "rope_render_masks: robot and camera must be set first");
-    if (n_render < 1 || n_render > c->n_links) ARG_FAIL(c, "rope_render_masks: n_render out of range");
-    if (pad < 1 || pad > ROPE_MASK_MAX_PAD) ARG_FAIL(c, "rope_render_masks: pad must be 1..64");
     uint8_t lut[256] = {};                                      // link id -> label bits; background (255) and the rest -> none
-    for (int l = 0; l < n_render; l++) {
-        if (label_of_link[l] == 255) continue;
-        if (label_of_link[l] > 7) ARG_FAIL(c, "rope_render_masks: label bit must be 0..7 or 255");
-        lut[l] = (uint8_t)(1u << label_of_link[l]);
-    }
-    const FrameParams fp = c->fp;
-    for (size_t i = 0; i < 6 * (size_t)N; i++)
-        if (!std::isfinite(q[i]) || std::fabs(q[i]) > 1.0e4) ARG_FAIL(c, "rope_render_masks: joint angle not finite or |q| > 1e4 rad");
-    bool clip = use_clip(c);
-    if (PV) {
-        for (size_t i = 0; i < 16 * (size_t)N; i++)
-            if (!std::isfinite(PV[i])) ARG_FAIL(c, "rope_render_masks: non-finite view matrix");
-        clip = c->strategy & STRATEGY_CLIP_KERNELS;                // the call's cameras decide, not the context's
-        for (int i = 0; i < N && !clip; i++) clip = near_plane_in_reach(c, PV + 16 * (size_t)i);
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t px = (size_t)fp.W * (size_t)fp.H;
-    const int chunk = (int)std::min<size_t>({(size_t)N, (size_t)MAX_ROWS, std::max<size_t>(1, RENDER_BATCH_BUDGET / (2 * px))});
-    int rc = ensure_capacity(c, chunk);
-    if (rc) return rc;
-    if ((size_t)chunk * px > c->rids_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->rids_cap = 0;
-        HIP_TRY(c, realloc_dev(&c->d_rids, (size_t)chunk * px));
-        c->rids_cap = (size_t)chunk * px;
-    }
-    if ((size_t)chunk * px > c->rmask_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->rmask_cap = 0;
-        HIP_TRY(c, realloc_dev(&c->d_rmask, (size_t)chunk * px));
-        c->rmask_cap = (size_t)chunk * px;
-    }
-    if ((size_t)chunk * 32 > c->rboxes_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->rboxes_cap = 0;
-        HIP_TRY(c, realloc_dev(&c->d_rboxes, (size_t)chunk * 32));
-        c->rboxes_cap = (size_t)chunk * 32;
-    }
-    // one block up per chunk: joint vectors | view matrices | view index | the 256-byte id -> label table
-    const size_t off_pv = 6 * (size_t)chunk * sizeof(double), off_vo = off_pv + (PV ? 16 * (size_t)chunk * sizeof(double) : 0),
-                 off_lut = (off_vo + (PV ? (size_t)chunk * sizeof(int32_t) : 0) + 15) & ~(size_t)15, bytes = off_lut + sizeof(lut);
-    if (bytes > c->vstage_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->h_vstage) { (void)hipHostFree(c->h_vstage); c->h_vstage = nullptr; }
-        c->vstage_cap = 0;
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_vstage, bytes, hipHostMallocDefault));
-        HIP_TRY(c, realloc_dev(&c->d_vstage, bytes));
-        c->vstage_cap = bytes;
-    }
-    c->cand_valid = c->results_valid = false;
-    c->cand_dev = nullptr;
-    c->mvp_valid = false;
-    for (int lo = 0; lo < N; lo += chunk) {
-        const int n = std::min(chunk, N - lo);
-        HIP_TRY(c, hipStreamSynchronize(c->stream));         // the block may still feed the previous chunk
-        std::memcpy(c->h_vstage, q + 6 * (size_t)lo, 6 * (size_t)n * sizeof(double));
-        if (PV) {
-            std::memcpy(c->h_vstage + off_pv, PV + 16 * (size_t)lo, 16 * (size_t)n * sizeof(double));
-            int32_t *vo = reinterpret_cast<int32_t *>(c->h_vstage + off_vo);
-            for (int i = 0; i < n; i++) vo[i] = i;
+    auto own_checks = [&]() -> const char * {
+        if (pad < 1 || pad > ROPE_MASK_MAX_PAD) return "rope_render_masks: pad must be 1..64";
+        for (int l = 0; l < n_render; l++) {
+            if (label_of_link[l] == 255) continue;
+            if (label_of_link[l] > 7) return "rope_render_masks: label bit must be 0..7 or 255";
+            lut[l] = (uint8_t)(1u << label_of_link[l]);
         }
-        std::memcpy(c->h_vstage + off_lut, lut, sizeof(lut));
-        HIP_TRY(c, hipMemcpyAsync(c->d_vstage, c->h_vstage, bytes, hipMemcpyHostToDevice, c->stream));
-        c->dv_cand = reinterpret_cast<const double *>(c->d_vstage);
-        c->dv_PV = PV ? reinterpret_cast<const double *>(c->d_vstage + off_pv) : c->d_PV;
-        c->dv_view_of = PV ? reinterpret_cast<const int32_t *>(c->d_vstage + off_vo) : nullptr;
-        c->C = n;
-        c->n_layers = n;
-        rc = enqueue_geometry(c, n_render, 0, fp, true);
-        if (rc) return rc;
-        HIP_TRY(c, hipMemsetAsync(c->d_rids, 0xFF, (size_t)n * px, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_rboxes, 0xFF, (size_t)n * 32 * sizeof(int32_t), c->stream));
-        RasterArgs a = base_args(c, n_render);
-        a.depth_out = nullptr;
-        a.ids_out = c->d_rids;
-        HIP_TRY(c, launch_raster(MODE_DUMP, ROPE_LOSS_DEPTH, n, c->stream, fp, c->rp, a, clip));
-        HIP_TRY(c, launch_masks(c->stream, c->d_rids, n, fp.H, fp.W, reinterpret_cast<const uint8_t *>(c->d_vstage + off_lut), pad,
-                                c->d_rmask, c->d_rboxes));
-        rc = copy_d2h_out(c, masks + (size_t)lo * px, c->d_rmask, (size_t)n * px);
-        if (rc) return rc;
-        if (boxes) { rc = copy_d2h_out(c, boxes + (size_t)lo * 32, c->d_rboxes, (size_t)n * 32 * sizeof(int32_t)); if (rc) return rc; }
-    }
-    c->C = 0;
-    c->last_n_render = n_render;
-    return ROPE_OK;
+        return nullptr;
+    };
+    const RenderAsk ask{"rope_render_masks", nullptr, false, true, true, lut};
+    return render_chunks(c, ask, q, PV, N, n_render, own_checks, [&](int lo, int n, size_t px, const uint8_t *lut_dev) -> int {
+        HIP_TRY(c, launch_masks(c->stream, c->d_rids, n, c->fp.H, c->fp.W, lut_dev, pad, c->d_rmask, c->d_rboxes));
+        int rc = copy_d2h_out(c, masks + (size_t)lo * px, c->d_rmask, (size_t)n * px);
+        if (!rc && boxes) rc = copy_d2h_out(c, boxes + (size_t)lo * 32, c->d_rboxes, (size_t)n * 32 * sizeof(int32_t));
+        return rc;
+    });
 }
 
 extern "C" int rope_render(rope_ctx *c, const double *q, int n_render, float *depth, uint8_t *ids)
@@ -1673,20 +1562,10 @@ extern "C" int rope_lookup_build(rope_ctx *c, const double *cand, int C, int n_r
     HIP_TRY(c, hipSetDevice(c->device));
     c->table_C = 0;
     const size_t px = (size_t)(crop[1] - crop[0] + 1) * (size_t)(crop[3] - crop[2] + 1), need = px * (size_t)C;
-    if (need > c->table_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, realloc_dev(&c->d_table, need));
-        c->table_cap = need;
-    }
-    if (C > c->tscore_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->tscore_cap = 0;
-        HIP_TRY(c, realloc_dev(&c->d_tsums, (size_t)C * ROPE_SUM_WORDS));
-        HIP_TRY(c, realloc_dev(&c->d_terr, (size_t)C + 2));
-        c->tscore_cap = C;
-    }
+    if (int rc = sync_grow(c, c->d_table, need)) return rc;
+    if (int rc = sync_grow(c, c->d_tsums, (size_t)C * ROPE_SUM_WORDS, c->d_terr, (size_t)C + 2)) return rc;
     if (!c->d_zero_total) {
-        HIP_TRY(c, hipMalloc((void **)&c->d_zero_total, ROPE_SUM_WORDS * sizeof(uint64_t)));
+        HIP_TRY(c, c->d_zero_total.grow(ROPE_SUM_WORDS));
         HIP_TRY(c, hipMemsetAsync(c->d_zero_total, 0, ROPE_SUM_WORDS * sizeof(uint64_t), c->stream));
     }
     HIP_TRY(c, hipMemsetAsync(c->d_table, 0, need * sizeof(float), c->stream));
@@ -1716,27 +1595,23 @@ extern "C" int rope_lookup_build(rope_ctx *c, const double *cand, int C, int n_r
     }
     // keep of every row only the groups of samples that hold something (the crop is the box of all poses together, and a pose
     // fills a fraction of its own box), then let the dense rows go: this is what the per-frame pass reads
-    if ((size_t)C > c->trow_cap) {
-        c->trow_cap = 0;
-        HIP_TRY(c, realloc_dev(&c->d_tcount, (size_t)C));
-        HIP_TRY(c, realloc_dev(&c->d_toff, (size_t)C));
-        c->trow_cap = (size_t)C;
-    }
-    if (!c->d_tused) HIP_TRY(c, realloc_dev(&c->d_tused, (size_t)1));
-    if (!c->d_ttotal) HIP_TRY(c, realloc_dev(&c->d_ttotal, (size_t)ROPE_SUM_WORDS));
+    HIP_TRY(c, c->d_tcount.grow((size_t)C));
+    HIP_TRY(c, c->d_toff.grow((size_t)C));
+    HIP_TRY(c, c->d_tused.grow(1));
+    HIP_TRY(c, c->d_ttotal.grow(ROPE_SUM_WORDS));
     const int cw = crop[3] - crop[2] + 1, ch = crop[1] - crop[0] + 1;
     unsigned long long used = 0;
     hipError_t e = hipMemsetAsync(c->d_tused, 0, sizeof(unsigned long long), c->stream);
     if (e == hipSuccess) e = launch_table_count(c->stream, cw, ch, c->d_table, C, c->d_tcount, c->d_toff, c->d_tused);
     if (e == hipSuccess) e = hipMemcpyAsync(&used, c->d_tused, sizeof(used), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (c->d_tgoff) { (void)hipFree(c->d_tgoff); c->d_tgoff = nullptr; }
-    if (c->d_tgval) { (void)hipFree(c->d_tgval); c->d_tgval = nullptr; }
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_tgoff, std::max<size_t>(used, 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_tgval, std::max<size_t>(used, 1) * sizeof(float4));
+    c->d_tgoff.release();
+    c->d_tgval.release();
+    if (e == hipSuccess) e = static_cast<hipError_t>(c->d_tgoff.reset(std::max<size_t>(used, 1)));
+    if (e == hipSuccess) e = static_cast<hipError_t>(c->d_tgval.reset(std::max<size_t>(used, 1)));
     if (e == hipSuccess) e = launch_table_fill(c->stream, cw, ch, c->d_table, C, c->d_toff, c->d_tgoff, c->d_tgval);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_table); c->d_table = nullptr; c->table_cap = 0;
+    c->d_table.release();
     HIP_TRY(c, e);
     c->table_groups = used;
     c->table_C = C;
@@ -1754,12 +1629,7 @@ extern "C" int rope_lookup_score(rope_ctx *c, double *scores_out, int32_t *best_
     fp.r0 = c->table_crop[0]; fp.r1 = c->table_crop[1]; fp.c0 = c->table_crop[2]; fp.c1 = c->table_crop[3];
     const double n_pix = (double)(fp.r1 - fp.r0 + 1) * (double)(fp.c1 - fp.c0 + 1);
     const size_t words = table_crop_words(fp);
-    if (words > c->tc_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->tc_cap = 0;
-        HIP_TRY(c, realloc_dev(&c->d_tc, words));
-        c->tc_cap = words;
-    }
+    if (int rc = sync_grow(c, c->d_tc, words)) return rc;
     HIP_TRY(c, launch_table_score(c->stream, fp, c->d_tcount, c->d_toff, c->d_tgoff, c->d_tgval, c->table_C, c->d_t32, c->d_tc,
                                   c->d_ttotal, c->d_tsums));
     HIP_TRY(c, launch_finalize(c->stream, c->d_tsums, c->d_zero_total, c->table_C, ROPE_LOSS_LOOKUP, ROPE_MAX_LINKS, n_pix, c->lf, c->d_terr));
@@ -1784,23 +1654,23 @@ extern "C" int rope_set_frames(rope_ctx *c, int n_frames, const double *q, const
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const size_t plane = (size_t)c->fp.W * c->fp.H, n = plane * (size_t)n_frames;
     // buffers only ever grow: a predictor calls this once per run with the same shapes
-    if (n > c->frames_cap) { HIP_TRY(c, realloc_dev(&c->d_ftq, n)); c->frames_cap = n; }
+    HIP_TRY(c, c->d_ftq.grow(n));
     int rc = copy_h2d_staged(c, c->d_ftq, tq, n * sizeof(uint64_t));
     if (rc) return rc;
     c->frames_t32 = (t32 != nullptr);
     if (t32) {
-        if (n > c->frames_t32_cap) { HIP_TRY(c, realloc_dev(&c->d_ft32, n)); c->frames_t32_cap = n; }
+        HIP_TRY(c, c->d_ft32.grow(n));
         rc = copy_h2d_staged(c, c->d_ft32, t32, n * sizeof(float));
         if (rc) return rc;
     }
     c->frames_tl = (link_planes != nullptr);
     if (link_planes) {
-        if (n * ROPE_MAX_LINKS > c->frames_tl_cap) { HIP_TRY(c, realloc_dev(&c->d_ftl, n * ROPE_MAX_LINKS)); c->frames_tl_cap = n * ROPE_MAX_LINKS; }
+        HIP_TRY(c, c->d_ftl.grow(n * ROPE_MAX_LINKS));
         rc = copy_h2d_staged(c, c->d_ftl, link_planes, n * ROPE_MAX_LINKS * sizeof(uint64_t));
         if (rc) return rc;
     }
-    if (n_frames > c->ftotal_cap) { HIP_TRY(c, realloc_dev(&c->d_ftotal, 5 * (size_t)n_frames * ROPE_SUM_WORDS)); c->ftotal_cap = n_frames; }
-    if (!c->d_fempty) HIP_TRY(c, realloc_dev(&c->d_fempty, (size_t)MAX_MASK_WORDS * 32 * ROPE_SUM_WORDS));   // any tile count
+    HIP_TRY(c, c->d_ftotal.grow(5 * (size_t)n_frames * ROPE_SUM_WORDS));                  // per loss kind, a block for the frames allocated
+    HIP_TRY(c, c->d_fempty.grow((size_t)MAX_MASK_WORDS * 32 * ROPE_SUM_WORDS));           // any tile count
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->h_fq.assign(q, q + 6 * (size_t)n_frames);
     c->n_frames = n_frames;
@@ -1832,15 +1702,10 @@ extern "C" int rope_eval_views(rope_ctx *c, const double *PV, int K, int n_rende
     // i's planes) | the K view matrices | view index | frame index
     const size_t off_pv = 6 * (size_t)C * sizeof(double), off_vo = off_pv + 16 * (size_t)K * sizeof(double),
                  off_fo = off_vo + (size_t)C * sizeof(int32_t), bytes = off_fo + (size_t)C * sizeof(int32_t);
-    if (bytes > c->vstage_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->h_vstage) { (void)hipHostFree(c->h_vstage); c->h_vstage = nullptr; }
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_vstage, bytes, hipHostMallocDefault));
-        HIP_TRY(c, realloc_dev(&c->d_vstage, bytes));
-        c->vstage_cap = bytes;
-    }
+    rc = sync_grow(c, c->h_vstage, bytes, c->d_vstage, bytes);
+    if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // the block may still feed the previous call's copy
-    double *hc = reinterpret_cast<double *>(c->h_vstage);
+    double *hc = reinterpret_cast<double *>(c->h_vstage.get());
     int32_t *hvo = reinterpret_cast<int32_t *>(c->h_vstage + off_vo), *hfo = reinterpret_cast<int32_t *>(c->h_vstage + off_fo);
     for (int k = 0; k < K; k++)
         for (int i = 0; i < N; i++) {
@@ -1850,7 +1715,7 @@ extern "C" int rope_eval_views(rope_ctx *c, const double *PV, int K, int n_rende
         }
     std::memcpy(c->h_vstage + off_pv, PV, 16 * (size_t)K * sizeof(double));
     HIP_TRY(c, hipMemcpyAsync(c->d_vstage, c->h_vstage, bytes, hipMemcpyHostToDevice, c->stream));
-    c->dv_cand = reinterpret_cast<const double *>(c->d_vstage);
+    c->dv_cand = reinterpret_cast<const double *>(c->d_vstage.get());
     c->dv_PV = reinterpret_cast<const double *>(c->d_vstage + off_pv);
     c->dv_view_of = reinterpret_cast<const int32_t *>(c->d_vstage + off_vo);
     c->dv_frame_of = reinterpret_cast<const int32_t *>(c->d_vstage + off_fo);
@@ -1860,7 +1725,7 @@ extern "C" int rope_eval_views(rope_ctx *c, const double *PV, int K, int n_rende
     c->cand_dev = nullptr;
     c->n_layers = C;                                  // every (view, frame) candidate is its own layer: nothing shared
     const size_t plane = (size_t)c->fp.W * c->fp.H;
-    uint64_t *ftotal = c->d_ftotal + (size_t)loss * c->ftotal_cap * ROPE_SUM_WORDS;     // one block of totals per loss kind
+    uint64_t *ftotal = c->d_ftotal + (size_t)loss * (c->d_ftotal.cap() / 5);            // one block of totals per loss kind
     if (!c->ftotal_valid[loss]) {
         // sums of every frame with nothing rendered: the raster launch only adds what the render changes
         for (int i = 0; i < N; i++)
@@ -1872,11 +1737,7 @@ extern "C" int rope_eval_views(rope_ctx *c, const double *PV, int K, int n_rende
     rc = enqueue_eval(c, n_render, loss, c->fp, (double)plane, nullptr, EVAL_VIEWS);
     if (rc) return rc;
     const size_t n_sums = (size_t)C * ROPE_SUM_WORDS, n_tot = (size_t)N * ROPE_SUM_WORDS;
-    if (n_sums + n_tot > c->vsums_cap) {
-        if (c->h_vsums) { (void)hipHostFree(c->h_vsums); c->h_vsums = nullptr; }
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_vsums, (n_sums + n_tot) * sizeof(uint64_t), hipHostMallocDefault));
-        c->vsums_cap = n_sums + n_tot;
-    }
+    HIP_TRY(c, c->h_vsums.grow(n_sums + n_tot));
     HIP_TRY(c, hipMemcpyAsync(c->h_vsums, c->d_sums, n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->h_vsums + n_sums, ftotal, n_tot * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1896,15 +1757,10 @@ extern "C" int rope_eval_views(rope_ctx *c, const double *PV, int K, int n_rende
 // per-frame scratch of the batched prediction, sized for n_frames resident targets
 static int size_target_scratch(rope_ctx *c, int n_frames)
 {
-    if (n_frames > c->tg_total_cap) {
-        c->tg_total_cap = 0;
-        for (int k = 0; k < 4; k++) HIP_TRY(c, realloc_dev(&c->d_tg_total[k], (size_t)n_frames * ROPE_SUM_WORDS));
-        HIP_TRY(c, realloc_dev(&c->d_tg_ltotal, (size_t)n_frames * ROPE_SUM_WORDS));
-        c->tg_total_cap = n_frames;
-    }
-    const size_t empties = (size_t)n_frames * c->n_tiles * ROPE_SUM_WORDS;
-    if (empties > c->tg_empty_cap) { c->tg_empty_cap = 0; HIP_TRY(c, realloc_dev(&c->d_tg_empty, empties)); c->tg_empty_cap = empties; }
-    if (n_frames > c->tg_best_cap) { c->tg_best_cap = 0; HIP_TRY(c, realloc_dev(&c->d_tg_best, 2 * (size_t)n_frames)); c->tg_best_cap = n_frames; }
+    for (int k = 0; k < 4; k++) HIP_TRY(c, c->d_tg_total[k].grow((size_t)n_frames * ROPE_SUM_WORDS));
+    HIP_TRY(c, c->d_tg_ltotal.grow((size_t)n_frames * ROPE_SUM_WORDS));
+    HIP_TRY(c, c->d_tg_empty.grow((size_t)n_frames * c->n_tiles * ROPE_SUM_WORDS));
+    HIP_TRY(c, c->d_tg_best.grow(2 * (size_t)n_frames));
     return ROPE_OK;
 }
 
@@ -1919,20 +1775,20 @@ extern "C" int rope_set_targets(rope_ctx *c, int n_frames, const uint64_t *tq, c
     c->n_targets = 0;
     c->n_frames = 0;                              // d_ftq / d_ft32 are shared with the camera-pose path's frames
     const size_t plane = (size_t)c->fp.W * c->fp.H, n = plane * (size_t)n_frames;
-    if (n > c->frames_cap) { c->frames_cap = 0; HIP_TRY(c, realloc_dev(&c->d_ftq, n)); c->frames_cap = n; }
+    HIP_TRY(c, c->d_ftq.grow(n));
     int rc = copy_h2d_staged(c, c->d_ftq, tq, n * sizeof(uint64_t));
     if (rc) return rc;
     if (t32) {
-        if (n > c->frames_t32_cap) { c->frames_t32_cap = 0; HIP_TRY(c, realloc_dev(&c->d_ft32, n)); c->frames_t32_cap = n; }
+        HIP_TRY(c, c->d_ft32.grow(n));
         rc = copy_h2d_staged(c, c->d_ft32, t32, n * sizeof(float));
         if (rc) return rc;
     }
     if (t32_tsweep) {
-        if (n > c->fts_cap) { c->fts_cap = 0; HIP_TRY(c, realloc_dev(&c->d_fts32, n)); c->fts_cap = n; }
+        HIP_TRY(c, c->d_fts32.grow(n));
         rc = copy_h2d_staged(c, c->d_fts32, t32_tsweep, n * sizeof(float));
         if (rc) return rc;
     }
-    if (n_frames > c->fflags_cap) { c->fflags_cap = 0; HIP_TRY(c, realloc_dev(&c->d_fflags, (size_t)n_frames)); c->fflags_cap = n_frames; }
+    HIP_TRY(c, c->d_fflags.grow((size_t)n_frames));
     static_assert(sizeof(LinkFlags) == 8, "link flags travel as 8 bytes per frame");
     rc = copy_h2d_staged(c, c->d_fflags, link_flags, 8 * (size_t)n_frames);
     if (rc) return rc;
@@ -1945,6 +1801,17 @@ extern "C" int rope_set_targets(rope_ctx *c, int n_frames, const uint64_t *tq, c
     for (bool &v : c->ftotal_valid) v = false;
     c->n_targets = n_frames;
     return ROPE_OK;
+}
+
+// The staged planes for n_frames frames, every one tried: rope_stage_targets and the slot-filling calls may run beside an
+// evaluation on another thread, so nothing here waits on, or reports through, anything the evaluation calls use.
+static bool grow_staged(rope_ctx *c, int n_frames, bool t32, bool ts)
+{
+    const size_t n = (size_t)c->fp.W * c->fp.H * (size_t)n_frames;
+    bool ok = c->s_ftq.grow(n) == 0;
+    if (t32) ok = (c->s_ft32.grow(n) == 0) && ok;
+    if (ts) ok = (c->s_fts32.grow(n) == 0) && ok;
+    return (c->s_fflags.grow((size_t)n_frames) == 0) && ok;
 }
 
 // waits for everything rope_stage_targets_segmented enqueued on its callers' streams
@@ -1978,26 +1845,12 @@ extern "C" int rope_stage_targets(rope_ctx *c, int n_frames, const uint64_t *tq,
     c->staged_n = 0;
     const int W = c->fp.W, H = c->fp.H;
     const size_t plane = (size_t)W * H, n = plane * (size_t)n_frames;
-    bool ok = true;
-    auto grow = [&](auto **p, size_t &cap, size_t want) {
-        if (want <= cap) return;
-        cap = 0;
-        if (realloc_dev(p, want) != hipSuccess) { ok = false; return; }
-        cap = want;
-    };
-    grow(&c->s_ftq, c->s_frames_cap, n);
-    if (t32) grow(&c->s_ft32, c->s_t32_cap, n);
-    if (t32_tsweep) grow(&c->s_fts32, c->s_fts_cap, n);
-    if (n_frames > c->s_fflags_cap) {
-        c->s_fflags_cap = 0;
-        if (realloc_dev(&c->s_fflags, (size_t)n_frames) == hipSuccess) c->s_fflags_cap = n_frames; else ok = false;
-    }
-    if (!ok) { (void)hipGetLastError(); return fail(ROPE_E_NOMEM, "rope_stage_targets: out of device memory"); }
+    if (!grow_staged(c, n_frames, t32 != nullptr, t32_tsweep != nullptr)) { (void)hipGetLastError(); return fail(ROPE_E_NOMEM, "rope_stage_targets: out of device memory"); }
     // the few bytes of flags first: a small (or pageable) source goes through the pinned block, which waits for the stream
-    int rc = copy_h2d_on(c->copy_stream, &c->h_copy2, c->stage_err, c->s_fflags, link_flags, 8 * (size_t)n_frames);
-    if (!rc) rc = copy_h2d_on(c->copy_stream, &c->h_copy2, c->stage_err, c->s_ftq, tq, n * sizeof(uint64_t));
-    if (!rc && t32) rc = copy_h2d_on(c->copy_stream, &c->h_copy2, c->stage_err, c->s_ft32, t32, n * sizeof(float));
-    if (!rc && t32_tsweep) rc = copy_h2d_on(c->copy_stream, &c->h_copy2, c->stage_err, c->s_fts32, t32_tsweep, n * sizeof(float));
+    int rc = copy_h2d_on(c->copy_stream, c->h_copy2, c->stage_err, c->s_fflags, link_flags, 8 * (size_t)n_frames);
+    if (!rc) rc = copy_h2d_on(c->copy_stream, c->h_copy2, c->stage_err, c->s_ftq, tq, n * sizeof(uint64_t));
+    if (!rc && t32) rc = copy_h2d_on(c->copy_stream, c->h_copy2, c->stage_err, c->s_ft32, t32, n * sizeof(float));
+    if (!rc && t32_tsweep) rc = copy_h2d_on(c->copy_stream, c->h_copy2, c->stage_err, c->s_fts32, t32_tsweep, n * sizeof(float));
     if (rc) return rc;
     c->staged_t32 = (t32 != nullptr);
     c->staged_ts = (t32_tsweep != nullptr);
@@ -2021,26 +1874,10 @@ static int stage_slots_begin(rope_ctx *c, const char *who, int n_total, int slot
     c->seg_n_total = 0;                           // a new set: sized here, once
     if (c->copy_stream && hipStreamSynchronize(c->copy_stream) != hipSuccess) return fail(ROPE_E_HIP, ": the upload stream failed");
     if (drain_stage_events(c)) return fail(ROPE_E_HIP, ": a staging kernel failed");   // of a set left unfinished
-    const size_t n = (size_t)W * H * (size_t)n_total;
-    bool ok = true;
-    auto grow = [&](auto **p, size_t &cap, size_t want) {
-        if (want <= cap) return;
-        cap = 0;
-        if (realloc_dev(p, want) != hipSuccess) { ok = false; return; }
-        cap = want;
-    };
-    grow(&c->s_ftq, c->s_frames_cap, n);
-    grow(&c->s_ft32, c->s_t32_cap, n);
-    if (ts) grow(&c->s_fts32, c->s_fts_cap, n);
-    if (n_total > c->s_fflags_cap) {
-        c->s_fflags_cap = 0;
-        if (realloc_dev(&c->s_fflags, (size_t)n_total) == hipSuccess) c->s_fflags_cap = n_total; else ok = false;
+    if (!grow_staged(c, n_total, true, ts) || c->s_counts.grow((size_t)n_total * 2 * ROPE_MAX_LINKS) != 0) {
+        (void)hipGetLastError();
+        return fail(ROPE_E_NOMEM, ": out of device memory");
     }
-    if (n_total > c->s_counts_cap) {
-        c->s_counts_cap = 0;
-        if (realloc_dev(&c->s_counts, (size_t)n_total * 2 * ROPE_MAX_LINKS) == hipSuccess) c->s_counts_cap = n_total; else ok = false;
-    }
-    if (!ok) { (void)hipGetLastError(); return fail(ROPE_E_NOMEM, ": out of device memory"); }
     c->meta_used = 0;
     c->seg_filled.assign((size_t)n_total, 0);
     c->seg_n_filled = 0;
@@ -2092,16 +1929,15 @@ extern "C" int rope_stage_targets_segmented(rope_ctx *c, int n_total, int slot0,
     const size_t plane = (size_t)W * H;
     // this call's tables, appended: plane offsets | links present per frame | code per plane
     const size_t need = 2 * (size_t)n_frames + 1 + (size_t)K;
-    if (c->meta_used + need > c->meta_cap) {      // the kernels in flight read the old block: wait for them, then start a larger one
+    if (c->meta_used + need > c->d_meta.cap()) {  // the kernels in flight read the old block: wait for them, then start a larger one
         if (drain_stage_events(c)) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: a staging kernel failed");
-        const size_t cap = std::max<size_t>(std::max<size_t>(2 * c->meta_cap, need), 4096);
-        c->meta_cap = c->meta_used = 0;
-        if (c->h_meta) { (void)hipHostFree(c->h_meta); c->h_meta = nullptr; }
-        if (hipHostMalloc((void **)&c->h_meta, cap * sizeof(int32_t), hipHostMallocDefault) != hipSuccess || realloc_dev(&c->d_meta, cap) != hipSuccess) {
+        const size_t cap = std::max<size_t>(std::max<size_t>(2 * c->d_meta.cap(), need), 4096);
+        c->meta_used = 0;
+        c->d_meta.release();                      // the device block, allocated last, says how large the pair is
+        if (c->h_meta.reset(cap) || c->d_meta.reset(cap)) {
             (void)hipGetLastError();
             return fail(ROPE_E_NOMEM, "rope_stage_targets_segmented: out of memory");
         }
-        c->meta_cap = cap;
     }
     int32_t *m = c->h_meta + c->meta_used;
     for (int i = 0; i <= n_frames; i++) m[i] = inst_first[i];
@@ -2238,10 +2074,10 @@ extern "C" int rope_commit_targets(rope_ctx *c)
     c->staged_n = 0;
     c->n_targets = 0;
     c->n_frames = 0;                              // d_ftq / d_ft32 are shared with the camera-pose path's frames
-    std::swap(c->d_ftq, c->s_ftq);       std::swap(c->frames_cap, c->s_frames_cap);
-    if (c->staged_t32) { std::swap(c->d_ft32, c->s_ft32);   std::swap(c->frames_t32_cap, c->s_t32_cap); }
-    if (c->staged_ts)  { std::swap(c->d_fts32, c->s_fts32); std::swap(c->fts_cap, c->s_fts_cap); }
-    std::swap(c->d_fflags, c->s_fflags); std::swap(c->fflags_cap, c->s_fflags_cap);
+    c->d_ftq.swap(c->s_ftq);
+    if (c->staged_t32) c->d_ft32.swap(c->s_ft32);
+    if (c->staged_ts) c->d_fts32.swap(c->s_fts32);
+    c->d_fflags.swap(c->s_fflags);
     int rc = size_target_scratch(c, n_frames);
     if (rc) return rc;
     c->targets_t32 = c->staged_t32;
@@ -2298,7 +2134,7 @@ extern "C" int rope_eval_targets(rope_ctx *c, const double *cand, const int32_t 
         if (rc) return rc;
         if (!c->err_on_host) HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::memcpy(err_out + lo, c->err_on_host ? c->h_err : c->h_stage, (size_t)n * sizeof(double));
+        std::memcpy(err_out + lo, c->err_on_host ? c->h_err.get() : c->h_stage.get(), (size_t)n * sizeof(double));
     }
     return ROPE_OK;
 }
@@ -2313,13 +2149,8 @@ extern "C" int rope_lookup_score_targets(rope_ctx *c, int32_t *best_idx, double 
     FrameParams fp = c->fp;
     fp.r0 = c->table_crop[0]; fp.r1 = c->table_crop[1]; fp.c0 = c->table_crop[2]; fp.c1 = c->table_crop[3];
     const size_t crop_px = table_crop_words(fp), N = (size_t)c->n_targets;     // crop rows padded to whole groups of four samples
-    if (N * crop_px > c->tg_t32c_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->tg_t32c_cap = 0;
-        HIP_TRY(c, realloc_dev(&c->d_tg_t32c, N * crop_px));
-        c->tg_t32c_cap = N * crop_px;
-    }
-    if (N * c->table_C > c->tg_scores_cap) { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->tg_scores_cap = 0; HIP_TRY(c, realloc_dev(&c->d_tg_scores, N * c->table_C)); c->tg_scores_cap = N * c->table_C; }
+    if (int rc = sync_grow(c, c->d_tg_t32c, N * crop_px)) return rc;
+    if (int rc = sync_grow(c, c->d_tg_scores, N * c->table_C)) return rc;
     HIP_TRY(c, launch_table_score_frames(c->stream, fp, c->d_tcount, c->d_toff, c->d_tgoff, c->d_tgval, c->table_C, c->d_ft32, c->n_targets, c->d_tg_t32c, c->d_tg_ltotal,
                                          c->d_tg_scores, c->d_tg_best));
     std::vector<double> best(2 * N);
