@@ -82,17 +82,28 @@ def test_predictor_reproduces_golden_trace():
 @pytest.mark.gpu
 def test_engine_renders_equal_the_independent_exact_rasteriser():
     """The HIP engine against tests/golden/pins_raster_160x120.npz (an independent rasteriser in Python integers over the real mesh,
-    tests/golden/make_pins.py): same covered pixels, same link on every pixel."""
+    tests/golden/make_pins.py): same covered pixels, same link on every pixel, and the depth within the interval that the exact
+    24-bit depth +- B spans (B: the per-pixel bound of DESIGN.md §6 on a float32 depth plane, pins_bound_160x120.npz; the ends
+    go through Oracle.resolve, so nothing is inverted on the device's side)."""
     from rope_s3d_amd import engine as eng
-    pins = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'pins_raster_160x120.npz'))
+    golden = os.path.join(os.path.dirname(__file__), 'golden')
+    pins, bounds = np.load(os.path.join(golden, 'pins_raster_160x120.npz')), np.load(os.path.join(golden, 'pins_bound_160x120.npz'))
     rb = helpers.robot()
     intr, PV = helpers.camera('640_480_color', ds=4)
+    o = helpers.make_oracle(rb, intr, PV)
     e = eng.Engine(0)
     e.set_robot(rb)
     e.set_camera(PV, intr.width, intr.height, ZNEAR, ZFAR)
+    assert np.array_equal(bounds['poses'], pins['poses'])
     for k, q in enumerate(pins['poses']):
         depth, ids = e.render(q, 6)
         near = pins[f'near{k}']
         assert np.array_equal(ids != 255, pins[f'ids{k}'] != 255) and np.array_equal(ids[~near], pins[f'ids{k}'][~near]), k
         assert ((depth != 0) == (ids != 255)).all()
-
+        drawn = (ids != 255) & ~near
+        d24, B = pins[f'd24_{k}'].astype(np.int64), bounds[f'bound{k}'].astype(np.int64)
+        assert (B[drawn] >= 1).all()
+        ends = [o.resolve((np.clip(d24 + s * B, 0, (1 << 24) - 2).astype(np.uint32) << 8) | pins[f'ids{k}'])[0] for s in (-1, 1)]
+        assert (ends[0][drawn] <= ends[1][drawn]).all()                      # the metric depth grows with the window depth
+        inside = (depth >= ends[0]) & (depth <= ends[1])
+        assert inside[drawn].all(), f"pose {k}: {(~inside[drawn]).sum()} px outside the exact depth +- B"

@@ -259,6 +259,7 @@ def test_oracle_rasteriser_against_the_independent_exact_one():
     the top-left rule, exact barycentric depth).  The C oracle must cover exactly the same pixels, give every pixel the same link,
     and its 24-bit depth (a float32 plane, quantised) must sit within two units of the exact value."""
     pins = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'pins_raster_160x120.npz'))
+    bounds = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'pins_bound_160x120.npz'))
     rb = helpers.robot()
     intr, PV = helpers.camera('640_480_color', ds=4)
     o = helpers.make_oracle(rb, intr, PV)
@@ -271,6 +272,13 @@ def test_oracle_rasteriser_against_the_independent_exact_one():
         assert np.array_equal(ids[~near], want_ids[~near]), f"pose {k}: link ids differ"
         drawn = want_ids != 255
         assert np.abs((key >> 8).astype(np.int64) - want_d24.astype(np.int64))[drawn & ~near].max() <= 2
+        # the per-pixel bound B of DESIGN.md §6 (pins_bound_160x120.npz, written by the same run of make_pins.py) holds here too,
+        # with the ratio the synthetic scenes pin: tests/test_golden.py holds the engine's depth to the interval it spans
+        assert np.array_equal(bounds['poses'], pins['poses']) and bounds[f'bound{k}'].shape == want_ids.shape
+        B = bounds[f'bound{k}'].astype(np.int64)
+        assert (B[drawn] >= 1).all() and (B[~drawn] == 0).all(), "the bound file belongs to these pins"
+        err = np.abs((key >> 8).astype(np.int64) - want_d24.astype(np.int64))
+        assert (err[drawn] <= 0.3 * B[drawn]).all(), f"pose {k}: err / B up to {(err[drawn] / B[drawn]).max()}"
         # and the metric depth read-back of those keys is pyrender's formula on the quantised value
         depth, _ = o.resolve(key)
         d = want_d24[drawn].astype(np.float64) / (2 ** 24 - 1)
