@@ -498,6 +498,25 @@ int rope_seg_roi_align_backward(const float *grad_out, const float *boxes, const
                                 const int64_t *level_off, int n_boxes, int channels, int pool, float inv_level_unit, const float *t,
                                 float *grad_rows, void *stream);
 
+/* ---- Segmentation evaluation (rope_s3d_amd/evaluation.py, evaluate.py).  Same conventions as the rope_seg_* calls above: no
+ * context, plain device pointers, the HIP stream to launch on, ROPE_E_ARG for arguments it refuses.
+ *
+ * rope_seg_mask_overlaps: how far the instance planes of a detector overlap the ground-truth labels of their frames, as exact
+ * pixel counts (csrc/rope_eval.hip), by kernels enqueued on `stream` with no host synchronisation in the call.
+ *   pred_dev      K_total = inst_first[n_frames] planes H x W of bytes, non-zero = inside the instance (any non-zero value; a
+ *                 torch.bool tensor (K, H, W), as rope_stage_targets_segmented takes it), DEVICE; may be NULL when K_total == 0
+ *   inst_first    n_frames + 1 offsets into the planes: frame i owns planes inst_first[i] .. inst_first[i + 1] - 1, HOST
+ *   gt_bits_dev   n_frames planes H x W of bytes, bit b set where the pixel belongs to ground-truth label b (what
+ *                 rope_render_masks writes: up to 8 labels, which may overlap), DEVICE
+ *   inter_dev     K_total x 8 uint32 out: [k][b] = pixels where plane k is non-zero and bit b of its frame's plane is set
+ *   area_pred_dev K_total uint32 out: non-zero pixels of plane k;  area_gt_dev: n_frames x 8 uint32 out: pixels of frame i with bit b
+ * The outputs are DEVICE memory of the caller's and are written completely (the caller need not clear them); the counts are exact
+ * integers, the same from run to run.  n_frames == 0 and K_total == 0 succeed (area_gt_dev is filled all the same).  ROPE_E_ARG for
+ * a null pointer where planes exist, n_frames < 0, H < 1, W < 1, H W >= 2^32, or an inst_first that does not start at 0 or
+ * decreases; a refused call enqueues nothing. */
+int rope_seg_mask_overlaps(const uint8_t *pred_dev, const int32_t *inst_first, int n_frames, const uint8_t *gt_bits_dev, int H, int W,
+                           uint32_t *inter_dev, uint32_t *area_pred_dev, uint32_t *area_gt_dev, void *stream);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

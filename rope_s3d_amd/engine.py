@@ -22,7 +22,7 @@ ABI_SYMBOLS = (
     'rope_candidates_upload', 'rope_eval_resident', 'rope_sync', 'rope_results_download', 'rope_eval',
     'rope_lookup_build', 'rope_lookup_score', 'rope_render', 'rope_render_batch', 'rope_render_masks', 'rope_trace_contours', 'rope_coverage', 'rope_debug_mvp', 'rope_profile_eval', 'rope_set_strategy',
     'rope_set_frames', 'rope_eval_views', 'rope_predict', 'rope_set_robot_mesh', 'rope_partition_mesh', 'rope_pack_target', 'rope_downsample_even',
-    'rope_seg_nms', 'rope_seg_roi_align', 'rope_seg_bias_act',
+    'rope_seg_nms', 'rope_seg_roi_align', 'rope_seg_bias_act', 'rope_seg_mask_overlaps',
     'rope_seg_rpn_targets', 'rope_seg_roi_targets', 'rope_seg_roi_align_float', 'rope_seg_roi_align_backward',
     'rope_set_target_tsweep', 'rope_set_targets', 'rope_stage_targets', 'rope_commit_targets', 'rope_eval_targets', 'rope_lookup_score_targets', 'rope_predict_batch',
     'rope_prepare_synthetic', 'rope_host_alloc', 'rope_host_free', 'rope_build_id', 'rope_camera_matrix', 'rope_lookup_grid', 'rope_crop_divisions',
@@ -139,6 +139,7 @@ def load_library(path: str = None):
     lib.rope_seg_roi_align_float.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]
     lib.rope_seg_roi_align_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]
     lib.rope_seg_bias_act.argtypes = [vp, vp, vp, C.c_int64, i32, C.c_int64, i32, vp]
+    lib.rope_seg_mask_overlaps.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_eval_views.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.rope_set_target_tsweep.argtypes = [vp, vp]

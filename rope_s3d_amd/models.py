@@ -99,6 +99,20 @@ class ModelManager:
         self.update()
         return folder
 
+    def add_benchmark(self, id: str, record: dict) -> str:
+        """Append one evaluation (evaluation.benchmark_record: dataset, split, ground-truth source, frame count, AP figures,
+        per-class figures, date) to the model's `benchmarks` list and rewrite its data file; the file's other fields stay as they
+        are.  -> the file."""
+        assert id in self.info, f"id {id} not found"
+        path = os.path.join(self.info[id].folder, MODELDATA_FILE_NAME)
+        with open(path) as f:
+            md = json.load(f)
+        md['benchmarks'] = list(md.get('benchmarks') or []) + [dict(record)]
+        with open(path, 'w') as f:
+            json.dump(md, f, indent=4)
+        self.info[id].benchmarks = md['benchmarks']
+        return path
+
     def loadByID(self, id: str) -> str:
         """The last checkpoint (by name, i.e. by epoch) of a model (models.py:180-190)."""
         assert id in self.info, f"id {id} not found"
