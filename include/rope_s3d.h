@@ -517,6 +517,33 @@ int rope_seg_roi_align_backward(const float *grad_out, const float *boxes, const
 int rope_seg_mask_overlaps(const uint8_t *pred_dev, const int32_t *inst_first, int n_frames, const uint8_t *gt_bits_dev, int H, int W,
                            uint32_t *inter_dev, uint32_t *area_pred_dev, uint32_t *area_gt_dev, void *stream);
 
+/* ---- Dataset verification (rope_s3d_amd/data/verification.py, verify.py).  Same conventions: no context, plain device pointers,
+ * the HIP stream to launch on, nothing synchronised in the call.
+ *
+ * rope_frame_agreement: how far every recorded frame agrees with the render at its recorded pose (csrc/rope_verify.hip).  It
+ * replaces verification.py:58-67 and :222, where the reference renders each frame, blends the render over the photograph and leaves
+ * the judgement to a person: here the render's depth is compared with the recorded depth pixel by pixel, in integers.
+ *   render_depth_dev  n_frames planes H x W float32 metres: the renders (rope_render_batch_device), DEVICE, 4-byte aligned.  The
+ *                     depth of a rendered pixel is finite and in [0, 128) (the renderer's far plane is at 100 m); other values
+ *                     count as the nearer end of that range, NaN as 0
+ *   render_ids_dev    n_frames planes H x W of link ids, 255 = background, DEVICE, any alignment
+ *   frame_depth_dev   n_frames planes H x W float32 metres: the recorded depth maps, DEVICE, 4-byte aligned
+ *   n_links           1 .. ROPE_MAX_LINKS: ids below it are links
+ *   tol_m             finite, >= 0: how far apart two depths may lie and still agree
+ *   sums_dev          n_frames x ROPE_AGREE_WORDS uint64 out, DEVICE, 8-byte aligned; zeroed by the call itself
+ * With q(x) = floor(x 2^32), R, id, T a pixel of the three planes: T is VALID when finite and 0 < T < 128; the pixel is RENDERED when
+ * id < n_links; BOTH = rendered and valid; CLOSE = both and |q(R) - q(T)| <= q(tol_m); FRONT = both and q(T) < q(R) - q(tol_m)
+ * (something stands before the robot).  Per frame:
+ *   [0] valid pixels   [1] rendered pixels   [2] sum over both of |q(R) - q(T)|
+ *   [3] pixels with n_links <= id < 255 (counted nowhere else)   [4 + 4 l .. 7 + 4 l] link l: rendered, both, close, front
+ * All sums are exact integers, the same from run to run.  ROPE_E_ARG, with nothing enqueued, for n_frames < 1, H < 1, W < 1,
+ * H W > 2^24 (word 2 holds 2^39 a pixel), n_links outside 1 .. ROPE_MAX_LINKS, a tol_m that is negative or not finite, a null or
+ * misaligned pointer.  ROPE_E_HIP when the runtime refuses the memset or the launch (a grid of n_frames x up to 2 048 workgroups:
+ * far beyond any set that fits the device); sums_dev may then have been zeroed already. */
+#define ROPE_AGREE_WORDS 28
+int rope_frame_agreement(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames, int H,
+                         int W, int n_links, float tol_m, uint64_t *sums_dev, void *stream);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

@@ -5,3 +5,4 @@ from rope_s3d_amd import Dataset, Grapher, Intrinsics, Paths, Predictor, Rendere
 from rope_s3d_amd.prediction.feed import JSONCoupling, LiveCamera  # noqa: F401
 from rope_s3d_amd.simulation import DatasetRenderer  # noqa: F401
 from rope_s3d_amd.data.annotation import AutomaticAnnotator  # noqa: F401
+from rope_s3d_amd.data.verification import Verifier  # noqa: F401

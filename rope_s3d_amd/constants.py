@@ -46,3 +46,10 @@ LINK_BLUE = np.array([c[0] for c in DEFAULT_RENDER_COLORS], dtype=np.uint8)
 BACKGROUND_ID = 255
 VIDEO_FPS = 15      # default preview video frames per second (constants.py:58)
 JSON_LINK_FILE = r"\\marvin\ROPE\joint_states.json"      # where the controller drops its joint state (constants.py:16)
+
+# Verifier (constants.py:49-53,59); VERIFIER_SELECTED_GAMMA belongs to the click-through GUI, which is not here
+VERIFIER_ALPHA = .7               # weight of the photograph in an overlay; the render takes the rest
+VERIFIER_SCALER = 1.5             # overlay size over the thumbnail's: the frame is shown at VERIFIER_SCALER / THUMBNAIL_DS_FACTOR
+VERIFIER_ROWS = 4                 # overlays per contact sheet: rows x columns
+VERIFIER_COLUMNS = 4
+THUMBNAIL_DS_FACTOR = 6           # a dataset's preview images are the frames shrunk by this factor (building.py:183-185)

@@ -95,8 +95,9 @@ class Dataset:
 
 
 def write_dataset(name: str, og_img: np.ndarray, depthmaps: np.ndarray, angles: np.ndarray, camera_pose: np.ndarray,
-                  color_intrinsics: str, positions: np.ndarray = None, extra_attrs: dict = None) -> str:
-    """Write arrays in the layout `Dataset` reads.  depthmaps are float64 metres (building.py:172-179)."""
+                  color_intrinsics: str, positions: np.ndarray = None, extra_attrs: dict = None, preview: np.ndarray = None) -> str:
+    """Write arrays in the layout `Dataset` reads.  depthmaps are float64 metres (building.py:172-179).  preview: the thumbnails
+    (preview_img.npy), when the set has some."""
     d = dataset_dir(name)
     os.makedirs(d, exist_ok=True)
     n = len(og_img)
@@ -105,6 +106,8 @@ def write_dataset(name: str, og_img: np.ndarray, depthmaps: np.ndarray, angles: 
     np.save(os.path.join(d, 'angles.npy'), np.asarray(angles, np.float64))
     np.save(os.path.join(d, 'camera_pose.npy'), np.asarray(camera_pose, np.float64))
     np.save(os.path.join(d, 'positions.npy'), np.zeros((n, 6, 3)) if positions is None else np.asarray(positions, np.float64))
+    if preview is not None:
+        np.save(os.path.join(d, 'preview_img.npy'), np.asarray(preview, np.uint8))
     attrs = {'name': os.path.basename(os.path.normpath(d)), 'length': int(n),
              'resolution': [int(og_img.shape[1]), int(og_img.shape[2])], 'color_intrinsics': str(color_intrinsics)}
     attrs.update(extra_attrs or {})
@@ -249,7 +252,7 @@ def open_dataset(name: str, device: int = 0):
 
 
 def write_h5_dataset(name: str, og_img, depthmaps, angles, camera_pose, color_intrinsics: str, positions=None,
-                     extra_attrs: dict = None, compression_level: int = 4) -> str:
+                     extra_attrs: dict = None, compression_level: int = 4, preview=None) -> str:
     """The same arrays as one `<name>/<name>.h5` in the reference's layout (building.py:195-242): what the reference's
     own Dataset class opens.  Needs the HDF5 C library (data/hdf5.py)."""
     from . import hdf5
@@ -259,5 +262,5 @@ def write_h5_dataset(name: str, og_img, depthmaps, angles, camera_pose, color_in
     for k, v in (extra_attrs or {}).items():
         attrs[k] = json.dumps(v) if isinstance(v, dict) else (int(v) if isinstance(v, bool) else v)
     path = os.path.join(d, os.path.basename(os.path.normpath(d)) + '.h5')
-    return hdf5.write_h5_dataset(path, og_img, depthmaps, angles, camera_pose, color_intrinsics, positions, attrs=attrs,
+    return hdf5.write_h5_dataset(path, og_img, depthmaps, angles, camera_pose, color_intrinsics, positions, preview=preview, attrs=attrs,
                                  compression_level=compression_level)

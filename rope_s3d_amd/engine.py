@@ -14,6 +14,7 @@ from .robot import RobotModel
 
 LOSS_DEPTH, LOSS_FULL, LOSS_LOOKUP, LOSS_TSWEEP, LOSS_CAMFULL = 0, 1, 2, 3, 4
 SUM_WORDS = 23
+AGREE_WORDS = 28                 # ROPE_AGREE_WORDS (include/rope_s3d.h): the words rope_frame_agreement writes per frame
 Q32 = 4294967296.0
 TQ_MAX = (1 << 39) - 1
 
@@ -27,7 +28,7 @@ ABI_SYMBOLS = (
     'rope_set_target_tsweep', 'rope_set_targets', 'rope_stage_targets', 'rope_commit_targets', 'rope_eval_targets', 'rope_lookup_score_targets', 'rope_predict_batch',
     'rope_prepare_synthetic', 'rope_host_alloc', 'rope_host_free', 'rope_build_id', 'rope_camera_matrix', 'rope_lookup_grid', 'rope_crop_divisions',
     'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets',
-    'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes')
+    'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes', 'rope_frame_agreement')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -140,6 +141,7 @@ def load_library(path: str = None):
     lib.rope_seg_roi_align_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]
     lib.rope_seg_bias_act.argtypes = [vp, vp, vp, C.c_int64, i32, C.c_int64, i32, vp]
     lib.rope_seg_mask_overlaps.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
+    lib.rope_frame_agreement.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp]
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_eval_views.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.rope_set_target_tsweep.argtypes = [vp, vp]
@@ -502,6 +504,38 @@ class Engine:
         if rc:
             raise EngineError(f"rope_depth_holes failed ({rc}): N <= 65535 planes, dilations and connection_factor at most 32")
         return depth_t
+
+    def frame_agreement(self, render_depth, render_ids, frame_depth, n_links: int, tol: float) -> np.ndarray:
+        """rope_frame_agreement: N renders against the N recorded depth maps of their frames -> (N, 28) uint64, per frame
+        [0] valid pixels of the recording, [1] rendered pixels, [2] the sum of |q(R) - q(T)| (q = floor(x 2^32)) over the pixels both
+        rendered and valid, [3] pixels whose id is neither a link's nor the background's, [4 + 4 l ..] link l: rendered, both, close
+        (within tol metres), front (the recording nearer by more than tol).  render_depth / frame_depth (N, H, W) float32 and
+        render_ids (N, H, W) uint8 are torch tensors on this engine's device (render_batch_device's); the kernel runs on torch's
+        current stream and the sums are waited for here."""
+        import torch
+        for name, t, dt in (('render_depth', render_depth, torch.float32), ('render_ids', render_ids, torch.uint8),
+                            ('frame_depth', frame_depth, torch.float32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
+            if t.device.type != 'cuda' or t.device.index != self.device:
+                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
+            if t.shape != render_depth.shape:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {tuple(render_depth.shape)}")
+        N, H, W = render_depth.shape
+        if N == 0:
+            return np.zeros((0, AGREE_WORDS), np.uint64)
+        dev = render_depth.device
+        with torch.cuda.device(dev):
+            sums = torch.empty((N, AGREE_WORDS), dtype=torch.int64, device=dev)
+            rc = self._lib.rope_frame_agreement(C.c_void_p(render_depth.data_ptr()), C.c_void_p(render_ids.data_ptr()),
+                                                C.c_void_p(frame_depth.data_ptr()), int(N), int(H), int(W), int(n_links), float(tol),
+                                                C.c_void_p(sums.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if rc == -1:
+                raise ValueError(f"rope_frame_agreement refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), "
+                                 f"n_links {n_links} (1 .. 6), tol {tol} (finite, not negative)")
+            if rc:
+                raise EngineError(f"rope_frame_agreement failed ({rc})")
+            return sums.cpu().numpy().view(np.uint64)
 
     def debug_targets(self, want_tsweep: bool = False):
         """rope_debug_targets: the resident set back on the host -> (tq (N,H,W) uint64, t32 (N,H,W) float32, tsweep planes or None,

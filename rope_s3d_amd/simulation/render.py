@@ -155,11 +155,12 @@ class Renderer:
         angles = np.asarray(angles, dtype=np.float64).reshape(-1, 6)
         return self.engine.render_batch(angles, self._n_render, self._views(camera_poses, len(angles)), crop)
 
-    def render_ids_batch_device(self, angles):
-        """render_ids_batch under the renderer's own camera with the planes left on the GPU (rope_render_batch_device)
+    def render_ids_batch_device(self, angles, camera_poses=None):
+        """render_ids_batch of the whole frame with the planes left on the GPU (rope_render_batch_device), each pose under its own
+        camera pose (the renderer's when None)
         -> (depths float32 (N, H, W), link ids uint8 (N, H, W)) as torch tensors on the engine's device."""
         angles = np.asarray(angles, dtype=np.float64).reshape(-1, 6)
-        return self.engine.render_batch_device(angles, self._n_render)
+        return self.engine.render_batch_device(angles, self._n_render, self._views(camera_poses, len(angles)))
 
     @property
     def blue_of_id(self) -> np.ndarray:
