@@ -544,6 +544,60 @@ int rope_seg_mask_overlaps(const uint8_t *pred_dev, const int32_t *inst_first, i
 int rope_frame_agreement(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames, int H,
                          int W, int n_links, float tol_m, uint64_t *sums_dev, void *stream);
 
+/* ---- Conditioning of raw depth frames (rope_s3d_amd/prediction/conditioning.py, csrc/rope_feed.hip).  Same conventions: no context,
+ * plain device pointers, the HIP stream to launch on, nothing synchronised in the call, no state that the caller does not own.
+ * They stand in for what the reference's LiveCamera asks of pyrealsense2 for every frame (feed.py:32-99: decimation, spatial and
+ * temporal filters, rs.align to the colour stream).  The arithmetic below is this project's definition, restated from memory of
+ * librealsense's filters and not checked against them; tests/feed_ref.py is its plain reference.
+ * All depth planes are uint16 in raw sensor units, 0 = no data, (n_frames, h, w) contiguous, DEVICE.  One stack of planes holds
+ * at most 2^31 - 1 elements.  Every call returns ROPE_E_ARG, with nothing enqueued and nothing written, for a null pointer, a size
+ * below 1 or a parameter outside the range given; ROPE_E_HIP when the runtime refuses a launch.
+ *
+ * rope_depth_decimated_shape (host only): the shape rope_depth_decimate writes for H x W planes and k in 2 .. 8:
+ *   h = ((H / k) / 4) * 4, w = ((W / k) / 4) * 4 in integer division; ROPE_E_ARG when either is 0.
+ * rope_depth_decimate: out (n_frames, h, w); pixel (r, c) from the k x k patch at (r k, c k) of the frame, rows and columns beyond
+ *   h k and w k dropped.  With m non-zero values in the patch: k 2 or 3: the value at index (m - 1) / 2 of those values sorted
+ *   ascending (the lower median); k >= 4: floor(sum / m); 0 when m == 0.
+ *
+ * rope_depth_spatial, in place: `iterations` (1 .. 5) times a horizontal sweep of every row, then a vertical sweep of every column.
+ *   A sweep of a line x[0 .. L) is a forward pass i = 1 .. L - 1, then a backward pass i = L - 2 .. 0.  A pass takes a = x[previous i]
+ *   as already updated in this pass and b = x[i]; if a != 0, b != 0 and 1 <= |b - a| <= delta then
+ *   x[i] = (uint16)(float(b) * alpha + float(a) * (1.0f - alpha) + 0.5f), float32 with each of the five operations rounded on its
+ *   own, then truncated; otherwise x[i] stays.  Zeros are never written over and never start a chain; a line of length 1 is left
+ *   alone.  alpha float32 in (0, 1], delta 1 .. 65535, n_frames at most 65535.
+ *
+ * rope_depth_temporal, in place; the n_frames of a call are consecutive in time.  last_dev (uint16, h x w) and history_dev (uint8,
+ *   h x w) are the caller's state, zeroed by the caller to reset.  Per pixel and frame, c the incoming value and p = last:
+ *     c != 0, p != 0, |c - p| <= delta:  f = (uint16)(alpha * float(c) + (1.0f - alpha) * float(p) + 0.5f); the frame and last get f
+ *     c != 0 otherwise:                  last = c, the frame keeps c
+ *     c == 0:                            the frame gets p when p != 0 and the persistence rule holds on history as it stood before
+ *                                        this frame, else stays 0; last is unchanged
+ *   and in every case history = (history << 1) | (c != 0) afterwards (bit 0 = the newest frame).  The rule for persistence 0 .. 8
+ *   is a (need, window) pair: 0 never, 1 (8, 8), 2 (2, 3), 3 (2, 4), 4 (2, 8), 5 (1, 2), 6 (1, 5), 7 (1, 8), 8 always; it holds when
+ *   popcount(history & ((1 << window) - 1)) >= need.  One call with n frames gives what n calls with one frame each give, state
+ *   included.  alpha float32 in (0, 1], delta 1 .. 65535.
+ *
+ * rope_depth_align: depth planes (n_frames, h, w) seen from the colour sensor: out_dev (n_frames, Hc, Wc), 0 where nothing lands.
+ *   depth_intrin, color_intrin   {fx, fy, cx, cy}, 4 doubles each, HOST, no distortion terms
+ *   extrin                       row-major 3x3 R followed by t, 12 doubles, HOST: depth to colour, metres
+ *   scratch_dev                  n_frames x Hc x Wc uint32, DEVICE, 4-byte aligned; filled by the call itself
+ *   Every pixel (x, y) with z != 0 contributes; Z = double(z) * depth_scale.  Its corners (x - 0.5, y - 0.5) and (x + 0.5, y + 0.5)
+ *   each go, in double and in this order of operations, through  P = ((u - cx) / fx * Z, (v - cy) / fy * Z, Z);
+ *   P' = R P + t, each row as ((R0 X + R1 Y) + R2 Z) + t;  the pixel is skipped when either corner has Z' <= 0;
+ *   (u', v') = (X' / Z' * fx + cx, Y' / Z' * fy + cy) with the colour sensor's terms.  x0 = floor(u0' + 0.5), likewise y0, x1, y1, then
+ *   ordered; the pixel is skipped when any of the four lies outside the colour image or the footprint is larger than
+ *   ROPE_ALIGN_MAX_FOOTPRINT colour pixels either way (with sane sensors it is 3 x 3).  Every colour pixel of [x0 .. x1] x [y0 .. y1]
+ *   takes the minimum z of all its contributors: an integer atomic minimum on scratch_dev, narrowed to out_dev by a second pass, so
+ *   the result does not depend on the order of the atomics.  depth_scale finite and > 0, all terms finite, depth fx, fy non-zero. */
+#define ROPE_ALIGN_MAX_FOOTPRINT 16
+int rope_depth_decimated_shape(int H, int W, int k, int *h, int *w);
+int rope_depth_decimate(const uint16_t *raw_dev, int n_frames, int H, int W, int k, uint16_t *out_dev, void *stream);
+int rope_depth_spatial(uint16_t *planes_dev, int n_frames, int h, int w, float alpha, int delta, int iterations, void *stream);
+int rope_depth_temporal(uint16_t *planes_dev, int n_frames, int h, int w, float alpha, int delta, int persistence, uint16_t *last_dev,
+                        uint8_t *history_dev, void *stream);
+int rope_depth_align(const uint16_t *planes_dev, int n_frames, int h, int w, const double *depth_intrin, const double *color_intrin,
+                     const double *extrin, double depth_scale, int Hc, int Wc, uint32_t *scratch_dev, uint16_t *out_dev, void *stream);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

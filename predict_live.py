@@ -7,6 +7,7 @@ Claims and predictions are saved to live_preds.npy as (2, n, 6) after every fram
 
     python predict_live.py                       # RealSense + the controller's JSON file (needs both)
     python predict_live.py -replay <dataset>     # a recorded Dataset as camera, its angles as the controller's claims
+    python predict_live.py -raw <folder>         # a capture of raw sensor frames, conditioned on the GPU (feed.RawRecordingCamera)
 
 No windows are opened (cv2.imshow in the reference): the state is printed when it changes."""
 import argparse
@@ -16,7 +17,7 @@ import numpy as np
 
 from robotpose import Dataset, Intrinsics, Predictor
 from rope_s3d_amd.prediction.analysis import JointDistance
-from rope_s3d_amd.prediction.feed import DatasetCamera, JSONCoupling, LiveCamera
+from rope_s3d_amd.prediction.feed import DatasetCamera, JSONCoupling, LiveCamera, RawRecordingCamera
 
 LENGTH = 3
 ALLOWED_DEVIANCE = 0.1
@@ -95,6 +96,7 @@ class Live:
 if __name__ == "__main__":
     parser = argparse.ArgumentParser()
     parser.add_argument('-replay', type=str, default=None, help="replay this recorded dataset instead of a live camera")
+    parser.add_argument('-raw', type=str, default=None, help="replay this folder of raw depth + colour frames (sensor.json beside them)")
     parser.add_argument('-dataset', type=str, default='set91', help="parent dataset: camera pose (and segmentation model) come from it")
     parser.add_argument('-intrin', type=str, default='1280_720_color')
     parser.add_argument('-angs', type=str, default='SLU')
@@ -106,6 +108,9 @@ if __name__ == "__main__":
         cam = DatasetCamera(ds)
         kw = {'color_dict': ds.attrs['color_dict']} if ds.attrs.get('synthetic') else {}
         a = Live(str(ds.intrinsics), ds, args.angs, args.ds_factor, camera=cam, link=cam.claims(), **kw)
+    elif args.raw:
+        cam = RawRecordingCamera(args.raw)
+        a = Live(args.intrin, args.dataset, args.angs, args.ds_factor, camera=cam, link=cam.claims() if cam.angles is not None else None)
     else:
         a = Live(args.intrin, args.dataset, args.angs, args.ds_factor)
     n = a.run(args.frames)

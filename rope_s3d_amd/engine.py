@@ -28,7 +28,8 @@ ABI_SYMBOLS = (
     'rope_set_target_tsweep', 'rope_set_targets', 'rope_stage_targets', 'rope_commit_targets', 'rope_eval_targets', 'rope_lookup_score_targets', 'rope_predict_batch',
     'rope_prepare_synthetic', 'rope_host_alloc', 'rope_host_free', 'rope_build_id', 'rope_camera_matrix', 'rope_lookup_grid', 'rope_crop_divisions',
     'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets',
-    'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes', 'rope_frame_agreement')
+    'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes', 'rope_frame_agreement',
+    'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -142,6 +143,11 @@ def load_library(path: str = None):
     lib.rope_seg_bias_act.argtypes = [vp, vp, vp, C.c_int64, i32, C.c_int64, i32, vp]
     lib.rope_seg_mask_overlaps.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
     lib.rope_frame_agreement.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp]
+    lib.rope_depth_decimated_shape.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+    lib.rope_depth_decimate.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.rope_depth_spatial.argtypes = [vp, i32, i32, i32, C.c_float, i32, i32, vp]
+    lib.rope_depth_temporal.argtypes = [vp, i32, i32, i32, C.c_float, i32, i32, vp, vp, vp]
+    lib.rope_depth_align.argtypes = [vp, i32, i32, i32, vp, vp, vp, dbl, i32, i32, vp, vp, vp]
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_eval_views.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.rope_set_target_tsweep.argtypes = [vp, vp]
