@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Mask R-CNN training annotations of a dataset from renders at its recorded poses (same command line as the reference's
-annotate.py).  `dataset` may be a 'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' name."""
+annotate.py).  `dataset` may be a 'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' or 'photo:...' name."""
 import argparse
 
 from robotpose import AutomaticAnnotator, DatasetRenderer

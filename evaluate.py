@@ -2,7 +2,7 @@
 """Evaluate a trained segmentation model on a dataset: mask IoU per class and average precision (AP50, AP75, AP 0.50:0.95)
 against ground truth from the dataset's annotations (what train.py trained on) or from renders at the recorded poses.  The model
 is the one Predictor(model_ds=dataset) would load, or -model ID.  The result is printed and appended to the model's
-ModelData.json (`benchmarks`).  `dataset` may be a 'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' name."""
+ModelData.json (`benchmarks`).  `dataset` may be a 'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' or 'photo:...' name."""
 import argparse
 import logging
 import os

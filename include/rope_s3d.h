@@ -598,6 +598,60 @@ int rope_depth_temporal(uint16_t *planes_dev, int n_frames, int h, int w, float 
 int rope_depth_align(const uint16_t *planes_dev, int n_frames, int h, int w, const double *depth_intrin, const double *color_intrin,
                      const double *extrin, double depth_scale, int Hc, int Wc, uint32_t *scratch_dev, uint16_t *out_dev, void *stream);
 
+/* ---- Photo-like synthetic frames (rope_s3d_amd/simulation/shading.py, csrc/rope_shade.hip).  Same conventions: no context, plain
+ * device pointers, the HIP stream to launch on, nothing synchronised, allocated or copied in the call.  This is the project's own
+ * picture of the robot, not the reference's (pyrender's shader): one directional light, a Lambert surface whose normals come from
+ * the rendered depth, a colour per link, a background and sensor noise.  tests/shade_ref.py restates the text below in numpy.
+ *
+ * rope_shade_frames: N renders to N pictures.
+ *   depth_dev, ids_dev   N planes H x W: float32 metres (4-byte aligned) and link ids, as rope_render_batch_device writes them, DEVICE
+ *   n_links              1 .. ROPE_MAX_LINKS: a pixel is ROBOT iff id < n_links; 255 and every other id are background
+ *   fx, fy, cx, cy       the camera's terms as float32
+ *   params               N records, HOST (they travel as kernel arguments); light is the direction the light TRAVELS in camera axes
+ *                        (x right, y down, z forward), of unit length as the host rounded it: the kernel does not renormalise
+ *   bg_dev               n_bg planes H x W x 3 bytes, DEVICE, any alignment; may be NULL when every bg_index is -1
+ *   frame0, seed         as in rope_depth_holes: plane m draws the noise of frame frame0 + m of the 64-bit seed
+ *   bgr_dev              N planes H x W x 3 bytes out, DEVICE, any alignment
+ *   depth_out_dev        NULL, or N planes H x W float32 out (4-byte aligned): depth where the pixel is robot, bg_depth elsewhere.
+ *                        It may be depth_dev itself.
+ * Everything below is float32 with ONE correctly rounded IEEE operation per written operation (no fused multiply-add; / and sqrt
+ * are the correctly rounded ones), in the order written; z = depth[y][x], id = ids[y][x], rec = params[m].
+ *   1. P(x, y) = (kx(x) * z, ky(y) * z, z) with kx(x) = ((float)x - cx) / fx and ky(y) = ((float)y - cy) / fy.
+ *   2. dX = P(x + 1, y) - P(x, y) if x + 1 < W and ids[y][x + 1] == id; else P(x, y) - P(x - 1, y) if x > 0 and ids[y][x - 1] == id;
+ *      else (0, 0, 0).  dY likewise along y (y + 1 first).  Differences never cross an id boundary or the image edge.
+ *   3. n = dX x dY: n.x = dX.y * dY.z - dX.z * dY.y, n.y = dX.z * dY.x - dX.x * dY.z, n.z = dX.x * dY.y - dX.y * dY.x (each a product
+ *      minus a product).  nn = (n.x * n.x + n.y * n.y) + n.z * n.z;  dot = (n.x * L.x + n.y * L.y) + n.z * L.z.
+ *      lam = 1 if nn == 0, else (dot > 0 ? dot : 0) / sqrt(nn).  dX x dY points away from the camera and so does L, so a surface that
+ *      faces a head-on light has dot > 0.  A NaN depth in the neighbourhood makes nn NaN, which is not == 0: lam is then NaN, and
+ *      the pixel comes out 0 in step 5 (this is why the test is nn == 0 and not nn > 0).
+ *   4. s = ambient + (1 - ambient) * lam;  shade = s > 1 ? 1 : s  (a NaN stays).
+ *   5. channel c (0 blue, 1 green, 2 red) of a robot pixel: v = rint(((float)albedo[id][c] * shade) * gain[c]), ties to even.
+ *   6. of a background pixel: v = (float)bg_dev[bg_index][y][x][c], or (float)bg_colour[c] when bg_index is -1.
+ *   7. noise: with noise_q == 0 it is 0 and nothing is drawn.  Otherwise the four words of Philox4x32-10 with rope_depth_holes' key
+ *      (seed low 32, seed high 32) and counter (y W + x, frame0 + m, 0, 1) — the last word keeps this stream apart from the holes' —
+ *      and for channel c, with b0..b3 the bytes of word c:  noise = ((b0 + b1 + b2 + b3 - 510) * noise_q) >> 10, an arithmetic shift
+ *      of a 32-bit integer (floor).
+ *   8. t = v + (float)noise;  byte = t > 0 ? (t < 255 ? t : 255) : 0, so a NaN gives 0; t is a whole number, the conversion exact.
+ * ROPE_E_ARG, with nothing enqueued, for N < 0, a null depth_dev, ids_dev, bgr_dev or params where N > 0, H or W < 1, H W >= 2^31,
+ * n_bg < 0, n_links outside 1 .. ROPE_MAX_LINKS, a noise_q outside 0 .. ROPE_SHADE_MAX_NOISE_Q, a bg_index outside -1 .. n_bg - 1 or
+ * one >= 0 with bg_dev NULL, a depth_dev or depth_out_dev that is not 4-byte aligned.  N == 0 succeeds.  ROPE_E_HIP when the runtime
+ * refuses a launch. */
+#define ROPE_SHADE_MAX_NOISE_Q 1023
+typedef struct rope_shade_params {
+    float light[3];                         /* L */
+    float ambient;
+    float gain[3];
+    float bg_depth;                         /* metres; 0 = leave the background empty */
+    int32_t noise_q;                        /* 0 .. ROPE_SHADE_MAX_NOISE_Q; the noise spans -+ (510 noise_q) >> 10 levels */
+    int32_t bg_index;                       /* -1 = bg_colour */
+    uint8_t albedo[ROPE_MAX_LINKS][3];      /* BGR per link; rows from n_links on are not read */
+    uint8_t bg_colour[3];
+    uint8_t reserved[3];                    /* to 64 bytes */
+} rope_shade_params;
+int rope_shade_frames(const float *depth_dev, const uint8_t *ids_dev, int N, int H, int W, int n_links, float fx, float fy, float cx, float cy,
+                      const rope_shade_params *params, const uint8_t *bg_dev, int n_bg, uint32_t frame0, uint64_t seed, uint8_t *bgr_dev,
+                      float *depth_out_dev, void *stream);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

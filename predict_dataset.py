@@ -41,7 +41,7 @@ def run(args):
     import time
     t_begin = time.perf_counter()
     from rope_s3d_amd.data.dataset import open_dataset
-    ds = open_dataset(args.dataset, gpu)                 # a stored set, or 'synthetic:<frames>[:<seed>[:<preset>]]' rendered as it is read
+    ds = open_dataset(args.dataset, gpu)                 # a stored set, or 'synthetic:...' / 'photo:<frames>[:<seed>[:<preset>]]' made as it is read
     kwargs = {}
     if getattr(args, 'segmenter', None) == 'maskrcnn':
         # BASELINE configs[2]: the segmentation stage on PyTorch-ROCm in front of the engine (predict.py:94-98,416).

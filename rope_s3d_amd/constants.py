@@ -53,3 +53,16 @@ VERIFIER_SCALER = 1.5             # overlay size over the thumbnail's: the frame
 VERIFIER_ROWS = 4                 # overlays per contact sheet: rows x columns
 VERIFIER_COLUMNS = 4
 THUMBNAIL_DS_FACTOR = 6           # a dataset's preview images are the frames shrunk by this factor (building.py:183-185)
+
+# Photo-like synthetic frames (simulation/shading.py: draw_params, make_backgrounds).  These ranges are this project's choice: the
+# reference has no such stage, and nothing here was fitted to a real camera.
+SHADE_AMBIENT = .12                                 # shade_depth's level, and default_params'
+SHADE_ALBEDO = 200                                  # shade_depth's grey
+SHADE_LIGHT_CONE_DEG = 50.0                         # the light travels within this angle of the view axis
+SHADE_AMBIENT_RANGE = (.10, .35)
+SHADE_PALETTE = ((160, 90, 30), (128, 128, 128), (235, 235, 235), (30, 110, 240))      # BGR: industrial blue, grey, white, orange
+SHADE_ALBEDO_JITTER = 18                            # levels either way, per channel
+SHADE_GAIN_RANGE = (.85, 1.15)                      # per channel: white balance
+SHADE_NOISE_Q_RANGE = (0, 48)                       # noise spans -+ (510 q) >> 10 levels: up to 23
+SHADE_BG_DEPTH_RANGE = (3.0, 6.0)                   # metres: behind the robot's workspace as DEFAULT_CAMERA_POSE sees it
+SHADE_N_BACKGROUNDS = 8                             # pictures a PhotoDataset draws its backgrounds from

@@ -206,7 +206,7 @@ class SyntheticDataset:
 
     @classmethod
     def parse_name(cls, name: str):
-        """'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' -> (frames, seed, preset), the defaults filled in."""
+        """'<prefix><frames>[:<seed>[:<intrinsics preset>]]' -> (frames, seed, preset), the defaults filled in."""
         parts = name[len(cls.PREFIX):].split(':')
         return int(parts[0]), int(parts[1]) if len(parts) > 1 else 7919, parts[2] if len(parts) > 2 else '640_480_color'
 
@@ -244,10 +244,72 @@ class SyntheticDataset:
         return self.length
 
 
+class PhotoDataset(SyntheticDataset):
+    """The poses of the 'synthetic:' set of the same seed as photographs (Renderer.render_photo_batch_device, csrc/rope_shade.hip):
+    og_img is the robot lit from a drawn direction, painted per link, over a procedural background with sensor noise; depthmaps is
+    the render's depth with a plane behind the robot.  Frame f's record is shading.draw_params(seed, [f]) and its noise carries f,
+    so a frame is the same bytes however it is read: frame(i), frames(a, b), another instance.  holes=True also punches the depth
+    holes of rope_depth_holes (frame f's, of the same seed) before the frames come down.  The frames say nothing about which pixel
+    is which link ('synthetic': False, no color_dict): they go through a segmenter, as a camera's do.
+    Name form: 'photo:<frames>[:<seed>[:<intrinsics preset>]]'."""
+
+    PREFIX = 'photo:'
+
+    def __init__(self, n_frames: int, base_intrin: str = '640_480_color', camera_pose=None, do_angles: str = 'SLU', seed: int = 7919,
+                 device: int = 0, holes: bool = False, n_backgrounds: int = None):
+        from ..constants import SHADE_N_BACKGROUNDS
+        super().__init__(n_frames, base_intrin, camera_pose, do_angles, seed, device)
+        self.seed, self.holes = int(seed), bool(holes)
+        self.n_backgrounds = SHADE_N_BACKGROUNDS if n_backgrounds is None else int(n_backgrounds)
+        self._bg = None                                 # the pictures, on the device from the first frame on
+        self.attrs = {k: v for k, v in self.attrs.items() if k != 'color_dict'}
+        self.attrs.update(synthetic=False, rendered=True)
+
+    def _photo(self, a: int, b: int):
+        import torch
+        from ..simulation.shading import draw_params, make_backgrounds
+        if self._bg is None and self.n_backgrounds > 0:
+            H, W = self._r.resolution
+            self._bg = torch.from_numpy(make_backgrounds(self.seed, self.n_backgrounds, H, W)).to(torch.device('cuda', self._r.engine.device))
+        params = draw_params(self.seed, np.arange(a, b), self._r.n_render, self.n_backgrounds)
+        bgr, depth, _ = self._r.render_photo_batch_device(self.angles[a:b], None, params, self._bg, frame0=a, seed=self.seed)
+        if self.holes:
+            self._r.engine.depth_holes(depth, self.seed, frame0=a)
+        return bgr.cpu().numpy(), depth.cpu().numpy()
+
+    def frame(self, i: int):
+        with self._lock:
+            if self._last[0] != i:
+                bgr, depth = self._photo(i, i + 1)
+                self._last = (i, (bgr[0], depth[0]))
+            return self._last[1]
+
+    def frames(self, a: int, b: int):
+        """-> (photographs uint8 (b-a, H, W, 3), depths float32 (b-a, H, W)) of frames a..b-1, made in one batch and kept."""
+        with self._lock:
+            if self._block[0] != (a, b):
+                self._block = ((a, b), self._photo(a, b))
+            return self._block[1]
+
+
+RENDERED_SETS = (SyntheticDataset, PhotoDataset)
+
+
+def rendered_set_of(name):
+    """The class whose frames a name like 'synthetic:...' or 'photo:...' asks for, None for a stored set's name."""
+    if isinstance(name, str):
+        for cls in RENDERED_SETS:
+            if name.startswith(cls.PREFIX):
+                return cls
+    return None
+
+
 def open_dataset(name: str, device: int = 0):
-    """Dataset(name), or the frames of a 'synthetic:<frames>[:<seed>[:<preset>]]' name rendered on the fly."""
-    if isinstance(name, str) and name.startswith(SyntheticDataset.PREFIX):
-        return SyntheticDataset.from_name(name, device)
+    """Dataset(name), or the frames of a 'synthetic:<frames>[:<seed>[:<preset>]]' or 'photo:<frames>[:<seed>[:<preset>]]' name made
+    on the fly."""
+    cls = rendered_set_of(name)
+    if cls is not None:
+        return cls.from_name(name, device)
     return Dataset(name)
 
 

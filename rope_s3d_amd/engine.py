@@ -15,6 +15,10 @@ from .robot import RobotModel
 LOSS_DEPTH, LOSS_FULL, LOSS_LOOKUP, LOSS_TSWEEP, LOSS_CAMFULL = 0, 1, 2, 3, 4
 SUM_WORDS = 23
 AGREE_WORDS = 28                 # ROPE_AGREE_WORDS (include/rope_s3d.h): the words rope_frame_agreement writes per frame
+SHADE_MAX_NOISE_Q = 1023         # ROPE_SHADE_MAX_NOISE_Q
+# rope_shade_params (include/rope_s3d.h), 64 bytes a record
+SHADE_DTYPE = np.dtype([('light', '<f4', 3), ('ambient', '<f4'), ('gain', '<f4', 3), ('bg_depth', '<f4'), ('noise_q', '<i4'), ('bg_index', '<i4'),
+                        ('albedo', 'u1', (6, 3)), ('bg_colour', 'u1', 3), ('reserved', 'u1', 3)])
 Q32 = 4294967296.0
 TQ_MAX = (1 << 39) - 1
 
@@ -29,7 +33,8 @@ ABI_SYMBOLS = (
     'rope_prepare_synthetic', 'rope_host_alloc', 'rope_host_free', 'rope_build_id', 'rope_camera_matrix', 'rope_lookup_grid', 'rope_crop_divisions',
     'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets',
     'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes', 'rope_frame_agreement',
-    'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align')
+    'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align',
+    'rope_shade_frames')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -148,6 +153,8 @@ def load_library(path: str = None):
     lib.rope_depth_spatial.argtypes = [vp, i32, i32, i32, C.c_float, i32, i32, vp]
     lib.rope_depth_temporal.argtypes = [vp, i32, i32, i32, C.c_float, i32, i32, vp, vp, vp]
     lib.rope_depth_align.argtypes = [vp, i32, i32, i32, vp, vp, vp, dbl, i32, i32, vp, vp, vp]
+    lib.rope_shade_frames.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, i32, C.c_uint32,
+                                      C.c_uint64, vp, vp, vp]
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_eval_views.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.rope_set_target_tsweep.argtypes = [vp, vp]
@@ -510,6 +517,56 @@ class Engine:
         if rc:
             raise EngineError(f"rope_depth_holes failed ({rc}): N <= 65535 planes, dilations and connection_factor at most 32")
         return depth_t
+
+    def shade_frames(self, depth_t, ids_t, params, intr, n_links: int, backgrounds=None, frame0: int = 0, seed: int = 0, depth_out=True,
+                     out=None):
+        """rope_shade_frames: the N renders depth_t (N, H, W) float32 / ids_t (N, H, W) uint8 (render_batch_device's, on this engine's
+        device) lit, painted, laid over their backgrounds and given sensor noise, by kernels on torch's current stream; nothing is
+        waited for.  params: N records of SHADE_DTYPE (simulation/shading.py makes them); intr: (fx, fy, cx, cy); backgrounds:
+        (n_bg, H, W, 3) uint8 on the device, or None when every bg_index is -1.  Plane m draws the noise of frame frame0 + m of the
+        64-bit seed.  depth_out: True = a new tensor, False = none, or the tensor to write (depth_t itself is allowed).  out: the
+        (N, H, W, 3) uint8 tensor to write the pictures to (any alignment), a new one when None.
+        -> (bgr (N, H, W, 3) uint8, depth with bg_depth behind the robot (N, H, W) float32 or None).
+        The arithmetic is the contract of include/rope_s3d.h; tests/shade_ref.py restates it in numpy."""
+        import torch
+        dev = depth_t.device
+        for name, t, dt in (('depth', depth_t, torch.float32), ('ids', ids_t, torch.uint8)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous() or t.shape != depth_t.shape:
+                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
+            if t.device.type != 'cuda' or t.device.index != self.device:
+                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
+        N, H, W = depth_t.shape
+        params = np.ascontiguousarray(params, SHADE_DTYPE).reshape(-1)
+        if len(params) != N:
+            raise ValueError(f"{len(params)} parameter records for {N} frames")
+        n_bg = 0
+        if backgrounds is not None:
+            if backgrounds.dtype != torch.uint8 or backgrounds.device != dev or not backgrounds.is_contiguous() or \
+                    tuple(backgrounds.shape[1:]) != (H, W, 3):
+                raise ValueError(f"backgrounds: a contiguous (n_bg, {H}, {W}, 3) uint8 tensor on {dev}")
+            n_bg = int(backgrounds.shape[0])
+        fx, fy, cx, cy = (float(v) for v in intr)
+        with torch.cuda.device(dev):
+            bgr = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
+            if bgr.dtype != torch.uint8 or tuple(bgr.shape) != (N, H, W, 3) or not bgr.is_contiguous() or bgr.device != dev:
+                raise ValueError(f"out: a contiguous ({N}, {H}, {W}, 3) uint8 tensor on {dev}")
+            if depth_out is True:
+                depth_out = torch.empty_like(depth_t)
+            elif depth_out is False:
+                depth_out = None
+            elif depth_out.dtype != torch.float32 or depth_out.shape != depth_t.shape or not depth_out.is_contiguous() or depth_out.device != dev:
+                raise ValueError("depth_out: a contiguous float32 tensor of the depth planes' shape, on their device")
+            rc = self._lib.rope_shade_frames(C.c_void_p(depth_t.data_ptr()), C.c_void_p(ids_t.data_ptr()), int(N), int(H), int(W), int(n_links),
+                                             fx, fy, cx, cy, _p(params), C.c_void_p(backgrounds.data_ptr()) if n_bg else None, n_bg,
+                                             int(frame0) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(bgr.data_ptr()),
+                                             C.c_void_p(depth_out.data_ptr()) if depth_out is not None else None,
+                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc == -1:
+            raise ValueError(f"rope_shade_frames refused its arguments: {N} frames of {H} x {W}, n_links {n_links} (1 .. 6), noise_q in "
+                             f"0 .. {SHADE_MAX_NOISE_Q}, bg_index in -1 .. {n_bg - 1}")
+        if rc:
+            raise EngineError(f"rope_shade_frames failed ({rc})")
+        return bgr, depth_out
 
     def frame_agreement(self, render_depth, render_ids, frame_depth, n_links: int, tol: float) -> np.ndarray:
         """rope_frame_agreement: N renders against the N recorded depth maps of their frames -> (N, 28) uint64, per frame

@@ -84,10 +84,11 @@ class ModelManager:
                     break
         folder = os.path.join(self.dir, name)
         os.makedirs(folder)
-        from .data.dataset import Dataset, SyntheticDataset
-        if dataset.startswith(SyntheticDataset.PREFIX):          # nothing rendered: the name holds the frame count
-            length = SyntheticDataset.parse_name(dataset)[0]
-            anno = SyntheticDataset.link_anno_path_of(dataset)
+        from .data.dataset import Dataset, rendered_set_of
+        rendered = rendered_set_of(dataset)
+        if rendered is not None:                                 # 'synthetic:' / 'photo:': nothing rendered, the name holds the frame count
+            length = rendered.parse_name(dataset)[0]
+            anno = rendered.link_anno_path_of(dataset)
         else:
             ds = Dataset(dataset)
             length, anno = ds.length, ds.link_anno_path

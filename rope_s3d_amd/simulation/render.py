@@ -162,6 +162,30 @@ class Renderer:
         angles = np.asarray(angles, dtype=np.float64).reshape(-1, 6)
         return self.engine.render_batch_device(angles, self._n_render, self._views(camera_poses, len(angles)))
 
+    def render_photo_batch_device(self, angles, camera_poses=None, params=None, backgrounds=None, frame0: int = 0, seed: int = 0):
+        """N poses as photographs, made on the GPU: render_ids_batch_device followed by rope_shade_frames (csrc/rope_shade.hip) —
+        the surface lit by one directional light with normals from the rendered depth, a colour per link, a background picture or
+        colour, sensor noise, and a depth map with a plane behind the robot.  params: N records (simulation/shading.py:
+        default_params when None, which is shade_depth's scene); backgrounds: (n_bg, H, W, 3) uint8, a torch tensor on the engine's
+        device or a numpy array (uploaded here), None when every record's bg_index is -1.  Plane m takes the noise of frame
+        frame0 + m of `seed`.  Mode 'real', render and render_batch are not touched by this.
+        -> (bgr uint8 (N, H, W, 3), depth float32 (N, H, W), ids uint8 (N, H, W)) torch tensors on the engine's device."""
+        import torch
+        from .shading import default_params
+        depth, ids = self.render_ids_batch_device(angles, camera_poses)
+        if params is None:
+            params = default_params(len(depth), self._n_render)
+        if backgrounds is not None and not isinstance(backgrounds, torch.Tensor):
+            backgrounds = torch.from_numpy(np.ascontiguousarray(backgrounds, np.uint8)).to(depth.device)
+        intr = self.intrinsics
+        bgr, depth = self.engine.shade_frames(depth, ids, params, (intr.fx, intr.fy, intr.cx, intr.cy), self._n_render, backgrounds, frame0,
+                                              seed, depth_out=depth)
+        return bgr, depth, ids
+
+    def render_photo_batch(self, angles, camera_poses=None, params=None, backgrounds=None, frame0: int = 0, seed: int = 0):
+        """render_photo_batch_device with the three stacks copied down -> numpy (bgr, depth, ids)."""
+        return tuple(t.cpu().numpy() for t in self.render_photo_batch_device(angles, camera_poses, params, backgrounds, frame0, seed))
+
     @property
     def blue_of_id(self) -> np.ndarray:
         """Channel 0 of the colour every link id is drawn in (256 bytes, the background's included): render()'s colour image has
@@ -206,7 +230,7 @@ class Renderer:
 
 class DatasetRenderer(Renderer):
     """Renders a dataset's frames at their recorded joint angles and camera poses (render.py:167-187).  `dataset` is a name
-    (open_dataset: 'synthetic:...' names too) or an opened Dataset / SyntheticDataset.  render_range / render_indices draw many
+    (open_dataset: 'synthetic:...' and 'photo:...' names too) or an opened Dataset / SyntheticDataset.  render_range / render_indices draw many
     frames in one batch, each under its own camera pose."""
 
     def __init__(self, dataset, mode: str = 'seg', camera_pose: np.ndarray = None):

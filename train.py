@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Train the segmentation network on a dataset's annotated renders (same command line as the reference's train.py, plus
 -epochs and -base).  The annotations and their train / test split come from annotate.py.  `dataset` may be a
-'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' name.  Checkpoints go to a new model folder (ModelManager.allocateNew),
+'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' or 'photo:...' name.  Checkpoints go to a new model folder (ModelManager.allocateNew),
 where Predictor(model_ds=dataset) finds them."""
 import argparse
 import logging

@@ -2,7 +2,7 @@
 """Check a dataset's frames against their recorded poses: every frame's depth map against the render at its joint angles and
 camera pose, on the GPU (the reference's Verifier shows the same comparison as pictures and leaves the decision to a person).
 Prints the agreement table's summary and the frames whose pose is to be questioned; -sheets writes their overlays as contact
-sheets, -remove writes the set without them.  `dataset` may be a 'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' name."""
+sheets, -remove writes the set without them.  `dataset` may be a 'synthetic:<frames>[:<seed>[:<intrinsics preset>]]' or 'photo:...' name."""
 import argparse
 import json
 
@@ -12,7 +12,7 @@ from robotpose import Verifier
 
 
 def verify(args):
-    if args.remove and args.dataset.startswith('synthetic:'):
+    if args.remove and args.dataset.startswith(('synthetic:', 'photo:')):
         raise SystemExit("-remove: a synthetic set is rendered as it is read and stored nowhere, so there is nothing to rewrite")
     ver = Verifier(args.dataset, batch=args.batch, tol=args.tol)
     table = ver.run()
