@@ -1,195 +1,15 @@
-// rope_abi.hip — host side of librope_hip.so: context, HBM buffers, launch sequencing.
+// rope_abi.hip — host side of librope_hip.so: the context's life cycle, robot, camera, single target, candidates, launch sequencing
+// (enqueue_*), results, render, coverage, the stored table and the debug entries.  The context itself: rope_ctx.h; the sets of
+// targets and the camera-pose frames: rope_abi_targets.hip; the entries that are plain CPU code: rope_hostprep.cpp.
 // Declarations and the reference call sites each entry point replaces: include/rope_s3d.h.
-#include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "rope_buffers.h"
-#include "rope_kernels.h"
-
-using namespace rope;
-
-// Every buffer the context owns is a DevBuf / PinnedBuf member (rope_buffers.h): the pointer and its size travel together, and
-// what is not released earlier goes with the context.  Plain pointers below own nothing.
-struct rope_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-
-    // robot
-    bool have_robot = false;
-    RobotParams rp{};
-    DevBuf<uint32_t> d_header, d_tris;
-    DevBuf<float> d_verts, d_aabb;
-    DevBuf<double> d_joint_fixed, d_joint_axes;
-    int n_links = 0, n_meshlets = 0;
-    double reach = 0.0;                     // no point of any link, at any joint angles, is farther than this from the base frame's origin
-    double h_PV[16] = {};                   // host copy of the camera matrix (the near-plane test below)
-    bool clip_views = false;                // rope_eval_views: one of the call's cameras is close enough for near-plane clipping
-
-    // camera
-    bool have_camera = false;
-    FrameParams fp{};
-    DevBuf<double> d_PV;
-    int n_tiles = 0;
-
-    // target
-    bool have_target = false;
-    DevBuf<uint64_t> d_tq;
-    DevBuf<float> d_t32;
-    bool have_t32 = false;
-    LinkFlags lf{};
-    uint64_t target_version = 0;
-    // per loss: empty-tile sums and their frame total, valid for (target_version, crop)
-    DevBuf<uint64_t> d_empty[4], d_total[4];
-    uint64_t empty_version[4] = {0, 0, 0, 0};
-    int empty_crop[4][4] = {};
-
-    // candidates + results: one group of per-candidate buffers, all sized for `cap` rows by ensure_capacity
-    int C = 0, cap = 0;
-    DevBuf<double> d_cand, d_err, d_best_err;
-    PinnedBuf<double> h_stage;             // pinned staging: candidates up, errors + best down
-    // small batches: the finalize kernel writes errors + best straight into mapped pinned host memory (no copy command)
-    static constexpr int HOST_ERR_ROWS = 256;
-    // lockstep batches (rope_eval_targets): a step's rows — 2 to 26 per frame, hundreds of frames — go up, and their errors come
-    // back, through mapped host memory as well: a pass reads every row once and writes every error once, and the three copy
-    // commands it would otherwise queue (rows, frame indices, errors: 20-30 us of stream time each between 100 us of kernels)
-    // were a fifth of the device's time in a lockstep run
-    static constexpr int TARGET_HOST_ROWS = 16384;
-    PinnedBuf<double> h_err{true};         // mapped: the device writes through dev()
-    // small batches: the candidates stay in mapped host memory and the FK kernel reads them from there — no copy command
-    // in front of the first launch of a latency-bound chain
-    PinnedBuf<double> h_cand{true};
-    const double *cand_dev = nullptr;      // where the resident candidates are: d_cand or h_cand.dev()
-    bool err_on_host = false;
-    // rope_eval_views / rope_lookup_score reuse C and the per-candidate buffers for rows of their own: after them the
-    // resident candidates (and the results of the last eval) are gone until rope_candidates_upload / the next eval
-    bool cand_valid = false, results_valid = false;
-    DevBuf<float> d_mvp;
-    DevBuf<short4> d_bounds;
-    DevBuf<uint32_t> d_mask_lo, d_mask_hi;
-    int mask_words = 0;
-    // shared upstream layers: candidates with bit-identical (q0, q1) have identical links 0..2
-    int n_layers = 0;
-    DevBuf<int32_t> d_layer_of, d_layer_rep;
-    DevBuf<uint32_t> d_layers;             // keys
-    DevBuf<uint64_t> d_layer_sums;
-    // second level of sharing: layers with bit-identical q0 have identical links 0..1 ("parents")
-    int n_parents = 0;
-    DevBuf<int32_t> d_parent_of, d_parent_rep;   // layer -> parent; parent -> representative candidate
-    DevBuf<uint32_t> d_parents;
-    DevBuf<uint64_t> d_sums;
-    DevBuf<int32_t> d_best_idx;
-    int last_n_render = 0;
-
-    // small batches: per-candidate tiles in global memory that split workgroups merge into
-    DevBuf<int> d_touched;                 // MODE_SPLIT_GEO: per (candidate, tile) the number of the pass that last drew into it
-    int pass_id = 0;
-    bool mvp_valid = false;                // d_mvp holds the resident candidates' matrices (not after a pass that kept them in LDS)
-    DevBuf<uint32_t> d_gtile;
-    bool gtile_dirty = true;
-    // MODE_SPLIT: busy workgroups aimed at per launch (one generation: 2 per CU), fewest / most per (tile, candidate), and the
-    // workgroups per launch of the scoring pass that follows.  Measured at 160x90, 640x360 and 640x480 (tools/r02_split_tune.sh).
-    int split_target = 512, split_min = 8, split_min_many = 3, split_cap = 64, score_target = 6144;
-    int geo_rows = 48;                     // most rows of a small batch whose raster workgroups do their own forward kinematics and boxes
-    int layer_min_wg = 64;                 // fewest busy workgroups of a shared-layer launch for it to pay in a small batch (layers_pay)
-    int strategy = 0;                          // STRATEGY_* bits (rope_set_strategy): launch structure only, never a result
-    // large batches: queue of the (candidate, tile) pairs with something to draw, worked off by a grid that just fills the chip
-    DevBuf<uint32_t> d_qitems, d_tile_tris, d_tile_tris_lo;
-    size_t q_segment = 0;
-    bool q_weighted = false;
-    DevBuf<int> d_qctr;                        // [0] pairs queued, [1] next pair to hand out; cleared by fk_mvp_kernel
-    int n_cu = 256;
-
-    // stored lookup table (cropped sqrt-depth of a pose grid)
-    DevBuf<float> d_table;                     // dense rows while a table is built (released once it is packed)
-    // the stored table (rope_lookup_build): per row d_tcount groups of four samples from d_toff on — d_tgoff: where in the crop,
-    // d_tgval: the four values
-    DevBuf<uint32_t> d_tcount, d_tgoff;
-    DevBuf<unsigned long long> d_toff, d_tused;
-    DevBuf<float4> d_tgval;
-    DevBuf<uint64_t> d_ttotal;
-    DevBuf<float> d_tc;                     // rope_lookup_score: the cropped target, rows padded to whole groups (table_crop_words)
-    int table_C = 0, table_crop[4] = {0, 0, 0, 0};
-    size_t table_groups = 0;                   // groups the stored table holds
-    DevBuf<uint64_t> d_zero_total;
-    // scores of the table's rows: buffers of their own (a grid may hold more rows than one candidate batch)
-    DevBuf<uint64_t> d_tsums;
-    DevBuf<double> d_terr;
-
-    // camera-pose path: frames (joint vector + target planes each) scored under candidate views
-    int n_frames = 0;
-    bool frames_t32 = false, frames_tl = false;
-    std::vector<double> h_fq;               // n_frames x 6
-    DevBuf<uint64_t> d_ftq, d_ftl, d_ftotal, d_fempty;
-    DevBuf<float> d_ft32;
-    // one pinned host block and its device twin per rope_eval_views call: candidates | view matrices | view index | frame index
-    PinnedBuf<unsigned char> h_vstage;
-    DevBuf<unsigned char> d_vstage;
-    const double *dv_cand = nullptr, *dv_PV = nullptr;                  // into d_vstage (dv_PV: or d_PV)
-    const int32_t *dv_view_of = nullptr, *dv_frame_of = nullptr;
-    PinnedBuf<uint64_t> h_vsums;            // K x N x 23 sums, then N x 23 totals
-    PinnedBuf<unsigned char> h_copy;        // staging of pageable host buffers on their way up (copy_h2d_staged)
-    bool ftotal_valid[5] = {false, false, false, false, false};   // per loss kind: d_ftotal[loss] holds the frames' "nothing rendered" totals
-
-    // batched prediction (rope_set_targets / rope_eval_targets / rope_lookup_score_targets): the targets of n_targets frames.  The
-    // packed planes and the lookup planes live in d_ftq / d_ft32, which the camera-pose path's frames use as well: setting one
-    // kind unsets the other.
-    int n_targets = 0;
-    bool targets_t32 = false, targets_ts = false;
-    DevBuf<float> d_fts32;                  // TensorSweep planes (the whole target depth as float32), when given
-    DevBuf<LinkFlags> d_fflags;             // per frame
-    DevBuf<uint64_t> d_tg_total[4];         // per loss: n_targets x SUM_WORDS "nothing rendered" totals
-    DevBuf<uint64_t> d_tg_empty;            // scratch: n_targets x n_tiles x SUM_WORDS
-    bool tg_total_valid[4] = {false, false, false, false};
-    // rope_stage_targets / rope_commit_targets: the NEXT set of targets, uploaded on a stream of its own while the resident set is
-    // in use; committing swaps the two sets of planes
-    hipStream_t copy_stream = nullptr;
-    PinnedBuf<unsigned char> h_copy2;       // pinned block for pageable sources on the upload stream
-    DevBuf<uint64_t> s_ftq;
-    DevBuf<float> s_ft32, s_fts32;
-    DevBuf<LinkFlags> s_fflags;
-    int staged_n = 0, staged_W = 0, staged_H = 0;
-    std::string stage_err;                  // rope_stage_targets may run beside an evaluation: its own message
-    bool staged_t32 = false, staged_ts = false;
-    // rope_stage_targets_segmented: the staged set filled slot by slot by kernels on the CALLER's streams.  One event per call,
-    // which rope_commit_targets waits for; the calls' small tables (plane offsets, link codes) go up through a page-locked block
-    // that is only ever appended to while a set is being filled, so no call waits for the one before it.
-    std::vector<hipEvent_t> stage_events;
-    DevBuf<unsigned long long> s_counts;      // per staged frame: n_mask, n_depth per link
-    PinnedBuf<int32_t> h_meta;
-    DevBuf<int32_t> d_meta;                   // as large as h_meta
-    size_t meta_used = 0;                     // int32 words
-    std::vector<uint8_t> seg_filled;          // per slot of the set being filled
-    int seg_n_total = 0, seg_n_filled = 0;    // seg_n_total 0: no set is being filled
-    bool seg_ts = false;
-    int tg_crop[4][4] = {};
-    DevBuf<int32_t> d_frame_of;               // rows' frame indices: device copy / mapped host memory (small batches)
-    PinnedBuf<int32_t> h_frame_of{true};
-    const int32_t *frame_of_dev = nullptr;    // d_frame_of or h_frame_of.dev()
-    // the stored lookup table against all targets
-    DevBuf<float> d_tg_t32c;
-    DevBuf<uint64_t> d_tg_ltotal;
-    DevBuf<double> d_tg_scores, d_tg_best;
-    // single target: the float32 plane ROPE_LOSS_TSWEEP reads when it is not the lookup plane (rope_set_target_tsweep)
-    DevBuf<float> d_t32ts;
-    bool have_t32ts = false;
-
-    // rope_coverage's plane
-    DevBuf<uint8_t> d_cover;
-    // the chunked render path (render_chunks): the output planes of one chunk of poses — depth and ids for rope_render_batch, ids,
-    // label planes and boxes for rope_render_masks
-    DevBuf<float> d_rdepth;
-    DevBuf<uint8_t> d_rids, d_rmask;
-    DevBuf<int32_t> d_rboxes;
-};
+#include "rope_ctx.h"
 
 // ---- roctx ranges (the reference times its stages with utils.Timer / FancyTimer, robotpose/utils.py:122-180).
 // Named ranges around the phases of a pass and around every stage of the stage machine show up in `rocprofv3 --marker-trace`;
@@ -214,27 +34,8 @@ struct Roctx {
 Roctx &roctx() { static Roctx r; return r; }
 }  // namespace
 
-void rope_range_push(const char *name) { if (roctx().push) (void)roctx().push(name); }      // also used by rope_predict.cpp (per stage)
+void rope_range_push(const char *name) { if (roctx().push) (void)roctx().push(name); }
 void rope_range_pop() { if (roctx().pop) (void)roctx().pop(); }
-struct RopeRange {
-    explicit RopeRange(const char *name) { rope_range_push(name); }
-    ~RopeRange() { rope_range_pop(); }
-};
-
-#define HIP_TRY(ctx, expr)                                                                     \
-    do {                                                                                       \
-        hipError_t e_ = static_cast<hipError_t>(expr);                                                              \
-        if (e_ != hipSuccess) {                                                                \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                    \
-            return ROPE_E_HIP;                                                                 \
-        }                                                                                      \
-    } while (0)
-
-#define ARG_FAIL(ctx, msg)      \
-    do {                        \
-        (ctx)->err = (msg);     \
-        return ROPE_E_ARG;      \
-    } while (0)
 
 // what rope_buffers.h allocates with
 int rope_dev_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
@@ -249,26 +50,7 @@ int rope_pinned_alloc(void **p, size_t bytes, void **dev_alias)
     return e;
 }
 
-// Grow-or-keep for buffers that work in flight on the context's stream may still use: (buffer, elements) pairs; when one of
-// them is too small the stream is waited for, once, and every one is grown.  Nothing happens, and nothing is waited for, otherwise.
-static bool any_short() { return false; }
-template <typename B, typename... R> static bool any_short(const B &b, size_t n, const R &...r) { return n > b.cap() || any_short(r...); }
-static int grow_each() { return 0; }
-template <typename B, typename... R> static int grow_each(B &b, size_t n, R &...r) { const int e = b.grow(n); return e ? e : grow_each(r...); }
-template <typename... A> static int sync_grow(rope_ctx *c, A &&...a)
-{
-    if (!any_short(a...)) return ROPE_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, grow_each(a...));
-    return ROPE_OK;
-}
-
 static thread_local std::string g_create_err;
-
-// Host buffers handed over the C ABI are pageable; the runtime's own path for those is slow (measured 0.35 GB/s for
-// freshly written numpy arrays).  Go through a pinned block instead: memcpy + asynchronous copy, chunk by chunk.
-static int copy_h2d_staged(rope_ctx *c, void *dst, const void *src, size_t bytes);
-static int copy_d2h_staged(rope_ctx *c, void *dst, const void *src, size_t bytes);   // returns with the data in dst
 
 extern "C" int rope_create(rope_ctx **out, int device)
 {
@@ -326,9 +108,7 @@ extern "C" void rope_host_free(void *p)
     if (p) (void)hipHostFree(p);
 }
 
-// `stream` / `block` / `err`: the context's own stream, pinned block and message by default; rope_stage_targets, which may run beside
-// an evaluation on another thread, passes the upload stream and a block and a message of its own
-static int copy_h2d_on(hipStream_t stream, PinnedBuf<unsigned char> &block, std::string &err, void *dst, const void *src, size_t bytes)
+int copy_h2d_on(hipStream_t stream, PinnedBuf<unsigned char> &block, std::string &err, void *dst, const void *src, size_t bytes)
 {
     constexpr size_t CHUNK = 8u << 20;
     auto failed = [&](hipError_t e, const char *what) { if (e != hipSuccess) err = std::string(what) + ": " + hipGetErrorString(e); return e != hipSuccess; };
@@ -347,12 +127,12 @@ static int copy_h2d_on(hipStream_t stream, PinnedBuf<unsigned char> &block, std:
     return ROPE_OK;
 }
 
-static int copy_h2d_staged(rope_ctx *c, void *dst, const void *src, size_t bytes)
+int copy_h2d_staged(rope_ctx *c, void *dst, const void *src, size_t bytes)
 {
     return copy_h2d_on(c->stream, c->h_copy, c->err, dst, src, bytes);
 }
 
-static int copy_d2h_staged(rope_ctx *c, void *dst, const void *src, size_t bytes)
+int copy_d2h_staged(rope_ctx *c, void *dst, const void *src, size_t bytes)
 {
     constexpr size_t CHUNK = 8u << 20;
     HIP_TRY(c, c->h_copy.grow(2 * CHUNK));
@@ -495,23 +275,15 @@ extern "C" int rope_set_camera(rope_ctx *c, const double *PV, int W, int H, doub
         // a failed allocation below must not leave old-sized (or freed) buffers behind a camera that looks usable:
         // the context has no camera, no target and no frames until this call has gone through
         c->have_camera = false;
-        c->have_target = false;
-        c->have_t32ts = false;
-        c->n_frames = 0;
-        c->n_targets = 0;
-        c->staged_n = 0;                          // a staged set of the old size is not committed
+        c->single.n = c->resident.n = 0;
+        c->single.has_ts = false;
+        c->staged.n = 0;                          // a staged set of the old size is not committed
         c->C = 0;
         c->cand_valid = c->results_valid = false;
-        const size_t n = (size_t)W * H;
-        HIP_TRY(c, c->d_tq.reset(n));
-        HIP_TRY(c, c->d_t32.reset(n));
-        HIP_TRY(c, c->d_t32ts.reset(n));
-        HIP_TRY(c, c->d_cover.reset(n));
-        for (int k = 0; k < 4; k++) {
-            HIP_TRY(c, c->d_empty[k].reset((size_t)n_tiles * ROPE_SUM_WORDS));
-            HIP_TRY(c, c->d_total[k].reset((size_t)ROPE_SUM_WORDS));
-            c->empty_version[k] = 0;
-        }
+        HIP_TRY(c, c->single.grow(W, H, 1, true, true, false));
+        HIP_TRY(c, c->d_cover.reset((size_t)W * H));
+        HIP_TRY(c, c->single_empty.grow(1, (size_t)n_tiles));
+        c->single_empty.invalidate();
     }
     HIP_TRY(c, hipMemcpyAsync(c->d_PV, PV, 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -538,386 +310,39 @@ extern "C" int rope_set_target(rope_ctx *c, const uint64_t *tq, const float *t32
     if (!tq || !link_flags) ARG_FAIL(c, "rope_set_target: null pointer");
     HIP_TRY(c, hipSetDevice(c->device));
     size_t n = (size_t)c->fp.W * c->fp.H;
-    int rc = copy_h2d_staged(c, c->d_tq, tq, n * sizeof(uint64_t));
+    int rc = copy_h2d_staged(c, c->single.tq, tq, n * sizeof(uint64_t));
     if (rc) return rc;
-    if (t32) { rc = copy_h2d_staged(c, c->d_t32, t32, n * sizeof(float)); if (rc) return rc; }
+    if (t32) { rc = copy_h2d_staged(c, c->single.t32, t32, n * sizeof(float)); if (rc) return rc; }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->have_t32 = (t32 != nullptr);
-    c->have_t32ts = false;
+    c->single.has_t32 = (t32 != nullptr);
+    c->single.has_ts = false;
     std::memcpy(c->lf.f, link_flags, 8);
-    c->have_target = true;
-    c->target_version++;
+    c->single.n = 1;
+    c->single_empty.invalidate();
     return ROPE_OK;
 }
 
 extern "C" int rope_set_target_tsweep(rope_ctx *c, const float *t32_full)
 {
     if (!c) return ROPE_E_ARG;
-    if (!c->have_target) ARG_FAIL(c, "rope_set_target_tsweep: call rope_set_target first");
+    if (c->single.n < 1) ARG_FAIL(c, "rope_set_target_tsweep: call rope_set_target first");
     HIP_TRY(c, hipSetDevice(c->device));
     if (t32_full) {
-        const int rc = copy_h2d_staged(c, c->d_t32ts, t32_full, (size_t)c->fp.W * c->fp.H * sizeof(float));
+        const int rc = copy_h2d_staged(c, c->single.ts, t32_full, (size_t)c->fp.W * c->fp.H * sizeof(float));
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    c->have_t32ts = (t32_full != nullptr);
-    c->empty_version[ROPE_LOSS_TSWEEP] = 0;         // that loss's "nothing rendered" sums belong to the other plane
+    c->single.has_ts = (t32_full != nullptr);
+    c->single_empty.valid[ROPE_LOSS_TSWEEP] = false;    // that loss's "nothing rendered" sums belong to the other plane
     return ROPE_OK;
 }
 
-// numpy's rint (round half to even) of a double in [0, 2^51) without a library call: adding and taking away 2^52 leaves the
-// nearest integer, ties to even, under the default rounding mode (every step one IEEE operation: -ffp-contract=off, no fast-math).
-// Beyond 2^51 the result is only used to be clipped to 2^39 - 1.
-static inline double rint_nonneg(double x)
-{
-    double t = x + 4503599627370496.0;
-    asm volatile("" : "+x"(t));                          // the sum is rounded to a double here: the two operations stay two operations
-    return t - 4503599627370496.0;
-}
-
-// depth in metres -> Q32, as rope_pack_target documents it
-static inline uint64_t q32_of_depth(double d)
-{
-    const double Q32 = 4294967296.0, top = 549755813887.0;          // 2^32, 2^39 - 1
-    double q = (d > 0.0 && d <= 1.7976931348623157e308) ? rint_nonneg(d * Q32) : 0.0;     // NaN, inf, zero and negatives: no depth
-    q = q < top ? q : top;
-    return (uint64_t)q;
-}
-
-// Host only: float64 metres + link-mask bits -> the packed plane of rope_set_target.  Rounding is numpy's rint (round half to even).
-extern "C" int rope_pack_target(const double *depth, const uint8_t *mask_bits, int64_t n, uint64_t *out)
-{
-    if (!depth || !out || n < 0) return ROPE_E_ARG;
-    for (int64_t i = 0; i < n; i++) out[i] = q32_of_depth(depth[i]) | (mask_bits ? (uint64_t)mask_bits[i] << 40 : 0);
-    return ROPE_OK;
-}
-
-// Host only: cv2.resize(img, (W/f, H/f)) with INTER_LINEAR for an EVEN integer factor f (Predictor._downsample,
-// predict.py:378-381).  The source coordinate of every output sample falls exactly between the two central taps of its
-// f x f block (f/2-1 and f/2), both with weight 1/2, so the general interpolation collapses to four taps per sample:
-//   kind 0  uint8 : OpenCV's fixed-point path — horizontal pass with 11-bit weights, >> 4, vertical pass >> 16, + 2 >> 2
-//   kind 1  float32, kind 2 float64 : (a*w + b*w) per row, then (top*w + bottom*w), w = 0.5 in the image's own type
-// `channels` interleaved values per pixel; rows are `row_stride` BYTES apart (a strided view is fine).
-extern "C" int rope_downsample_even(const void *src, int H, int W, int channels, int64_t row_stride, int f, int kind, void *dst)
-{
-    if (!src || !dst || H < 1 || W < 1 || channels < 1 || f < 2 || (f & 1) || H % f || W % f || kind < 0 || kind > 2) return ROPE_E_ARG;
-    const int oh = H / f, ow = W / f, a = f / 2 - 1, b = f / 2;
-    const char *base = (const char *)src;
-    for (int y = 0; y < oh; y++) {
-        const char *r0 = base + (int64_t)(y * f + a) * row_stride, *r1 = base + (int64_t)(y * f + b) * row_stride;
-        for (int x = 0; x < ow; x++)
-            for (int ch = 0; ch < channels; ch++) {
-                const size_t ia = (size_t)(x * f + a) * channels + ch, ib = (size_t)(x * f + b) * channels + ch;
-                const size_t o = ((size_t)y * ow + x) * channels + ch;
-                if (kind == 0) {
-                    const uint8_t *p0 = (const uint8_t *)r0, *p1 = (const uint8_t *)r1;
-                    const int64_t t = ((int64_t)p0[ia] * 1024 + (int64_t)p0[ib] * 1024) >> 4, u = ((int64_t)p1[ia] * 1024 + (int64_t)p1[ib] * 1024) >> 4;
-                    int64_t v = (((1024 * t) >> 16) + ((1024 * u) >> 16) + 2) >> 2;
-                    ((uint8_t *)dst)[o] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-                } else if (kind == 1) {
-                    const float *p0 = (const float *)r0, *p1 = (const float *)r1;
-                    const float top = p0[ia] * 0.5f + p0[ib] * 0.5f, bot = p1[ia] * 0.5f + p1[ib] * 0.5f;
-                    ((float *)dst)[o] = top * 0.5f + bot * 0.5f;
-                } else {
-                    const double *p0 = (const double *)r0, *p1 = (const double *)r1;
-                    const double top = p0[ia] * 0.5 + p0[ib] * 0.5, bot = p1[ia] * 0.5 + p1[ib] * 0.5;
-                    ((double *)dst)[o] = top * 0.5 + bot * 0.5;
-                }
-            }
-    }
-    return ROPE_OK;
-}
-
-// Host only: one frame of the synthetic path from the camera's arrays to what rope_set_target(s) takes, in one pass — the
-// down-sampling of Predictor._downsample (predict.py:378-381: cv2.resize INTER_LINEAR; the taps and roundings of
-// rope_downsample_even), the link masks read off channel 0 of the colour render and the lookup depth of _loadSynthetic
-// (predict.py:445-469), the per-link flags and the packing of _load_target (predict.py:397-413, rope_pack_target).
-extern "C" int rope_prepare_synthetic(const uint8_t *color, int64_t color_stride, const void *depth, int depth_kind, int64_t depth_stride,
-                                      int H0, int W0, int f, const int32_t *link_blue, int n_links, int n_lookup_links,
-                                      uint64_t *tq, float *lookup_f32, double *tgt_depth, uint8_t *flags)
-{
-    if (!color || !depth || !link_blue || !tq || !lookup_f32 || !flags) return ROPE_E_ARG;
-    if (H0 < 1 || W0 < 1 || f < 1 || (f > 1 && (f & 1)) || H0 % f || W0 % f || (depth_kind != 1 && depth_kind != 2)) return ROPE_E_ARG;
-    if (n_links < 1 || n_links > ROPE_MAX_LINKS || n_lookup_links < 0 || n_lookup_links > n_links) return ROPE_E_ARG;
-    const int H = H0 / f, W = W0 / f, a = f / 2 - 1, b = f / 2;
-    // what a channel-0 value says about a pixel, looked up instead of compared link by link: the links whose colour it is (two
-    // links may share one), and whether one of them is a lookup link; the counts are kept per value and folded per link at the end
-    uint8_t bits_of[256] = {}, hit_of[256] = {};
-    int64_t n_val[256] = {}, n_val_depth[256] = {};
-    for (int l = 0; l < n_links; l++)
-        if (link_blue[l] >= 0 && link_blue[l] <= 255) {
-            bits_of[link_blue[l]] |= (uint8_t)(1u << l);
-            if (l < n_lookup_links) hit_of[link_blue[l]] = 1;
-        }
-    int cur = -1;                                                  // counts are kept for the run of equal values and flushed when it ends:
-    int64_t run = 0, run_depth = 0;                                // a colour-coded frame is long runs, and a counter in memory per pixel is a chain of store-to-load stalls
-    for (int y = 0; y < H; y++) {
-        const int ya = f > 1 ? y * f + a : y, yb = f > 1 ? y * f + b : y;
-        const uint8_t *c0 = color + (int64_t)ya * color_stride, *c1 = color + (int64_t)yb * color_stride;
-        const char *d0 = (const char *)depth + (int64_t)ya * depth_stride, *d1 = (const char *)depth + (int64_t)yb * depth_stride;
-        for (int x = 0; x < W; x++) {
-            const size_t xa = f > 1 ? (size_t)(x * f + a) : (size_t)x, xb = f > 1 ? (size_t)(x * f + b) : (size_t)x;
-            int blue;
-            double d;
-            if (f > 1) {
-                // OpenCV's fixed-point path for uint8 (rope_downsample_even, kind 0); channel 0 of three interleaved
-                const int64_t t = ((int64_t)c0[3 * xa] * 1024 + (int64_t)c0[3 * xb] * 1024) >> 4, u = ((int64_t)c1[3 * xa] * 1024 + (int64_t)c1[3 * xb] * 1024) >> 4;
-                const int64_t v = (((1024 * t) >> 16) + ((1024 * u) >> 16) + 2) >> 2;
-                blue = (int)(v < 0 ? 0 : (v > 255 ? 255 : v));
-                if (depth_kind == 1) {
-                    const float *p0 = (const float *)d0, *p1 = (const float *)d1;
-                    const float tp = p0[xa] * 0.5f + p0[xb] * 0.5f, bt = p1[xa] * 0.5f + p1[xb] * 0.5f;
-                    d = (double)(tp * 0.5f + bt * 0.5f);
-                } else {
-                    const double *p0 = (const double *)d0, *p1 = (const double *)d1;
-                    const double tp = p0[xa] * 0.5 + p0[xb] * 0.5, bt = p1[xa] * 0.5 + p1[xb] * 0.5;
-                    d = tp * 0.5 + bt * 0.5;
-                }
-            } else {
-                blue = c0[3 * xa];
-                d = depth_kind == 1 ? (double)((const float *)d0)[xa] : ((const double *)d0)[xa];
-            }
-            const unsigned bits = bits_of[blue];
-            if (blue != cur) {
-                if (cur >= 0) { n_val[cur] += run; n_val_depth[cur] += run_depth; }
-                cur = blue; run = 0; run_depth = 0;
-            }
-            run++;
-            run_depth += (d != 0.0);                               // NaN counts, as `depth != 0` does
-            const size_t o = (size_t)y * W + x;
-            if (tgt_depth) tgt_depth[o] = d;
-            lookup_f32[o] = (float)(d * (hit_of[blue] ? 1.0 : 0.0));     // target_depth * hit (predict.py:449-454): NaN stays NaN
-            tq[o] = q32_of_depth(d) | ((uint64_t)bits << 40);
-        }
-    }
-    if (cur >= 0) { n_val[cur] += run; n_val_depth[cur] += run_depth; }
-    std::memset(flags, 0, 8);
-    for (int l = 0; l < n_links; l++) {
-        if (link_blue[l] < 0 || link_blue[l] > 255) continue;
-        const int64_t n_mask = n_val[link_blue[l]], n_depth = n_val_depth[link_blue[l]];
-        if (n_mask > 0) {                                          // np.sum(mask) > 0 (predict.py:465)
-            flags[l] |= 1;
-            if ((double)n_depth > 0.05 * (double)n_mask) flags[l] |= 2;      // predict.py:495, a fact of the target alone
-        }
-    }
-    return ROPE_OK;
-}
-
-// Host only: camera pose + pinhole intrinsics -> P·V, the matrix rope_set_camera takes.  Every step is one IEEE double operation in
-// the written order (the library is built with -ffp-contract=off), sin / cos from libm.
-//   pose   [x, y, z, a3, a4, a5] as Renderer.setCameraPose takes it (render.py:107-111): roll = a4 + pi/2, pitch = a3, yaw = a5,
-//          camera-to-world R = Rz(yaw)·Ry(pitch)·Rx(roll) by the element formulas of angToPoseArr (render_utils.py:56-85),
-//          t = (x, y, z); the camera looks along its -Z, +Y up (OpenGL); V = the rigid inverse [R^T | -R^T t]
-//   P      pyrender 0.1.45's IntrinsicsCamera.get_projection_matrix (projection.py:161-169): P00 = 2fx/W, P11 = 2fy/H,
-//          P02 = 1 - 2cx/W, P12 = 2cy/H - 1, P22 = (f+n)/(n-f), P23 = 2fn/(n-f), P32 = -1
-extern "C" int rope_camera_matrix(const double *pose, double fx, double fy, double cx, double cy, int W, int H, double znear, double zfar,
-                                  double *PV)
-{
-    if (!pose || !PV || W < 1 || H < 1 || !(znear > 0.0) || !(zfar > znear)) return ROPE_E_ARG;
-    const double yaw = pose[5], pitch = pose[3], roll = pose[4] + 3.141592653589793 / 2;
-    const double c0 = std::cos(yaw), c1 = std::cos(pitch), c2 = std::cos(roll), s0 = std::sin(yaw), s1 = std::sin(pitch), s2 = std::sin(roll);
-    double R[3][3];
-    R[0][0] = c0 * c1;
-    R[1][0] = c1 * s0;
-    R[2][0] = -1 * s1;
-    R[0][1] = c0 * s1 * s2 - c2 * s0;
-    R[1][1] = c0 * c2 + (s0 * s1) * s2;
-    R[2][1] = c1 * s2;
-    R[0][2] = s0 * s2 + c0 * c2 * s1;
-    R[1][2] = c2 * s0 * s1 - c0 * s2;
-    R[2][2] = c1 * c2;
-    double V[4][4] = {};
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) V[i][j] = R[j][i];
-        V[i][3] = -((R[0][i] * pose[0] + R[1][i] * pose[1]) + R[2][i] * pose[2]);
-    }
-    V[3][3] = 1.0;
-    const double w = (double)W, h = (double)H;
-    const double P00 = 2.0 * fx / w, P11 = 2.0 * fy / h, P02 = 1.0 - 2.0 * cx / w, P12 = 2.0 * cy / h - 1.0;
-    const double P22 = (zfar + znear) / (znear - zfar), P23 = (2.0 * zfar * znear) / (znear - zfar);
-    for (int j = 0; j < 4; j++) {
-        PV[j] = P00 * V[0][j] + P02 * V[2][j];
-        PV[4 + j] = P11 * V[1][j] + P12 * V[2][j];
-        PV[8 + j] = P22 * V[2][j] + P23 * V[3][j];
-        PV[12 + j] = -V[2][j];
-    }
-    for (int k = 0; k < 16; k++)
-        if (!std::isfinite(PV[k])) return ROPE_E_ARG;
-    return ROPE_OK;
-}
-
-// Host only: the Lookup stage's pose grid in the reference's order (lookup.py:39-66).  divisions[j] >= 1: joint j takes that many
-// samples between its limits (np.linspace: lo + i * step, the last one hi itself; a single sample is lo), clipped to
-// LOOKUP_MAX_DIV_PER_LINK = 200 (constants.py:30); divisions[j] <= 0: joint j is not part of the grid and stays 0.  Joint 0 varies
-// fastest.  Returns the number of rows (the product of the sample counts); writes them when `out` is given and `capacity` rows fit
-// (ROPE_E_ARG otherwise).
-extern "C" int64_t rope_lookup_grid(const double *limits, const int32_t *divisions, double *out, int64_t capacity)
-{
-    if (!limits || !divisions) return ROPE_E_ARG;
-    int64_t div[6], n = 1;
-    for (int j = 0; j < 6; j++) {
-        div[j] = divisions[j] < 1 ? 1 : (divisions[j] > 200 ? 200 : divisions[j]);
-        n *= div[j];
-    }
-    if (!out) return n;
-    if (capacity < n) return ROPE_E_ARG;
-    int64_t repeat = 1;
-    for (int j = 0; j < 6; j++) {
-        const double lo = limits[2 * j], hi = limits[2 * j + 1], dv = (double)(div[j] - 1), delta = hi - lo;
-        const double step = div[j] > 1 ? delta / dv : 0.0;
-        for (int64_t r = 0; r < n; r++) {
-            const int64_t i = (r / repeat) % div[j];
-            double v = 0.0;                                         // not part of the grid: np.zeros
-            if (divisions[j] >= 1) {
-                if (div[j] == 1) v = lo;
-                else if (i == div[j] - 1) v = hi;
-                else v = step == 0.0 ? ((double)i / dv) * delta + lo : (double)i * step + lo;
-            }
-            out[6 * r + j] = v;
-        }
-        repeat *= div[j];
-    }
-    return n;
-}
-
-// Host only: the divisions of the pose grid Crop renders to find the image bounds of the first `num_links` links
-// (robotpose/crop.py:114-146), in rope_lookup_grid's convention — feed them to rope_lookup_grid for the poses.  Weights 6:3:3:0:1
-// over the joints S L U R B (constants.py:19: CROP_RENDER_WEIGHTING), a budget of 20 s at the reference's cost model of
-// pixels x 1.2e-8 + 0.002 s per render (crop.py:121-123), at most 50 samples per joint; joints beyond the rendered links sit at
-// their lower limit (np.linspace(lo, hi, 1)), R and T are not part of the grid (CROP_VARYING = 'SLUB') and stay 0.
-extern "C" int rope_crop_divisions(int64_t n_pixels, int num_links, int32_t *divisions)
-{
-    if (!divisions || n_pixels < 1 || num_links < 2 || num_links > 6) return ROPE_E_ARG;
-    const double weighting[6] = {6, 3, 3, 0, 1, 0};
-    const int n = num_links - 1;
-    double w[6], sum = 0.0, prod = 1.0;
-    int nz = 0;
-    for (int j = 0; j < n; j++) sum += weighting[j];
-    for (int j = 0; j < n; j++) {
-        w[j] = weighting[j] / sum;
-        if (w[j] != 0.0) { prod *= w[j]; nz++; }
-    }
-    const double num_poses = 20.0 / ((double)n_pixels * 1.2 * 1.0e-8 + .002);
-    const double scale = std::pow(num_poses / prod, 1.0 / (double)nz);
-    const bool varying[6] = {true, true, true, false, true, false};          // S L U B
-    for (int j = 0; j < 6; j++) {
-        int d = 1;
-        if (j < n) {
-            double b = w[j] * scale;
-            if (b < 1.0) b = 1.0;
-            if (b > 50.0) b = 50.0;
-            d = (int)b;
-        }
-        divisions[j] = varying[j] ? d : 0;
-    }
-    return ROPE_OK;
-}
-
-// cv2.dilate / cv2.erode of a binary image with a ones(k, k) kernel, default anchor (k / 2, k / 2), a border that never wins
-// (predict.py:428,437): separable, rows then columns; `grow` true: a pixel is set when any pixel of its window is (outside counts
-// as clear), false: when all are (outside counts as set)
-static void box_morph(const uint8_t *src, uint8_t *dst, uint8_t *tmp, int H, int W, int k, bool grow)
-{
-    const int a = k / 2, b = k - 1 - a;                  // the window of x reaches from x - a to x + b
-    for (int y = 0; y < H; y++)
-        for (int x = 0; x < W; x++) {
-            const int lo = x - a < 0 ? 0 : x - a, hi = x + b > W - 1 ? W - 1 : x + b;
-            uint8_t v = grow ? 0 : 1;
-            for (int i = lo; i <= hi; i++) v = grow ? (uint8_t)(v | src[(size_t)y * W + i]) : (uint8_t)(v & src[(size_t)y * W + i]);
-            tmp[(size_t)y * W + x] = v;
-        }
-    for (int y = 0; y < H; y++) {
-        const int lo = y - a < 0 ? 0 : y - a, hi = y + b > H - 1 ? H - 1 : y + b;
-        for (int x = 0; x < W; x++) {
-            uint8_t v = grow ? 0 : 1;
-            for (int i = lo; i <= hi; i++) v = grow ? (uint8_t)(v | tmp[(size_t)i * W + x]) : (uint8_t)(v & tmp[(size_t)i * W + x]);
-            dst[(size_t)y * W + x] = v;
-        }
-    }
-}
-
-// Host only: one frame of the SEGMENTATION path from the segmenter's instance masks to what rope_set_target(s) takes — the merge of
-// a class's instances (_reorganize_by_link, predict.py:383-395), the body mask erode7(dilate8(sum of the masks)) that zeroes the
-// depth outside the robot, once over all classes and once over the lookup links (predict.py:419-438), the depth's own
-// down-sampling (predict.py:378-381), the per-link flags and the packing of _load_target (predict.py:397-413).
-//   masks     H x W x K bytes (non-zero = inside instance k), as the segmenter returns them;  link_of: K link indices (0..n_links-1),
-//             or -1 for an instance of a class that is not one of the rendered links (it still counts for the body mask)
-extern "C" int rope_prepare_segmented(const void *depth, int depth_kind, int64_t depth_stride, int H0, int W0, int f, const uint8_t *masks,
-                                      int K, const int32_t *link_of, int n_links, int n_lookup_links, uint64_t *tq, float *lookup_f32,
-                                      double *tgt_depth, uint8_t *flags)
-{
-    if (!depth || (K > 0 && (!masks || !link_of)) || !tq || !lookup_f32 || !flags || K < 0) return ROPE_E_ARG;
-    if (H0 < 1 || W0 < 1 || f < 1 || (f > 1 && (f & 1)) || H0 % f || W0 % f || (depth_kind != 1 && depth_kind != 2)) return ROPE_E_ARG;
-    if (n_links < 1 || n_links > ROPE_MAX_LINKS || n_lookup_links < 0 || n_lookup_links > n_links) return ROPE_E_ARG;
-    for (int k = 0; k < K; k++)
-        if (link_of[k] < -1 || link_of[k] >= n_links) return ROPE_E_ARG;
-    const int H = H0 / f, W = W0 / f, a = f / 2 - 1, b = f / 2;
-    const size_t n = (size_t)H * W;
-    std::vector<uint8_t> bits(n, 0), any(n, 0), look(n, 0), body(n), body_look(n), t1(n), t2(n);
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t *m = masks + i * (size_t)K;
-        for (int k = 0; k < K; k++)
-            if (m[k]) {
-                any[i] = 1;
-                if (link_of[k] >= 0) {
-                    bits[i] |= (uint8_t)(1u << link_of[k]);
-                    if (link_of[k] < n_lookup_links) look[i] = 1;
-                }
-            }
-    }
-    box_morph(any.data(), t1.data(), t2.data(), H, W, 8, true);
-    box_morph(t1.data(), body.data(), t2.data(), H, W, 7, false);
-    box_morph(look.data(), t1.data(), t2.data(), H, W, 8, true);
-    box_morph(t1.data(), body_look.data(), t2.data(), H, W, 7, false);
-    int64_t n_mask[ROPE_MAX_LINKS] = {}, n_depth[ROPE_MAX_LINKS] = {};
-    bool present[ROPE_MAX_LINKS] = {};
-    for (int k = 0; k < K; k++)
-        if (link_of[k] >= 0) present[link_of[k]] = true;             // a class that was detected has a mask, however empty (predict.py:408-413)
-    for (int y = 0; y < H; y++) {
-        const int ya = f > 1 ? y * f + a : y, yb = f > 1 ? y * f + b : y;
-        const char *d0 = (const char *)depth + (int64_t)ya * depth_stride, *d1 = (const char *)depth + (int64_t)yb * depth_stride;
-        for (int x = 0; x < W; x++) {
-            const size_t xa = f > 1 ? (size_t)(x * f + a) : (size_t)x, xb = f > 1 ? (size_t)(x * f + b) : (size_t)x, o = (size_t)y * W + x;
-            double d;
-            if (f > 1) {
-                if (depth_kind == 1) {
-                    const float *p0 = (const float *)d0, *p1 = (const float *)d1;
-                    const float tp = p0[xa] * 0.5f + p0[xb] * 0.5f, bt = p1[xa] * 0.5f + p1[xb] * 0.5f;
-                    d = (double)(tp * 0.5f + bt * 0.5f);
-                } else {
-                    const double *p0 = (const double *)d0, *p1 = (const double *)d1;
-                    const double tp = p0[xa] * 0.5 + p0[xb] * 0.5, bt = p1[xa] * 0.5 + p1[xb] * 0.5;
-                    d = tp * 0.5 + bt * 0.5;
-                }
-            } else {
-                d = depth_kind == 1 ? (double)((const float *)d0)[xa] : ((const double *)d0)[xa];
-            }
-            d = d * (body[o] ? 1.0 : 0.0);                           // target_depth *= body (predict.py:429)
-            const double dl = d * (body_look[o] ? 1.0 : 0.0);        // lookup_depth = the copy, *= the lookup links' body (predict.py:432-438)
-            for (int l = 0; l < n_links; l++)
-                if ((bits[o] >> l) & 1) {
-                    n_mask[l]++;
-                    if (d != 0.0) n_depth[l]++;
-                }
-            if (tgt_depth) tgt_depth[o] = d;
-            lookup_f32[o] = (float)dl;
-            tq[o] = q32_of_depth(d) | ((uint64_t)bits[o] << 40);
-        }
-    }
-    std::memset(flags, 0, 8);
-    for (int l = 0; l < n_links; l++)
-        if (present[l]) {
-            flags[l] |= 1;
-            if ((double)n_depth[l] > 0.05 * (double)n_mask[l]) flags[l] |= 2;
-        }
-    return ROPE_OK;
-}
 
 // Can a vertex of the robot get behind the near plane of camera PV (P·V, row-major doubles)?  z + w is affine in the world
 // position; over the ball of radius `reach` about the base origin it is at least its value at the origin minus |gradient|
 // times the radius.  Conservative with a centimetre to spare: "no" means the kernels without the clipping code draw every
 // triangle exactly as the clipping ones would.
-static bool near_plane_in_reach(const rope_ctx *c, const double *PV)
+bool near_plane_in_reach(const rope_ctx *c, const double *PV)
 {
     const double g[3] = {PV[8] + PV[12], PV[9] + PV[13], PV[10] + PV[14]}, h = PV[11] + PV[15];
     const double gn = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
@@ -930,7 +355,8 @@ static bool use_clip(const rope_ctx *c, bool views = false)
     if (c->strategy & STRATEGY_CLIP_KERNELS) return true;
     return views ? c->clip_views : near_plane_in_reach(c, c->h_PV);
 }
-static int ensure_capacity(rope_ctx *c, int C)
+
+int ensure_capacity(rope_ctx *c, int C)
 {
     if (C <= c->cap) return ROPE_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -961,17 +387,13 @@ static int ensure_capacity(rope_ctx *c, int C)
     return ROPE_OK;
 }
 
-static int upload_candidates(rope_ctx *c, const double *cand, int C, bool group, const int32_t *frame_of = nullptr);
-
 extern "C" int rope_candidates_upload(rope_ctx *c, const double *cand, int C)
 {
     if (!c) return ROPE_E_ARG;
     return upload_candidates(c, cand, C, true);
 }
 
-// frame_of (rope_eval_targets): the frame every row is scored against; rows only share a layer inside one frame (a layer
-// carries loss sums, and those belong to a target)
-static int upload_candidates(rope_ctx *c, const double *cand, int C, bool group, const int32_t *frame_of)
+int upload_candidates(rope_ctx *c, const double *cand, int C, bool group, const int32_t *frame_of)
 {
     if (!cand || C < 1 || C > 65535) ARG_FAIL(c, "rope_candidates_upload: need 1 <= C <= 65535");
     for (size_t i = 0; i < 6 * (size_t)C; i++)
@@ -1045,36 +467,41 @@ static int upload_candidates(rope_ctx *c, const double *cand, int C, bool group,
     return ROPE_OK;
 }
 
+int apply_crop(rope_ctx *c, const char *who, const int32_t *crop, FrameParams &fp, double &n_pix)
+{
+    if (crop[0] < 0 || crop[1] >= fp.H || crop[0] > crop[1] || crop[2] < 0 || crop[3] >= fp.W || crop[2] > crop[3])
+        ARG_FAIL(c, std::string(who) + ": crop outside the image");
+    fp.r0 = crop[0]; fp.r1 = crop[1]; fp.c0 = crop[2]; fp.c1 = crop[3];
+    n_pix = (double)(crop[1] - crop[0] + 1) * (double)(crop[3] - crop[2] + 1);
+    return ROPE_OK;
+}
+
+int loss_frame(rope_ctx *c, const char *who, int loss, const int32_t *crop, FrameParams &fp, double &n_pix)
+{
+    fp = c->fp;
+    n_pix = (double)fp.W * fp.H;
+    if (loss != ROPE_LOSS_LOOKUP) return ROPE_OK;
+    if (!crop) ARG_FAIL(c, std::string(who) + ": lookup loss needs a crop");
+    return apply_crop(c, who, crop, fp, n_pix);
+}
+
 static int check_eval_args(rope_ctx *c, int n_render, int loss, const int32_t *crop, FrameParams &fp, double &n_pix)
 {
     if (!c->have_robot || !c->have_camera) ARG_FAIL(c, "eval: robot and camera must be set first");
     if (c->C < 1 || !c->cand_valid) ARG_FAIL(c, "eval: no candidates resident (upload them again after rope_eval_views)");
     if (n_render < 1 || n_render > c->n_links) ARG_FAIL(c, "eval: n_render out of range");
     if (loss < 0 || loss > 3) ARG_FAIL(c, "eval: unknown loss");
-    if (!c->have_target) ARG_FAIL(c, "eval: no target set");
-    if (loss == ROPE_LOSS_LOOKUP && !c->have_t32) ARG_FAIL(c, "eval: this loss needs the float32 target plane");
-    if (loss == ROPE_LOSS_TSWEEP && !c->have_t32 && !c->have_t32ts) ARG_FAIL(c, "eval: this loss needs a float32 target plane");
-    fp = c->fp;
-    n_pix = (double)fp.W * fp.H;
-    if (loss == ROPE_LOSS_LOOKUP) {
-        if (!crop) ARG_FAIL(c, "eval: lookup loss needs a crop");
-        if (crop[0] < 0 || crop[1] >= fp.H || crop[0] > crop[1] || crop[2] < 0 || crop[3] >= fp.W || crop[2] > crop[3]) ARG_FAIL(c, "eval: crop outside the image");
-        fp.r0 = crop[0]; fp.r1 = crop[1]; fp.c0 = crop[2]; fp.c1 = crop[3];
-        n_pix = (double)(crop[1] - crop[0] + 1) * (double)(crop[3] - crop[2] + 1);
-    }
-    return ROPE_OK;
+    if (c->single.n < 1) ARG_FAIL(c, "eval: no target set");
+    if (loss == ROPE_LOSS_LOOKUP && !c->single.has_t32) ARG_FAIL(c, "eval: this loss needs the float32 target plane");
+    if (loss == ROPE_LOSS_TSWEEP && !c->single.plane32(loss)) ARG_FAIL(c, "eval: this loss needs a float32 target plane");
+    return loss_frame(c, "eval", loss, crop, fp, n_pix);
 }
 
-// the float32 plane a loss reads: TensorSweep takes the whole target depth when it was given (rope_set_target_tsweep)
-static const float *t32_plane(const rope_ctx *c, int loss) { return (loss == ROPE_LOSS_TSWEEP && c->have_t32ts) ? c->d_t32ts : c->d_t32; }
-
-static int ensure_empty(rope_ctx *c, int loss, const FrameParams &fp)
+int ensure_totals(rope_ctx *c, const TargetSet &s, EmptyCache &cache, int loss, const FrameParams &fp)
 {
-    const int cr[4] = {fp.r0, fp.r1, fp.c0, fp.c1};
-    if (c->empty_version[loss] == c->target_version && std::memcmp(cr, c->empty_crop[loss], sizeof cr) == 0) return ROPE_OK;
-    HIP_TRY(c, launch_empty(loss, c->stream, fp, c->d_tq, t32_plane(c, loss), nullptr, c->d_empty[loss], c->d_total[loss]));
-    c->empty_version[loss] = c->target_version;
-    std::memcpy(c->empty_crop[loss], cr, sizeof cr);
+    if (cache.fresh(loss, fp)) return ROPE_OK;
+    HIP_TRY(c, launch_empty(loss, c->stream, fp, s.tq, s.plane32(loss), nullptr, cache.scratch, cache.total(loss), s.n));
+    cache.filled(loss, fp);
     return ROPE_OK;
 }
 
@@ -1154,8 +581,6 @@ static uint32_t *queue_weights(const rope_ctx *c)
 }
 
 // forward kinematics + link matrices + screen boxes + tile masks (+ cleared sums) of the resident candidates
-enum { EVAL_SINGLE = 0, EVAL_VIEWS = 1, EVAL_TARGETS = 2 };    // one target / camera-pose path (a view and a frame per row) / a frame per row
-
 static int enqueue_geometry(rope_ctx *c, int n_render, int n_shared, const FrameParams &fp, bool views)
 {
     const double *PV = views ? c->dv_PV : c->d_PV, *cand = views ? c->dv_cand : c->cand_dev;
@@ -1174,11 +599,9 @@ static int enqueue_geometry(rope_ctx *c, int n_render, int n_shared, const Frame
     return ROPE_OK;
 }
 
-static int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, double n_pix,
-                        hipEvent_t *ev /* 5 events or nullptr */, int mode = EVAL_SINGLE)
+int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, double n_pix, const EvalPlanes &pl, EvalKind kind, hipEvent_t *ev)
 {
-    const bool views = mode == EVAL_VIEWS, targets = mode == EVAL_TARGETS;
-    const float *tg_t32 = !targets ? nullptr : ((loss == ROPE_LOSS_TSWEEP && c->targets_ts) ? c->d_fts32 : (c->targets_t32 ? c->d_ft32 : nullptr));
+    const bool views = kind == EVAL_VIEWS, targets = kind == EVAL_TARGETS;
     const bool layers = !views && want_layers(c) && layers_pay(c) && !(c->strategy & STRATEGY_NO_LAYERS);
     const int n_shared = layers ? std::min(3, n_render) : 0;
     if (layers) { int rc = ensure_layers(c); if (rc) return rc; }
@@ -1238,14 +661,11 @@ static int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &
     }
     if (layers) {
         RasterArgs la = a;
-        la.layer_sums = c->d_layer_sums; la.tq = c->d_tq; la.t32 = t32_plane(c, loss);
-        if (targets) { la.tq = c->d_ftq; la.t32 = tg_t32; la.frame_of = c->frame_of_dev; }
+        la.layer_sums = c->d_layer_sums; la.tq = pl.tq; la.t32 = pl.t32; la.frame_of = pl.frame_of;
         { RopeRange r("rope:shared-layers"); int rc = enqueue_layers(c, la, loss, n_shared, fp); if (rc) return rc; }
         a.l_begin = n_shared; a.layer_of = c->d_layer_of; a.layer_rep = c->d_layer_rep; a.layers = c->d_layers; a.layer_sums = c->d_layer_sums;
     }
-    a.tq = c->d_tq; a.t32 = t32_plane(c, loss); a.sums = c->d_sums;
-    if (targets) { a.tq = c->d_ftq; a.t32 = tg_t32; a.frame_of = c->frame_of_dev; }
-    if (views) { a.tq = c->d_ftq; a.t32 = c->frames_t32 ? c->d_ft32 : nullptr; a.tl = c->frames_tl ? c->d_ftl : nullptr; a.frame_of = c->dv_frame_of; }
+    a.tq = pl.tq; a.t32 = pl.t32; a.tl = pl.tl; a.frame_of = pl.frame_of; a.sums = c->d_sums;
     if (ev) HIP_TRY(c, hipEventRecord(ev[2], c->stream));
     {
         RopeRange r("rope:raster+score");
@@ -1267,16 +687,18 @@ static int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &
     if (views) return ROPE_OK;                     // per-(view, frame) sums are finalised by the caller
     c->err_on_host = c->C <= (targets ? rope_ctx::TARGET_HOST_ROWS : rope_ctx::HOST_ERR_ROWS);
     if (targets)                                   // every row against its own frame's totals and link flags; no argmin (rows of many frames)
-        HIP_TRY(c, launch_finalize_frames(c->stream, c->d_sums, c->d_tg_total[loss], c->frame_of_dev, c->d_fflags, c->C, loss, n_render, n_pix,
+        HIP_TRY(c, launch_finalize_frames(c->stream, c->d_sums, c->resident_empty.total(loss), pl.frame_of, c->resident.flags, c->C, loss, n_render, n_pix,
                                           c->err_on_host ? c->h_err.dev() : c->d_err.get()));
     else
-        HIP_TRY(c, launch_finalize(c->stream, c->d_sums, c->d_total[loss], c->C, loss, n_render, n_pix, c->lf,
+        HIP_TRY(c, launch_finalize(c->stream, c->d_sums, c->single_empty.total(loss), c->C, loss, n_render, n_pix, c->lf,
                                    c->err_on_host ? c->h_err.dev() : c->d_err.get()));
     if (ev) HIP_TRY(c, hipEventRecord(ev[4], c->stream));
     c->last_n_render = n_render;
     c->results_valid = true;
     return ROPE_OK;
 }
+
+static EvalPlanes single_planes(const rope_ctx *c, int loss) { return {c->single.tq, c->single.plane32(loss), nullptr, nullptr}; }
 
 extern "C" int rope_eval_resident(rope_ctx *c, int n_render, int loss, const int32_t *crop)
 {
@@ -1285,9 +707,9 @@ extern "C" int rope_eval_resident(rope_ctx *c, int n_render, int loss, const int
     int rc = check_eval_args(c, n_render, loss, crop, fp, n_pix);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    rc = ensure_empty(c, loss, fp);
+    rc = ensure_totals(c, c->single, c->single_empty, loss, fp);
     if (rc) return rc;
-    return enqueue_eval(c, n_render, loss, fp, n_pix, nullptr);
+    return enqueue_eval(c, n_render, loss, fp, n_pix, single_planes(c, loss), EVAL_SINGLE);
 }
 
 extern "C" int rope_sync(rope_ctx *c)
@@ -1313,9 +735,6 @@ extern "C" int rope_results_download(rope_ctx *c, double *err_out, uint64_t *sum
     if (best_idx) *best_idx = (int32_t)res[c->C + 1];
     return ROPE_OK;
 }
-
-// One batch is at most MAX_ROWS candidates (the grid's y dimension).
-static constexpr int MAX_ROWS = 65535;
 
 extern "C" int rope_eval(rope_ctx *c, const double *cand, int C, int n_render, int loss, const int32_t *crop,
                          double *err_out, uint64_t *sums_out, int32_t *best_idx, double *best_err)
@@ -1400,11 +819,9 @@ static int render_chunks(rope_ctx *c, const RenderAsk &ask, const double *q, con
     if (!c->have_robot || !c->have_camera) RC_FAIL("robot and camera must be set first");
     if (n_render < 1 || n_render > c->n_links) RC_FAIL("n_render out of range");
     FrameParams fp = c->fp;
-    if (const int32_t *crop = ask.crop) {
-        if (crop[0] < 0 || crop[1] >= fp.H || crop[0] > crop[1] || crop[2] < 0 || crop[3] >= fp.W || crop[2] > crop[3])
-            RC_FAIL("crop outside the image");
-        fp.r0 = crop[0]; fp.r1 = crop[1]; fp.c0 = crop[2]; fp.c1 = crop[3];
-    }
+    double n_pix = (double)fp.W * fp.H;
+    if (ask.crop)
+        if (int rc = apply_crop(c, ask.entry, ask.crop, fp, n_pix)) return rc;
     if (const char *msg = own_checks()) ARG_FAIL(c, msg);
     for (size_t i = 0; i < 6 * (size_t)N; i++)
         if (!std::isfinite(q[i]) || std::fabs(q[i]) > 1.0e4) RC_FAIL("joint angle not finite or |q| > 1e4 rad");
@@ -1417,7 +834,7 @@ static int render_chunks(rope_ctx *c, const RenderAsk &ask, const double *q, con
     }
 #undef RC_FAIL
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t px = (size_t)(fp.r1 - fp.r0 + 1) * (size_t)(fp.c1 - fp.c0 + 1);
+    const size_t px = (size_t)n_pix;
     const size_t per_pose = px * ((ask.depth ? sizeof(float) : 0) + (ask.ids ? 1 : 0) + (ask.labels ? 1 : 0));
     const int chunk = (int)std::min<size_t>({(size_t)N, (size_t)MAX_ROWS, std::max<size_t>(1, RENDER_BATCH_BUDGET / per_pose)});
     int rc = ensure_capacity(c, chunk);
@@ -1557,11 +974,12 @@ extern "C" int rope_lookup_build(rope_ctx *c, const double *cand, int C, int n_r
     if (C < 1) ARG_FAIL(c, "rope_lookup_build: empty grid");
     if (!c->have_robot || !c->have_camera) ARG_FAIL(c, "rope_lookup_build: robot and camera must be set first");
     if (n_render < 1 || n_render > c->n_links) ARG_FAIL(c, "rope_lookup_build: n_render out of range");
-    if (crop[0] < 0 || crop[1] >= c->fp.H || crop[0] > crop[1] || crop[2] < 0 || crop[3] >= c->fp.W || crop[2] > crop[3])
-        ARG_FAIL(c, "rope_lookup_build: crop outside the image");
+    FrameParams fp = c->fp;
+    double n_pix;
+    if (int rc = apply_crop(c, "rope_lookup_build", crop, fp, n_pix)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->table_C = 0;
-    const size_t px = (size_t)(crop[1] - crop[0] + 1) * (size_t)(crop[3] - crop[2] + 1), need = px * (size_t)C;
+    const size_t px = (size_t)n_pix, need = px * (size_t)C;
     if (int rc = sync_grow(c, c->d_table, need)) return rc;
     if (int rc = sync_grow(c, c->d_tsums, (size_t)C * ROPE_SUM_WORDS, c->d_terr, (size_t)C + 2)) return rc;
     if (!c->d_zero_total) {
@@ -1569,8 +987,6 @@ extern "C" int rope_lookup_build(rope_ctx *c, const double *cand, int C, int n_r
         HIP_TRY(c, hipMemsetAsync(c->d_zero_total, 0, ROPE_SUM_WORDS * sizeof(uint64_t), c->stream));
     }
     HIP_TRY(c, hipMemsetAsync(c->d_table, 0, need * sizeof(float), c->stream));
-    FrameParams fp = c->fp;
-    fp.r0 = crop[0]; fp.r1 = crop[1]; fp.c0 = crop[2]; fp.c1 = crop[3];
     // the reference allows 200 divisions per joint (lookup.py:50, constants.py:30): more rows than one batch holds, so the
     // grid is rendered batch after batch into its rows of the table
     for (int lo = 0; lo < C; lo += MAX_ROWS) {
@@ -1623,14 +1039,13 @@ extern "C" int rope_lookup_score(rope_ctx *c, double *scores_out, int32_t *best_
 {
     if (!c) return ROPE_E_ARG;
     if (c->table_C < 1) ARG_FAIL(c, "rope_lookup_score: no table built");
-    if (!c->have_target || !c->have_t32) ARG_FAIL(c, "rope_lookup_score: needs a target with the float32 plane");
+    if (c->single.n < 1 || !c->single.has_t32) ARG_FAIL(c, "rope_lookup_score: needs a target with the float32 plane");
     HIP_TRY(c, hipSetDevice(c->device));
-    FrameParams fp = c->fp;
-    fp.r0 = c->table_crop[0]; fp.r1 = c->table_crop[1]; fp.c0 = c->table_crop[2]; fp.c1 = c->table_crop[3];
+    const FrameParams fp = table_frame(c);
     const double n_pix = (double)(fp.r1 - fp.r0 + 1) * (double)(fp.c1 - fp.c0 + 1);
     const size_t words = table_crop_words(fp);
     if (int rc = sync_grow(c, c->d_tc, words)) return rc;
-    HIP_TRY(c, launch_table_score(c->stream, fp, c->d_tcount, c->d_toff, c->d_tgoff, c->d_tgval, c->table_C, c->d_t32, c->d_tc,
+    HIP_TRY(c, launch_table_score(c->stream, fp, c->d_tcount, c->d_toff, c->d_tgoff, c->d_tgval, c->table_C, c->single.t32, c->d_tc,
                                   c->d_ttotal, c->d_tsums));
     HIP_TRY(c, launch_finalize(c->stream, c->d_tsums, c->d_zero_total, c->table_C, ROPE_LOSS_LOOKUP, ROPE_MAX_LINKS, n_pix, c->lf, c->d_terr));
     if (scores_out) HIP_TRY(c, hipMemcpyAsync(scores_out, c->d_terr, (size_t)c->table_C * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1642,388 +1057,6 @@ extern "C" int rope_lookup_score(rope_ctx *c, double *scores_out, int32_t *best_
     return ROPE_OK;
 }
 
-extern "C" int rope_set_frames(rope_ctx *c, int n_frames, const double *q, const uint64_t *tq, const float *t32,
-                               const uint64_t *link_planes)
-{
-    if (!c) return ROPE_E_ARG;
-    if (!c->have_camera) ARG_FAIL(c, "rope_set_frames: call rope_set_camera first (image size)");
-    if (!q || !tq || n_frames < 1 || n_frames > 4096) ARG_FAIL(c, "rope_set_frames: need 1 <= n_frames <= 4096, q and tq");
-    for (size_t i = 0; i < 6 * (size_t)n_frames; i++)
-        if (!std::isfinite(q[i]) || std::fabs(q[i]) > 1.0e4) ARG_FAIL(c, "rope_set_frames: joint angle not finite or |q| > 1e4 rad");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t plane = (size_t)c->fp.W * c->fp.H, n = plane * (size_t)n_frames;
-    // buffers only ever grow: a predictor calls this once per run with the same shapes
-    HIP_TRY(c, c->d_ftq.grow(n));
-    int rc = copy_h2d_staged(c, c->d_ftq, tq, n * sizeof(uint64_t));
-    if (rc) return rc;
-    c->frames_t32 = (t32 != nullptr);
-    if (t32) {
-        HIP_TRY(c, c->d_ft32.grow(n));
-        rc = copy_h2d_staged(c, c->d_ft32, t32, n * sizeof(float));
-        if (rc) return rc;
-    }
-    c->frames_tl = (link_planes != nullptr);
-    if (link_planes) {
-        HIP_TRY(c, c->d_ftl.grow(n * ROPE_MAX_LINKS));
-        rc = copy_h2d_staged(c, c->d_ftl, link_planes, n * ROPE_MAX_LINKS * sizeof(uint64_t));
-        if (rc) return rc;
-    }
-    HIP_TRY(c, c->d_ftotal.grow(5 * (size_t)n_frames * ROPE_SUM_WORDS));                  // per loss kind, a block for the frames allocated
-    HIP_TRY(c, c->d_fempty.grow((size_t)MAX_MASK_WORDS * 32 * ROPE_SUM_WORDS));           // any tile count
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->h_fq.assign(q, q + 6 * (size_t)n_frames);
-    c->n_frames = n_frames;
-    c->n_targets = 0;                             // the planes are the camera-pose path's now
-    for (bool &v : c->ftotal_valid) v = false;
-    return ROPE_OK;
-}
-
-extern "C" int rope_eval_views(rope_ctx *c, const double *PV, int K, int n_render, int loss, uint64_t *sums_out)
-{
-    if (!c) return ROPE_E_ARG;
-    if (!c->have_robot || !c->have_camera) ARG_FAIL(c, "rope_eval_views: robot and camera must be set first");
-    if (c->n_frames < 1) ARG_FAIL(c, "rope_eval_views: no frames set");
-    if (!PV || !sums_out || K < 1) ARG_FAIL(c, "rope_eval_views: bad arguments");
-    if ((long long)K * c->n_frames > 65535) ARG_FAIL(c, "rope_eval_views: views x frames must not exceed 65535");
-    if (n_render < 1 || n_render > c->n_links) ARG_FAIL(c, "rope_eval_views: n_render out of range");
-    if (loss != ROPE_LOSS_DEPTH && loss != ROPE_LOSS_TSWEEP && loss != ROPE_LOSS_CAMFULL) ARG_FAIL(c, "rope_eval_views: loss must be DEPTH, TSWEEP or CAMFULL");
-    if (loss == ROPE_LOSS_TSWEEP && !c->frames_t32) ARG_FAIL(c, "rope_eval_views: this loss needs the frames' float32 planes");
-    if (loss == ROPE_LOSS_CAMFULL && !c->frames_tl) ARG_FAIL(c, "rope_eval_views: this loss needs the frames' link planes");
-    for (size_t i = 0; i < 16 * (size_t)K; i++)
-        if (!std::isfinite(PV[i])) ARG_FAIL(c, "rope_eval_views: non-finite view matrix");
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->clip_views = false;
-    for (int k = 0; k < K; k++) c->clip_views = c->clip_views || near_plane_in_reach(c, PV + 16 * (size_t)k);
-    const int N = c->n_frames, C = K * N;
-    int rc = ensure_capacity(c, C);
-    if (rc) return rc;
-    // One pinned block -> one copy: candidate (k, i) = view k, frame i (joint vector of frame i, scored against frame
-    // i's planes) | the K view matrices | view index | frame index
-    const size_t off_pv = 6 * (size_t)C * sizeof(double), off_vo = off_pv + 16 * (size_t)K * sizeof(double),
-                 off_fo = off_vo + (size_t)C * sizeof(int32_t), bytes = off_fo + (size_t)C * sizeof(int32_t);
-    rc = sync_grow(c, c->h_vstage, bytes, c->d_vstage, bytes);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));      // the block may still feed the previous call's copy
-    double *hc = reinterpret_cast<double *>(c->h_vstage.get());
-    int32_t *hvo = reinterpret_cast<int32_t *>(c->h_vstage + off_vo), *hfo = reinterpret_cast<int32_t *>(c->h_vstage + off_fo);
-    for (int k = 0; k < K; k++)
-        for (int i = 0; i < N; i++) {
-            std::memcpy(hc + 6 * ((size_t)k * N + i), &c->h_fq[6 * (size_t)i], 6 * sizeof(double));
-            hvo[(size_t)k * N + i] = k;
-            hfo[(size_t)k * N + i] = i;
-        }
-    std::memcpy(c->h_vstage + off_pv, PV, 16 * (size_t)K * sizeof(double));
-    HIP_TRY(c, hipMemcpyAsync(c->d_vstage, c->h_vstage, bytes, hipMemcpyHostToDevice, c->stream));
-    c->dv_cand = reinterpret_cast<const double *>(c->d_vstage.get());
-    c->dv_PV = reinterpret_cast<const double *>(c->d_vstage + off_pv);
-    c->dv_view_of = reinterpret_cast<const int32_t *>(c->d_vstage + off_vo);
-    c->dv_frame_of = reinterpret_cast<const int32_t *>(c->d_vstage + off_fo);
-    c->C = C;
-    c->cand_valid = false;                            // the rows are (view, frame) pairs now: cand_dev / err_on_host describe nothing
-    c->results_valid = false;
-    c->cand_dev = nullptr;
-    c->n_layers = C;                                  // every (view, frame) candidate is its own layer: nothing shared
-    const size_t plane = (size_t)c->fp.W * c->fp.H;
-    uint64_t *ftotal = c->d_ftotal + (size_t)loss * (c->d_ftotal.cap() / 5);            // one block of totals per loss kind
-    if (!c->ftotal_valid[loss]) {
-        // sums of every frame with nothing rendered: the raster launch only adds what the render changes
-        for (int i = 0; i < N; i++)
-            HIP_TRY(c, launch_empty(loss, c->stream, c->fp, c->d_ftq + (size_t)i * plane, c->frames_t32 ? c->d_ft32 + (size_t)i * plane : nullptr,
-                                    c->frames_tl ? c->d_ftl + (size_t)i * plane * ROPE_MAX_LINKS : nullptr, c->d_fempty,
-                                    ftotal + (size_t)i * ROPE_SUM_WORDS));
-        c->ftotal_valid[loss] = true;
-    }
-    rc = enqueue_eval(c, n_render, loss, c->fp, (double)plane, nullptr, EVAL_VIEWS);
-    if (rc) return rc;
-    const size_t n_sums = (size_t)C * ROPE_SUM_WORDS, n_tot = (size_t)N * ROPE_SUM_WORDS;
-    HIP_TRY(c, c->h_vsums.grow(n_sums + n_tot));
-    HIP_TRY(c, hipMemcpyAsync(c->h_vsums, c->d_sums, n_sums * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->h_vsums + n_sums, ftotal, n_tot * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const uint64_t *total = c->h_vsums + n_sums;
-    std::memcpy(sums_out, c->h_vsums, n_sums * sizeof(uint64_t));
-    const bool links = (loss == ROPE_LOSS_CAMFULL);
-    for (int k = 0; k < K; k++)
-        for (int i = 0; i < N; i++)
-            for (int w = 0; w < ROPE_SUM_WORDS; w++) {
-                uint64_t &o = sums_out[((size_t)k * N + i) * ROPE_SUM_WORDS + w];
-                const bool live = w < SUM_LINK0 || (links && w < SUM_LINK0 + 3 * n_render);
-                o = live ? o + total[(size_t)i * ROPE_SUM_WORDS + w] : 0;      // modulo 2^64, as the kernel's deltas are
-            }
-    return ROPE_OK;
-}
-
-// per-frame scratch of the batched prediction, sized for n_frames resident targets
-static int size_target_scratch(rope_ctx *c, int n_frames)
-{
-    for (int k = 0; k < 4; k++) HIP_TRY(c, c->d_tg_total[k].grow((size_t)n_frames * ROPE_SUM_WORDS));
-    HIP_TRY(c, c->d_tg_ltotal.grow((size_t)n_frames * ROPE_SUM_WORDS));
-    HIP_TRY(c, c->d_tg_empty.grow((size_t)n_frames * c->n_tiles * ROPE_SUM_WORDS));
-    HIP_TRY(c, c->d_tg_best.grow(2 * (size_t)n_frames));
-    return ROPE_OK;
-}
-
-// ---- batched prediction: the targets of many frames resident at once, every row of a batch scored against its own frame's
-extern "C" int rope_set_targets(rope_ctx *c, int n_frames, const uint64_t *tq, const float *t32, const float *t32_tsweep, const uint8_t *link_flags)
-{
-    if (!c) return ROPE_E_ARG;
-    if (!c->have_camera) ARG_FAIL(c, "rope_set_targets: call rope_set_camera first (image size)");
-    if (!tq || !link_flags || n_frames < 1 || n_frames > 65535) ARG_FAIL(c, "rope_set_targets: need 1 <= n_frames <= 65535, tq and link_flags");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->n_targets = 0;
-    c->n_frames = 0;                              // d_ftq / d_ft32 are shared with the camera-pose path's frames
-    const size_t plane = (size_t)c->fp.W * c->fp.H, n = plane * (size_t)n_frames;
-    HIP_TRY(c, c->d_ftq.grow(n));
-    int rc = copy_h2d_staged(c, c->d_ftq, tq, n * sizeof(uint64_t));
-    if (rc) return rc;
-    if (t32) {
-        HIP_TRY(c, c->d_ft32.grow(n));
-        rc = copy_h2d_staged(c, c->d_ft32, t32, n * sizeof(float));
-        if (rc) return rc;
-    }
-    if (t32_tsweep) {
-        HIP_TRY(c, c->d_fts32.grow(n));
-        rc = copy_h2d_staged(c, c->d_fts32, t32_tsweep, n * sizeof(float));
-        if (rc) return rc;
-    }
-    HIP_TRY(c, c->d_fflags.grow((size_t)n_frames));
-    static_assert(sizeof(LinkFlags) == 8, "link flags travel as 8 bytes per frame");
-    rc = copy_h2d_staged(c, c->d_fflags, link_flags, 8 * (size_t)n_frames);
-    if (rc) return rc;
-    rc = size_target_scratch(c, n_frames);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->targets_t32 = (t32 != nullptr);
-    c->targets_ts = (t32_tsweep != nullptr);
-    for (bool &v : c->tg_total_valid) v = false;
-    for (bool &v : c->ftotal_valid) v = false;
-    c->n_targets = n_frames;
-    return ROPE_OK;
-}
-
-// The staged planes for n_frames frames, every one tried: rope_stage_targets and the slot-filling calls may run beside an
-// evaluation on another thread, so nothing here waits on, or reports through, anything the evaluation calls use.
-static bool grow_staged(rope_ctx *c, int n_frames, bool t32, bool ts)
-{
-    const size_t n = (size_t)c->fp.W * c->fp.H * (size_t)n_frames;
-    bool ok = c->s_ftq.grow(n) == 0;
-    if (t32) ok = (c->s_ft32.grow(n) == 0) && ok;
-    if (ts) ok = (c->s_fts32.grow(n) == 0) && ok;
-    return (c->s_fflags.grow((size_t)n_frames) == 0) && ok;
-}
-
-// waits for everything rope_stage_targets_segmented enqueued on its callers' streams
-static int drain_stage_events(rope_ctx *c)
-{
-    int rc = ROPE_OK;
-    for (hipEvent_t e : c->stage_events) {
-        if (hipEventSynchronize(e) != hipSuccess) rc = ROPE_E_HIP;
-        (void)hipEventDestroy(e);
-    }
-    c->stage_events.clear();
-    return rc;
-}
-
-// The same targets as rope_set_targets, but into the context's SECOND set of planes and on a stream of its own: returns once the
-// copies are enqueued (page-locked sources, rope_host_alloc) — the resident set stays in use meanwhile, from this or another thread
-// (this call touches nothing the evaluation calls use).  The host buffers belong to the copy until rope_commit_targets returns.
-extern "C" int rope_stage_targets(rope_ctx *c, int n_frames, const uint64_t *tq, const float *t32, const float *t32_tsweep, const uint8_t *link_flags)
-{
-    if (!c) return ROPE_E_ARG;
-    // this call may run beside an evaluation on another thread: its failures are reported through the return code and a message of its own
-    auto fail = [&](int code, const char *msg) { c->stage_err = msg; return code; };
-    c->stage_err.clear();
-    if (!c->have_camera) return fail(ROPE_E_ARG, "rope_stage_targets: call rope_set_camera first (image size)");
-    if (!tq || !link_flags || n_frames < 1 || n_frames > 65535) return fail(ROPE_E_ARG, "rope_stage_targets: need 1 <= n_frames <= 65535, tq and link_flags");
-    if (hipSetDevice(c->device) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets: hipSetDevice failed");
-    if (!c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets: no stream");
-    if (hipStreamSynchronize(c->copy_stream) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets: the upload stream failed");
-    if (drain_stage_events(c)) return fail(ROPE_E_HIP, "rope_stage_targets: a staging kernel failed");     // of a set left unfinished
-    c->seg_n_total = 0;
-    c->staged_n = 0;
-    const int W = c->fp.W, H = c->fp.H;
-    const size_t plane = (size_t)W * H, n = plane * (size_t)n_frames;
-    if (!grow_staged(c, n_frames, t32 != nullptr, t32_tsweep != nullptr)) { (void)hipGetLastError(); return fail(ROPE_E_NOMEM, "rope_stage_targets: out of device memory"); }
-    // the few bytes of flags first: a small (or pageable) source goes through the pinned block, which waits for the stream
-    int rc = copy_h2d_on(c->copy_stream, c->h_copy2, c->stage_err, c->s_fflags, link_flags, 8 * (size_t)n_frames);
-    if (!rc) rc = copy_h2d_on(c->copy_stream, c->h_copy2, c->stage_err, c->s_ftq, tq, n * sizeof(uint64_t));
-    if (!rc && t32) rc = copy_h2d_on(c->copy_stream, c->h_copy2, c->stage_err, c->s_ft32, t32, n * sizeof(float));
-    if (!rc && t32_tsweep) rc = copy_h2d_on(c->copy_stream, c->h_copy2, c->stage_err, c->s_fts32, t32_tsweep, n * sizeof(float));
-    if (rc) return rc;
-    c->staged_t32 = (t32 != nullptr);
-    c->staged_ts = (t32_tsweep != nullptr);
-    c->staged_W = W; c->staged_H = H;
-    c->staged_n = n_frames;
-    return ROPE_OK;
-}
-
-// What a call that fills slots of the staged set ON THE DEVICE starts with, its arguments checked: a call with slot0 > 0 must go on
-// with the set as it was started; the staged planes are written from here on, so a complete staging is withdrawn; slot0 == 0 sizes
-// a new set of n_total frames.  `who` names the caller in the messages.
-static int stage_slots_begin(rope_ctx *c, const char *who, int n_total, int slot0, bool ts)
-{
-    auto fail = [&](int code, const char *msg) { c->stage_err = std::string(who) + msg; return code; };
-    const int W = c->fp.W, H = c->fp.H;
-    if (slot0 > 0 && (c->seg_n_total != n_total || c->seg_ts != ts || c->staged_W != W || c->staged_H != H))
-        return fail(ROPE_E_ARG, ": n_total, want_tsweep or the image size changed in mid-set (slot0 == 0 starts a set)");
-    if (hipSetDevice(c->device) != hipSuccess) return fail(ROPE_E_HIP, ": hipSetDevice failed");
-    c->staged_n = 0;                              // the staged planes are written from here on: complete again when every slot is filled
-    if (slot0 != 0) return ROPE_OK;
-    c->seg_n_total = 0;                           // a new set: sized here, once
-    if (c->copy_stream && hipStreamSynchronize(c->copy_stream) != hipSuccess) return fail(ROPE_E_HIP, ": the upload stream failed");
-    if (drain_stage_events(c)) return fail(ROPE_E_HIP, ": a staging kernel failed");   // of a set left unfinished
-    if (!grow_staged(c, n_total, true, ts) || c->s_counts.grow((size_t)n_total * 2 * ROPE_MAX_LINKS) != 0) {
-        (void)hipGetLastError();
-        return fail(ROPE_E_NOMEM, ": out of device memory");
-    }
-    c->meta_used = 0;
-    c->seg_filled.assign((size_t)n_total, 0);
-    c->seg_n_filled = 0;
-    c->seg_ts = ts;
-    c->staged_W = W; c->staged_H = H;
-    c->seg_n_total = n_total;
-    return ROPE_OK;
-}
-
-// ... and ends with, its kernels enqueued: the slots are marked, and the set is complete once every one of them has been filled
-static void stage_slots_filled(rope_ctx *c, int n_total, int slot0, int n_frames, bool ts)
-{
-    for (int i = slot0; i < slot0 + n_frames; i++)
-        if (!c->seg_filled[i]) { c->seg_filled[i] = 1; c->seg_n_filled++; }
-    if (c->seg_n_filled == n_total) {
-        c->staged_t32 = true;
-        c->staged_ts = ts;
-        c->staged_n = n_total;
-    }
-}
-
-// The staged set filled on the DEVICE, slots slot0 .. slot0 + n_frames - 1 of n_total: the segmentation path's targets from instance
-// masks that are in HBM already (rope_targets.hip: what rope_prepare_segmented computes per frame at f == 1).  The kernels go onto
-// `stream`, the caller's, behind the work that produced the masks; the call does not wait for them — rope_commit_targets does.
-extern "C" int rope_stage_targets_segmented(rope_ctx *c, int n_total, int slot0, int n_frames, const void *depth_dev, int depth_kind,
-                                            const uint8_t *masks_dev, const int32_t *inst_first, const int32_t *link_of, int n_lookup_links,
-                                            int want_tsweep, void *stream)
-{
-    if (!c) return ROPE_E_ARG;
-    auto fail = [&](int code, const char *msg) { c->stage_err = msg; return code; };
-    c->stage_err.clear();
-    // the arguments first: a refused call changes nothing, neither a staging that waits for its commit nor a set half filled
-    if (!c->have_camera || !c->have_robot) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: robot and camera must be set first");
-    if (n_total < 1 || n_total > 65535 || n_frames < 1 || slot0 < 0 || slot0 > n_total || n_frames > n_total - slot0)
-        return fail(ROPE_E_ARG, "rope_stage_targets_segmented: need 1 <= n_total <= 65535 and slots slot0 .. slot0 + n_frames - 1 inside it");
-    if (depth_kind != 1 && depth_kind != 2) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: depth_kind is 1 (float32) or 2 (float64)");
-    if (!depth_dev || !inst_first) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: depth_dev and inst_first are required");
-    if (n_lookup_links < 0 || n_lookup_links > c->n_links) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: n_lookup_links outside 0 .. n_links");
-    if (inst_first[0] < 0) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: inst_first not monotone");
-    for (int i = 0; i < n_frames; i++)
-        if (inst_first[i + 1] < inst_first[i]) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: inst_first not monotone");
-    const int K = inst_first[n_frames];
-    if (K > 0 && (!masks_dev || !link_of)) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: instances without masks_dev / link_of");
-    for (int k = 0; k < K; k++)
-        if (link_of[k] < -1 || link_of[k] >= c->n_links) return fail(ROPE_E_ARG, "rope_stage_targets_segmented: link_of outside -1 .. n_links - 1");
-    const bool ts = want_tsweep != 0;
-    if (int rc = stage_slots_begin(c, "rope_stage_targets_segmented", n_total, slot0, ts)) return rc;
-    const int W = c->fp.W, H = c->fp.H;
-    const size_t plane = (size_t)W * H;
-    // this call's tables, appended: plane offsets | links present per frame | code per plane
-    const size_t need = 2 * (size_t)n_frames + 1 + (size_t)K;
-    if (c->meta_used + need > c->d_meta.cap()) {  // the kernels in flight read the old block: wait for them, then start a larger one
-        if (drain_stage_events(c)) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: a staging kernel failed");
-        const size_t cap = std::max<size_t>(std::max<size_t>(2 * c->d_meta.cap(), need), 4096);
-        c->meta_used = 0;
-        c->d_meta.release();                      // the device block, allocated last, says how large the pair is
-        if (c->h_meta.reset(cap) || c->d_meta.reset(cap)) {
-            (void)hipGetLastError();
-            return fail(ROPE_E_NOMEM, "rope_stage_targets_segmented: out of memory");
-        }
-    }
-    int32_t *m = c->h_meta + c->meta_used;
-    for (int i = 0; i <= n_frames; i++) m[i] = inst_first[i];
-    for (int i = 0; i < n_frames; i++) {
-        int present = 0;
-        for (int k = inst_first[i]; k < inst_first[i + 1]; k++)
-            if (link_of[k] >= 0) present |= 1 << link_of[k];
-        m[n_frames + 1 + i] = present;
-    }
-    for (int k = 0; k < K; k++)
-        m[2 * n_frames + 1 + k] = 0x200 | (link_of[k] >= 0 ? (1 << link_of[k]) | (link_of[k] < n_lookup_links ? 0x100 : 0) : 0);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int32_t *meta_dev = c->d_meta + c->meta_used;
-    if (hipMemcpyAsync(c->d_meta + c->meta_used, m, need * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess)
-        return fail(ROPE_E_HIP, "rope_stage_targets_segmented: hipMemcpyAsync failed");
-    c->meta_used += need;
-    const size_t o = plane * (size_t)slot0;
-    hipEvent_t done = nullptr;
-    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets_segmented: no event");
-    c->stage_events.push_back(done);              // recorded or not, the next wait gets rid of it
-    if (launch_segmented_targets(st, H, W, n_frames, depth_dev, depth_kind, masks_dev, meta_dev, c->n_links, c->s_ftq + o, c->s_ft32 + o,
-                                 ts ? c->s_fts32 + o : nullptr, c->s_counts + (size_t)slot0 * 2 * ROPE_MAX_LINKS, c->s_fflags + slot0) != hipSuccess ||
-        hipEventRecord(done, st) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ROPE_E_HIP, "rope_stage_targets_segmented: the launch failed");
-    }
-    stage_slots_filled(c, n_total, slot0, n_frames, ts);
-    return ROPE_OK;
-}
-
-// The same slots filled from full-size renders that are in HBM already (rope_synth.hip: what rope_prepare_synthetic computes per
-// frame for the colour plane blue_of_id[ids] and float32 depth, the down-sampling included).  Slots, completion, commit, threading
-// and refusals are those of rope_stage_targets_segmented.
-extern "C" int rope_stage_targets_synthetic(rope_ctx *c, int n_total, int slot0, int n_frames, const float *depth_dev, const uint8_t *ids_dev,
-                                            int H0, int W0, int f, const uint8_t *blue_of_id, const int32_t *link_blue, int n_links,
-                                            int n_lookup_links, int want_tsweep, void *stream)
-{
-    if (!c) return ROPE_E_ARG;
-    auto fail = [&](int code, const char *msg) { c->stage_err = msg; return code; };
-    c->stage_err.clear();
-    // the arguments first: a refused call changes nothing, neither a staging that waits for its commit nor a set half filled
-    if (!c->have_camera || !c->have_robot) return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: robot and camera must be set first");
-    if (n_total < 1 || n_total > 65535 || n_frames < 1 || slot0 < 0 || slot0 > n_total || n_frames > n_total - slot0)
-        return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: need 1 <= n_total <= 65535 and slots slot0 .. slot0 + n_frames - 1 inside it");
-    if (!depth_dev || !ids_dev || !blue_of_id || !link_blue) return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: depth_dev, ids_dev, blue_of_id and link_blue are required");
-    if (n_links < 1 || n_links > ROPE_MAX_LINKS || n_lookup_links < 0 || n_lookup_links > n_links)
-        return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: need 1 <= n_links <= 6 and n_lookup_links inside 0 .. n_links");
-    if (H0 < 1 || W0 < 1 || f < 1 || (f > 1 && (f & 1)) || H0 % f || W0 % f || H0 / f != c->fp.H || W0 / f != c->fp.W)
-        return fail(ROPE_E_ARG, "rope_stage_targets_synthetic: f is 1 or even, and H0 / f x W0 / f must be the image size of rope_set_camera");
-    const bool ts = want_tsweep != 0;
-    if (int rc = stage_slots_begin(c, "rope_stage_targets_synthetic", n_total, slot0, ts)) return rc;
-    const size_t plane = (size_t)c->fp.W * c->fp.H, o = plane * (size_t)slot0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t done = nullptr;
-    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) return fail(ROPE_E_HIP, "rope_stage_targets_synthetic: no event");
-    c->stage_events.push_back(done);              // recorded or not, the next wait gets rid of it
-    if (launch_synthetic_targets(st, H0, W0, f, n_frames, depth_dev, ids_dev, blue_of_id, link_blue, n_links, n_lookup_links, c->s_ftq + o,
-                                 c->s_ft32 + o, ts ? c->s_fts32 + o : nullptr, c->s_counts + (size_t)slot0 * 2 * ROPE_MAX_LINKS,
-                                 c->s_fflags + slot0) != hipSuccess ||
-        hipEventRecord(done, st) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ROPE_E_HIP, "rope_stage_targets_synthetic: the launch failed");
-    }
-    stage_slots_filled(c, n_total, slot0, n_frames, ts);
-    return ROPE_OK;
-}
-
-// Host only: the thresholds of the depth holes' seed bits.  Dilation j has size d = 3 (j + 1) < max_size (np.arange(3, max_size, 3),
-// noise.py:16); a pixel is a seed of it when |N(0, std)| >= 1 - thresh_factor / d, with probability p = erfc(thresh / (std sqrt 2));
-// T = floor(p 2^32), the whole range when p reaches 1.  Every step one IEEE double operation, erfc and sqrt from libm.
-extern "C" int rope_hole_thresholds(double sigma, double thresh_factor, int max_size, uint32_t *T_out, int *n_out)
-{
-    if (!n_out || !(sigma > 0.0) || !std::isfinite(sigma) || !std::isfinite(thresh_factor)) return ROPE_E_ARG;
-    const int n = max_size > 3 ? (max_size - 1) / 3 : 0;
-    if (n > ROPE_HOLE_MAX_DILATIONS || 3 * n > ROPE_HOLE_MAX_WINDOW) return ROPE_E_ARG;
-    *n_out = n;
-    if (!T_out) return ROPE_OK;
-    for (int j = 0; j < n; j++) {
-        const double d = 3.0 * (j + 1);
-        const double thresh = 1.0 - thresh_factor / d;
-        const double p = std::erfc(thresh / (sigma * std::sqrt(2.0)));
-        const double t = std::floor(p * 4294967296.0);
-        T_out[j] = t >= 4294967295.0 ? 0xFFFFFFFFu : (t > 0.0 ? (uint32_t)t : 0u);
-    }
-    return ROPE_OK;
-}
 
 // Depth holes in place on N float32 planes that are in HBM (rope_synth.hip), on the caller's stream; no context, the current device.
 extern "C" int rope_depth_holes(float *depth_dev, int N, int H, int W, uint32_t frame0, uint64_t seed, const uint32_t *T, const int32_t *d,
@@ -2041,128 +1074,6 @@ extern "C" int rope_depth_holes(float *depth_dev, int N, int H, int W, uint32_t 
     return ROPE_OK;
 }
 
-// The resident set of targets back to the host, for tests: tq / t32 / t32_tsweep n_targets planes, flags n_targets x 8 bytes; any
-// may be NULL.
-extern "C" int rope_debug_targets(rope_ctx *c, uint64_t *tq, float *t32, float *t32_tsweep, uint8_t *flags)
-{
-    if (!c) return ROPE_E_ARG;
-    if (c->n_targets < 1) ARG_FAIL(c, "rope_debug_targets: no targets set (rope_set_targets / rope_commit_targets)");
-    if ((t32 && !c->targets_t32) || (t32_tsweep && !c->targets_ts)) ARG_FAIL(c, "rope_debug_targets: the resident set has no such float32 planes");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)c->fp.W * c->fp.H * (size_t)c->n_targets;
-    int rc = ROPE_OK;
-    if (tq) rc = copy_d2h_staged(c, tq, c->d_ftq, n * sizeof(uint64_t));
-    if (!rc && t32) rc = copy_d2h_staged(c, t32, c->d_ft32, n * sizeof(float));
-    if (!rc && t32_tsweep) rc = copy_d2h_staged(c, t32_tsweep, c->d_fts32, n * sizeof(float));
-    if (!rc && flags) rc = copy_d2h_staged(c, flags, c->d_fflags, 8 * (size_t)c->n_targets);
-    return rc;
-}
-
-// The staged set becomes the resident one (and the resident planes the next staging space): waits for the upload and for the
-// context's own stream, then swaps.
-extern "C" int rope_commit_targets(rope_ctx *c)
-{
-    if (!c) return ROPE_E_ARG;
-    if (c->staged_n < 1) { c->err = c->stage_err.empty() ? "rope_commit_targets: nothing staged (rope_stage_targets)" : c->stage_err; return ROPE_E_ARG; }
-    if (c->staged_W != c->fp.W || c->staged_H != c->fp.H) { c->staged_n = 0; ARG_FAIL(c, "rope_commit_targets: the image size changed since rope_stage_targets"); }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-    if (drain_stage_events(c)) { c->staged_n = 0; c->seg_n_total = 0; c->err = "rope_commit_targets: a staging kernel failed"; return ROPE_E_HIP; }
-    c->seg_n_total = 0;                           // the set is taken: a later rope_stage_targets_segmented starts at slot 0
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const int n_frames = c->staged_n;
-    c->staged_n = 0;
-    c->n_targets = 0;
-    c->n_frames = 0;                              // d_ftq / d_ft32 are shared with the camera-pose path's frames
-    c->d_ftq.swap(c->s_ftq);
-    if (c->staged_t32) c->d_ft32.swap(c->s_ft32);
-    if (c->staged_ts) c->d_fts32.swap(c->s_fts32);
-    c->d_fflags.swap(c->s_fflags);
-    int rc = size_target_scratch(c, n_frames);
-    if (rc) return rc;
-    c->targets_t32 = c->staged_t32;
-    c->targets_ts = c->staged_ts;
-    for (bool &v : c->tg_total_valid) v = false;
-    for (bool &v : c->ftotal_valid) v = false;
-    c->n_targets = n_frames;
-    return ROPE_OK;
-}
-
-// "nothing rendered" totals of every resident target for this loss (and crop)
-static int ensure_target_totals(rope_ctx *c, int loss, const FrameParams &fp)
-{
-    const int cr[4] = {fp.r0, fp.r1, fp.c0, fp.c1};
-    if (c->tg_total_valid[loss] && std::memcmp(cr, c->tg_crop[loss], sizeof cr) == 0) return ROPE_OK;
-    const float *t32 = (loss == ROPE_LOSS_TSWEEP && c->targets_ts) ? c->d_fts32 : (c->targets_t32 ? c->d_ft32 : nullptr);
-    HIP_TRY(c, launch_empty(loss, c->stream, fp, c->d_ftq, t32, nullptr, c->d_tg_empty, c->d_tg_total[loss], c->n_targets));
-    c->tg_total_valid[loss] = true;
-    std::memcpy(c->tg_crop[loss], cr, sizeof cr);
-    return ROPE_OK;
-}
-
-extern "C" int rope_eval_targets(rope_ctx *c, const double *cand, const int32_t *frame_of, int R, int n_render, int loss, const int32_t *crop,
-                                 double *err_out)
-{
-    if (!c) return ROPE_E_ARG;
-    if (!c->have_robot || !c->have_camera) ARG_FAIL(c, "rope_eval_targets: robot and camera must be set first");
-    if (c->n_targets < 1) ARG_FAIL(c, "rope_eval_targets: no targets set (rope_set_targets)");
-    if (!cand || !frame_of || !err_out || R < 1) ARG_FAIL(c, "rope_eval_targets: bad arguments");
-    if (n_render < 1 || n_render > c->n_links) ARG_FAIL(c, "rope_eval_targets: n_render out of range");
-    if (loss < 0 || loss > 3) ARG_FAIL(c, "rope_eval_targets: unknown loss");
-    if (loss == ROPE_LOSS_LOOKUP && !c->targets_t32) ARG_FAIL(c, "rope_eval_targets: this loss needs the targets' float32 planes");
-    if (loss == ROPE_LOSS_TSWEEP && !c->targets_t32 && !c->targets_ts) ARG_FAIL(c, "rope_eval_targets: this loss needs float32 planes");
-    for (int i = 0; i < R; i++)
-        if (frame_of[i] < 0 || frame_of[i] >= c->n_targets) ARG_FAIL(c, "rope_eval_targets: frame index outside the resident targets");
-    FrameParams fp = c->fp;
-    double n_pix = (double)fp.W * fp.H;
-    if (loss == ROPE_LOSS_LOOKUP) {
-        if (!crop) ARG_FAIL(c, "rope_eval_targets: lookup loss needs a crop");
-        if (crop[0] < 0 || crop[1] >= fp.H || crop[0] > crop[1] || crop[2] < 0 || crop[3] >= fp.W || crop[2] > crop[3]) ARG_FAIL(c, "rope_eval_targets: crop outside the image");
-        fp.r0 = crop[0]; fp.r1 = crop[1]; fp.c0 = crop[2]; fp.c1 = crop[3];
-        n_pix = (double)(crop[1] - crop[0] + 1) * (double)(crop[3] - crop[2] + 1);
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_target_totals(c, loss, fp);
-    if (rc) return rc;
-    for (int lo = 0; lo < R; lo += MAX_ROWS) {
-        const int n = std::min(MAX_ROWS, R - lo);
-        rc = upload_candidates(c, cand + 6 * (size_t)lo, n, true, frame_of + lo);
-        if (rc) return rc;
-        rc = enqueue_eval(c, n_render, loss, fp, n_pix, nullptr, EVAL_TARGETS);
-        // the rows are scored against the frames' targets: nothing here is a result of the single-target calls
-        c->cand_valid = c->results_valid = false;
-        if (rc) return rc;
-        if (!c->err_on_host) HIP_TRY(c, hipMemcpyAsync(c->h_stage, c->d_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::memcpy(err_out + lo, c->err_on_host ? c->h_err.get() : c->h_stage.get(), (size_t)n * sizeof(double));
-    }
-    return ROPE_OK;
-}
-
-extern "C" int rope_lookup_score_targets(rope_ctx *c, int32_t *best_idx, double *best_score, double *scores_out)
-{
-    if (!c) return ROPE_E_ARG;
-    if (c->table_C < 1) ARG_FAIL(c, "rope_lookup_score_targets: no table built");
-    if (c->n_targets < 1 || !c->targets_t32) ARG_FAIL(c, "rope_lookup_score_targets: needs targets with their float32 planes (rope_set_targets)");
-    if (!best_idx) ARG_FAIL(c, "rope_lookup_score_targets: null pointer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    FrameParams fp = c->fp;
-    fp.r0 = c->table_crop[0]; fp.r1 = c->table_crop[1]; fp.c0 = c->table_crop[2]; fp.c1 = c->table_crop[3];
-    const size_t crop_px = table_crop_words(fp), N = (size_t)c->n_targets;     // crop rows padded to whole groups of four samples
-    if (int rc = sync_grow(c, c->d_tg_t32c, N * crop_px)) return rc;
-    if (int rc = sync_grow(c, c->d_tg_scores, N * c->table_C)) return rc;
-    HIP_TRY(c, launch_table_score_frames(c->stream, fp, c->d_tcount, c->d_toff, c->d_tgoff, c->d_tgval, c->table_C, c->d_ft32, c->n_targets, c->d_tg_t32c, c->d_tg_ltotal,
-                                         c->d_tg_scores, c->d_tg_best));
-    std::vector<double> best(2 * N);
-    HIP_TRY(c, hipMemcpyAsync(best.data(), c->d_tg_best, 2 * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (scores_out) HIP_TRY(c, hipMemcpyAsync(scores_out, c->d_tg_scores, N * c->table_C * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t f = 0; f < N; f++) {
-        best_idx[f] = (int32_t)best[2 * f + 1];
-        if (best_score) best_score[f] = best[2 * f];
-    }
-    return ROPE_OK;
-}
 
 extern "C" int rope_debug_mvp(rope_ctx *c, float *mvp_out, int C, int n_render)
 {
@@ -2251,12 +1162,12 @@ extern "C" int rope_profile_eval(rope_ctx *c, int n_render, int loss, const int3
     int rc = check_eval_args(c, n_render, loss, crop, fp, n_pix);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    rc = ensure_empty(c, loss, fp);
+    rc = ensure_totals(c, c->single, c->single_empty, loss, fp);
     if (rc) return rc;
     std::vector<hipEvent_t> ev(5 * (size_t)reps);
     for (auto &e : ev) HIP_TRY(c, hipEventCreate(&e));
     for (int r = 0; r < reps; r++) {
-        rc = enqueue_eval(c, n_render, loss, fp, n_pix, &ev[5 * (size_t)r]);
+        rc = enqueue_eval(c, n_render, loss, fp, n_pix, single_planes(c, loss), EVAL_SINGLE, &ev[5 * (size_t)r]);
         if (rc) break;
     }
     if (!rc) {

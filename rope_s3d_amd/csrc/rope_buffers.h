@@ -1,4 +1,4 @@
-// rope_buffers.h — the owning buffer types of the context (rope_abi.hip): a pointer and the number of elements allocated behind
+// rope_buffers.h — the owning buffer types of the context (rope_ctx.h): a pointer and the number of elements allocated behind
 // it, kept together.  No runtime header: the four functions below are defined by whoever links this — rope_abi.hip over
 // hipMalloc / hipFree / hipHostMalloc / hipHostFree, tests/buffers_main.cpp over malloc.  A buffer knows nothing of streams or of
 // the context: it never waits, and whoever may have work in flight on a block waits before growing it.

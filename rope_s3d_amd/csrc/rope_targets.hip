@@ -1,7 +1,7 @@
 // rope_targets.hip — the segmentation path's targets built on the device, for gfx950: instance masks that are already in HBM
 // (the segmenter's (K, H, W) planes) and the frame's depth -> the packed plane, the lookup plane, the TensorSweep plane and the
 // per-link flags of rope_set_targets, with no trip through host memory.  Per frame exactly what the host function
-// rope_prepare_segmented (rope_abi.hip) computes at f == 1:
+// rope_prepare_segmented (rope_hostprep.cpp) computes at f == 1:
 //   merge      any |= m_k;  bits |= 1 << link_of[k] (link_of[k] >= 0);  look |= m_k (0 <= link_of[k] < n_lookup_links)
 //   body       erode7(dilate8(any)), body_look = erode7(dilate8(look)): cv2's box kernels with their default anchors (the dilate
 //              window of x is x-4..x+3, the erode window x-3..x+3, in both axes) and borders that never win: outside the image is
@@ -31,7 +31,7 @@ constexpr int TG_IN_PITCH = TG_IN_W + 3, TG_DIL_PITCH = TG_DIL_W + 2;
 static_assert(TG_TW == 64, "one wave per tile row: the flag counts are ballots over a row");
 static_assert((TG_TW * TG_TH) % TG_THREADS == 0, "whole rows per pass of the workgroup");
 
-// depth in metres -> Q32 with the rounding and clipping of rope_pack_target (q32_of_depth, rope_abi.hip): round half to even,
+// depth in metres -> Q32 with the rounding and clipping of rope_pack_target (q32_of_depth, rope_hostprep.cpp): round half to even,
 // NaN, inf, zero and negatives are "no depth", clipped to 2^39 - 1.  rint is exact where the host's 2^52 trick is, and beyond
 // 2^52 both end at the clip.
 __device__ inline uint64_t q32_of_depth_dev(double d)

@@ -155,3 +155,111 @@ def test_created_and_destroyed_contexts_give_their_memory_back():
     e = use()
     d, i = e.render(q[0], 6)
     assert (i != 255).any() and d.max() > 0
+
+
+def test_the_kinds_of_target_in_turn_on_one_context():
+    """A single target, a resident set, camera-pose frames, two staged sets (the first without float32 planes) and the single
+    target's TensorSweep plane, one after the other on ONE context: every answer is byte for byte what a fresh engine gives
+    that has only ever seen that kind.  80x60, 64 candidates (a 4x4x4 grid), 3 target frames, 2 camera-pose frames x 2 views."""
+    import re
+    from rope_s3d_amd.constants import DEFAULT_CAMERA_POSE
+    rb = helpers.robot()
+    intr, PV0 = helpers.camera('640_480_color', ds=8)
+
+    def make():
+        f = eng.Engine(0)
+        f.set_robot(rb)
+        f.set_camera(PV0, intr.width, intr.height, ZNEAR, ZFAR)
+        return f
+
+    def fresh(setup, *calls):
+        f = make()
+        setup(f)
+        out = [call(f) for call in calls]
+        f.close()
+        return out
+
+    def same(got, want):                                                            # arrays, scalars, None, or tuples of them
+        if isinstance(got, tuple):
+            return len(got) == len(want) and all(same(g, w) for g, w in zip(got, want))
+        if isinstance(got, np.ndarray):
+            return _same(got, want)
+        return got == want or (got != got and want != want)
+
+    e = make()
+    cand = helpers.slu_grid(rb.joint_limits, 4)
+    grid = helpers.slu_grid(rb.joint_limits, 3)
+    assert len(cand) == 64
+    crop, frame_of = (8, 51, 12, 71), (np.arange(64) % 3).astype(np.int32)
+    frames = []
+    for r in _poses(6, 31, joints=5):
+        depth, ids = e.render(r, 6)
+        tq, t32, flags, tgt, _, _ = helpers.synthetic_target(depth, ids)
+        full = np.ascontiguousarray(tgt, np.float32)
+        frames.append((tq, t32, flags, np.where(full > 0, full + np.float32(0.125), np.float32(0)).astype(np.float32)))
+    assert all((f[1] != f[3]).any() for f in frames)                                # the TensorSweep planes are planes of their own
+
+    def planes(idx, t32=True, ts=False):
+        return (np.stack([frames[i][0] for i in idx]), np.stack([frames[i][1] for i in idx]) if t32 else None,
+                np.stack([frames[i][2] for i in idx]), np.stack([frames[i][3] for i in idx]) if ts else None)
+
+    def ev(loss, cr=None):
+        return lambda f: tuple(x for x in f.eval(cand, 6, loss, cr) if x is not None)   # errors, argmin, its error
+
+    def evt(loss, cr=None):
+        return lambda f: f.eval_targets(cand, frame_of, 6, loss, cr)
+
+    def refused(call, message):
+        with pytest.raises(eng.EngineError, match=re.escape(f'failed (-1): {message}')):
+            call(e)
+
+    tq0, t320, flags0, ts0 = frames[0]
+    single = lambda f: f.set_target(tq0, t320, flags0)                              # noqa: E731
+    # 1. the single target
+    single(e)
+    calls1 = [ev(eng.LOSS_FULL), ev(eng.LOSS_LOOKUP, crop), ev(eng.LOSS_TSWEEP)]
+    want1 = fresh(single, *calls1)
+    assert same(tuple(c(e) for c in calls1), tuple(want1)) and np.isfinite(want1[0][0]).all()
+    # 2. a resident set with its float32 planes, and the stored table against it
+    set2 = lambda f: f.set_targets(*planes([1, 2, 3]))                              # noqa: E731
+    table = lambda f: (f.lookup_build(grid, 3, crop), f.lookup_score_targets(True))[1]   # noqa: E731
+    calls2 = [evt(eng.LOSS_FULL), evt(eng.LOSS_LOOKUP, crop), evt(eng.LOSS_TSWEEP), table]
+    set2(e)
+    assert same(tuple(c(e) for c in calls2), tuple(fresh(set2, *calls2)))
+    # 3. camera-pose frames in the same planes: the resident set is gone
+    qs = _poses(2, 32, joints=5)
+    views = np.stack([PV0, helpers.camera('640_480_color', ds=8, pose=np.array(DEFAULT_CAMERA_POSE, float) + .05)[1]])
+    set3 = lambda f: f.set_frames(qs, *planes([4, 5])[:2])                          # noqa: E731
+    calls3 = [lambda f: f.eval_views(views, 6, eng.LOSS_DEPTH), lambda f: f.eval_views(views, 6, eng.LOSS_TSWEEP)]
+    set3(e)
+    assert same(tuple(c(e) for c in calls3), tuple(fresh(set3, *calls3)))
+    refused(evt(eng.LOSS_DEPTH), 'rope_eval_targets: no targets set (rope_set_targets)')
+    # 4. a staged set WITHOUT float32 planes becomes the resident one: the planes of step 3 are still in the buffers, and not read
+    def staged(idx, t32, ts):
+        def setup(f):
+            tq, a, flags, b = planes(idx, t32, ts)
+            f.stage_targets(tq, a, flags, b)
+            f.commit_targets()
+        return setup
+    staged([3, 0, 5], False, False)(e)
+    refused(evt(eng.LOSS_LOOKUP, crop), "rope_eval_targets: this loss needs the targets' float32 planes")
+    refused(evt(eng.LOSS_TSWEEP), 'rope_eval_targets: this loss needs float32 planes')
+    assert same(evt(eng.LOSS_DEPTH)(e), fresh(lambda f: f.set_targets(*planes([3, 0, 5], False)), evt(eng.LOSS_DEPTH))[0])
+    # 5. a staged set with both kinds of float32 plane: TensorSweep reads its own
+    staged([2, 4, 1], True, True)(e)
+    calls5 = [evt(eng.LOSS_LOOKUP, crop), evt(eng.LOSS_TSWEEP), evt(eng.LOSS_FULL)]
+    got5 = tuple(c(e) for c in calls5)
+    assert same(got5, tuple(fresh(lambda f: f.set_targets(*planes([2, 4, 1], True, True)), *calls5)))
+    tq5, t325, flags5, ts5 = planes([2, 4, 1], True, True)
+    as_t32, plain = (fresh(lambda f: f.set_targets(tq5, p, flags5), evt(eng.LOSS_TSWEEP))[0] for p in (ts5, t325))
+    assert same(got5[1], as_t32) and not same(got5[1], plain)
+    # 6. the single target's TensorSweep plane, which the next rope_set_target takes away again
+    e.set_target_tsweep(ts0)
+    with_ts = ev(eng.LOSS_TSWEEP)(e)
+    assert same(with_ts, fresh(lambda f: (single(f), f.set_target_tsweep(ts0)), ev(eng.LOSS_TSWEEP))[0]) and not same(with_ts, want1[2])
+    assert same(ev(eng.LOSS_LOOKUP, crop)(e), want1[1])                             # that plane is TensorSweep's alone
+    single(e)
+    assert same(ev(eng.LOSS_TSWEEP)(e), want1[2])
+    # 7. the single target as in step 1: it never depended on the sets
+    assert same(tuple(c(e) for c in calls1), tuple(want1))
+    e.close()
