@@ -652,6 +652,54 @@ int rope_shade_frames(const float *depth_dev, const uint8_t *ids_dev, int N, int
                       const rope_shade_params *params, const uint8_t *bg_dev, int n_bg, uint32_t frame0, uint64_t seed, uint8_t *bgr_dev,
                       float *depth_out_dev, void *stream);
 
+/* ---- Pose refinement (rope_s3d_amd/prediction/refinement.py, csrc/rope_refine.hip).  Same conventions: no context, plain device
+ * pointers, the HIP stream to launch on, nothing synchronised, allocated or copied in the call.  The reference has nothing like it:
+ * its answer is the last lattice point of a search.  tests/refine_ref.py restates the text below in numpy.
+ *
+ * rope_pose_normal_equations: per frame, the Gauss-Newton normal equations of the depth residual between the render at a pose and
+ * the frame, with respect to the joint angles.
+ *   render_depth_dev, render_ids_dev   n_frames planes H x W: float32 metres (4-byte aligned) and link ids (255 = background), as
+ *                        rope_render_batch_device writes them at the pose, DEVICE
+ *   frame_depth_dev      n_frames planes H x W float32 metres: the frames, DEVICE, 4-byte aligned
+ *   n_links              1 .. ROPE_MAX_LINKS: ids below it are links
+ *   fx, fy, cx, cy       the camera's terms as float32, as rope_shade_frames takes them; finite, fx and fy not 0
+ *   joints_dev           n_frames x n_joints x 6 doubles, DEVICE, 8-byte aligned: per joint its unit axis a and a point o on the axis,
+ *                        at the frame's pose, in the camera axes of P below (x right, y down, z forward, metres)
+ *   n_joints             1 .. 6.  Link l is moved by the joints j < l; link 0 is the base and moves with none
+ *   clip_m               finite, > 0: the truncation of the residual, metres
+ *   out_dev              n_frames x ROPE_NEQ_WORDS doubles out, DEVICE, 8-byte aligned; written completely
+ *   work_dev             rope_pose_normal_workspace(n_frames, H, W) bytes of scratch, DEVICE, 8-byte aligned
+ * Everything is float64 with ONE correctly rounded IEEE operation per written operation, in the order written; R, T, fx .. cy and
+ * clip_m are widened first.  z = R[y][x], id = ids[y][x], T = depth[y][x]; dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z; u x v has the
+ * components u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x.
+ *   1. P(x, y) = (kx(x) z, ky(y) z, z) with kx(x) = (x - cx) / fx, ky(y) = (y - cy) / fy: rope_shade_frames' points, in float64.
+ *   2. dX = P(x + 1, y) - P(x, y) if x + 1 < W and ids[y][x + 1] == id; else P(x, y) - P(x - 1, y) if x > 0 and ids[y][x - 1] == id;
+ *      else 0.  dY likewise along y.  n = dX x dY.  The pixel has NO NORMAL when a component of n is not finite or all three are 0.
+ *   3. RENDERED: id < n_links.  VALID: T finite and 0 < T < 128 (compared as float32).  BOTH: rendered and valid.  r = z - T.
+ *      MOVING: 1 <= id <= n_joints.
+ *   4. INLIER: both, moving, |r| <= clip, a normal, and with nn = dot(n, n), nP = dot(n, P), PP = dot(P, P):
+ *      nP nP >= 0.01 (nn PP) and nP != 0 — the surface is seen at more than 0.1 of head-on (a design constant, not a measurement).
+ *   5. For an inlier on link l = id and joint j < min(l, n_joints), a and o the joint's:
+ *      J_j = (z dot(n, a x (P - o))) / nP;  J_j = 0 for every other j < 6.  (Exact for a plane turning about the axis: the
+ *      normal's own rotation cancels at first order.)
+ * Per frame:  [0] BOTH pixels   [1] sum over both of (r r <= clip clip ? r r : clip clip) (a NaN residual counts as the clip)
+ *   [2] inliers   [3] sum over inliers of r r   [4 + j] sum of J_j r   [10 ..30] sum of J_j J_i for j <= i, row by row
+ *   (00 01 .. 05 11 12 .. 55)   [31] 0.  The counts are doubles too (exact: at most 2^24).
+ * Determinism is part of the contract: no floating-point atomic is used; a workgroup covers pixels that depend on H W alone and
+ * adds them in a fixed order, its one partial goes to work_dev, and a second kernel adds a frame's partials in index order.  The
+ * same planes give the same bytes from run to run, and whether the frames come in one call or in several.  The ORDER of the
+ * summation is not part of the contract: a restatement that adds in another order differs by at most the rounding of a sum of
+ * that many terms.
+ * ROPE_E_ARG, with nothing enqueued, for n_frames < 1, H < 1, W < 1, H W > 2^24, 2^24 workgroups or more (n_frames x
+ * ceil(H W / 2048)), n_links outside 1 .. ROPE_MAX_LINKS, n_joints outside 1 .. 6, a clip_m that is not finite or not positive,
+ * camera terms that are not finite or a zero fx or fy, a null or misaligned pointer.  ROPE_E_HIP when the runtime refuses a launch.
+ * rope_pose_normal_workspace (host only): the bytes of work_dev for such a call; 0 for a shape the call refuses. */
+#define ROPE_NEQ_WORDS 32
+int rope_pose_normal_equations(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames, int H,
+                               int W, int n_links, float fx, float fy, float cx, float cy, const double *joints_dev, int n_joints, float clip_m,
+                               double *out_dev, double *work_dev, void *stream);
+size_t rope_pose_normal_workspace(int n_frames, int H, int W);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Predict every frame of a dataset (same command line as the reference's predict_dataset.py:58-64).
 
-    python predict_dataset.py <dataset> [-angs SLU]
+    python predict_dataset.py <dataset> [-angs SLU] [-refine [-sigma FILE.npy]]
     python -m torch.distributed.run --nproc-per-node N ... predict_dataset.py <dataset>    # frames shard over N GPUs
 
 Frames are independent, so rank r predicts a contiguous block of frames on its own GPU and
@@ -69,6 +69,13 @@ def run(args):
         kwargs['lookup_divisions'] = int(args.lookup_divisions)
     if getattr(args, 'device_targets', False):
         kwargs['device_targets'] = True
+    refine = bool(getattr(args, 'refine', False))
+    if getattr(args, 'sigma', None) and not refine:
+        raise SystemExit("-sigma needs -refine: the sigmas come out of the refinement's normal equations")
+    if refine:
+        if int(getattr(args, 'predictors', 1) or 1) > 1:
+            raise SystemExit("-refine runs with one Predictor (-predictors 1)")
+        kwargs['refine'] = True                               # Gauss-Newton polish of every prediction (prediction/refinement.py)
     am = Predictor(ds_factor=args.ds_factor, camera_pose=ds.camera_pose[0], preview=False, base_intrin=ds.intrinsics,
                    do_angles=args.angs, model_ds=args.dataset, device=gpu, **kwargs)
     # Frames are independent (predict_dataset.py:43-44 is a plain loop; fresh state per frame, predict.py:144-148): ONE Predictor
@@ -86,6 +93,7 @@ def run(args):
 
     lo, hi = shard_range(ds.length, rank, world)
     out = np.zeros((hi - lo, 6))
+    sig = np.full((hi - lo, 6), np.nan)                       # -refine: the formal sigma of every angle (inf: not seen, nan: not refined)
     t_ready = time.perf_counter()
     # The reference reads ~200 frames at a time (predict_dataset.py:27-41).  Here a chunk is several lockstep batches, so that inside
     # run_many the preparation and upload of one batch hide behind the stages of the one before; bounded by the bytes of raw
@@ -115,12 +123,18 @@ def run(args):
             out[start - lo:end - lo] = pool.run_many(og_imgs, dms, cam_poses)
         else:
             out[start - lo:end - lo] = am.run_many(og_imgs, dms, cam_poses, batch=getattr(args, 'batch', None))
+            if refine:
+                sig[start - lo:end - lo] = am.last_refinement.sigma
     reader.shutdown()
     if rank == 0 and os.environ.get('ROPE_TIMING'):
         t_end = time.perf_counter()
         print(f"rank 0: set-up {t_ready - t_begin:.2f} s (data set, segmenter, Predictor, lookup table), {hi - lo} frames in {t_end - t_ready:.2f} s = "
               f"{(hi - lo) / max(t_end - t_ready, 1e-9):.1f} frames/s")
     full = gather_rows(out, ds.length, device=device, single_rank_too=use_dist)
+    if getattr(args, 'sigma', None):
+        sig_full = gather_rows(sig, ds.length, device=device, single_rank_too=use_dist)
+        if rank == 0:
+            np.save(args.sigma, sig_full)
     if rank == 0:
         if use_dist:
             print(f"{ds.length} frames of {world} rank(s) gathered over {os.environ.get('ROPE_DIST_BACKEND', 'nccl')}")
@@ -150,5 +164,7 @@ if __name__ == "__main__":
     parser.add_argument('-device_targets', action='store_true',
                         help="With -segmenter maskrcnn: the network's masks stay on the GPU and the targets are built there "
                              "(Predictor(device_targets=True)); other segmenters do not offer that and run as without the flag.")
+    parser.add_argument('-refine', action='store_true', help="Polish every prediction with Gauss-Newton steps on the depth residual (Predictor(refine=True)).")
+    parser.add_argument('-sigma', type=str, default=None, help="With -refine: save the (n, 6) formal sigmas of the angles (rad; inf = not seen, nan = not refined) to this .npy.")
     parser.add_argument('-weights', type=str, default=None, help="weights for -segmenter maskrcnn: the reference's trained Keras .h5 or a torch state_dict (random weights otherwise).")
     run(parser.parse_args())

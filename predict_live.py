@@ -89,8 +89,12 @@ class Live:
     def displayState(self):
         if self.state != self._last_state:
             self._last_state = self.state
+            sure = ''
+            polished = getattr(self.pred, 'last_refinement', None)
+            if polished is not None and len(polished):          # -refine: how sure the newest prediction is; the verdict does not read it
+                sure = f", largest formal sigma of the refined joints {float(np.nanmax(polished.sigma[-1])):.2e} rad"
             print(f"frame {len(self.running_claims)}: {'OUT OF RANGE' if self.state else 'in range'} "
-                  f"(tool deviation {float(np.ravel(self.diff)[0]) * 1000:.1f} mm)")
+                  f"(tool deviation {float(np.ravel(self.diff)[0]) * 1000:.1f} mm{sure})")
 
 
 if __name__ == "__main__":
@@ -102,17 +106,19 @@ if __name__ == "__main__":
     parser.add_argument('-angs', type=str, default='SLU')
     parser.add_argument('-ds_factor', type=int, default=8)
     parser.add_argument('-frames', type=int, default=None)
+    parser.add_argument('-refine', action='store_true', help="polish every prediction (Predictor(refine=True)) and print its largest formal sigma beside the deviation")
     args = parser.parse_args()
+    extra = {'refine': True} if args.refine else {}
     if args.replay:
         ds = Dataset(args.replay)
         cam = DatasetCamera(ds)
         kw = {'color_dict': ds.attrs['color_dict']} if ds.attrs.get('synthetic') else {}
-        a = Live(str(ds.intrinsics), ds, args.angs, args.ds_factor, camera=cam, link=cam.claims(), **kw)
+        a = Live(str(ds.intrinsics), ds, args.angs, args.ds_factor, camera=cam, link=cam.claims(), **kw, **extra)
     elif args.raw:
         cam = RawRecordingCamera(args.raw)
-        a = Live(args.intrin, args.dataset, args.angs, args.ds_factor, camera=cam, link=cam.claims() if cam.angles is not None else None)
+        a = Live(args.intrin, args.dataset, args.angs, args.ds_factor, camera=cam, link=cam.claims() if cam.angles is not None else None, **extra)
     else:
-        a = Live(args.intrin, args.dataset, args.angs, args.ds_factor)
+        a = Live(args.intrin, args.dataset, args.angs, args.ds_factor, **extra)
     n = a.run(args.frames)
     a.stop()
     print(f"{n} frames, saved to {a.save_to}")

@@ -16,6 +16,7 @@ LOSS_DEPTH, LOSS_FULL, LOSS_LOOKUP, LOSS_TSWEEP, LOSS_CAMFULL = 0, 1, 2, 3, 4
 SUM_WORDS = 23
 AGREE_WORDS = 28                 # ROPE_AGREE_WORDS (include/rope_s3d.h): the words rope_frame_agreement writes per frame
 SHADE_MAX_NOISE_Q = 1023         # ROPE_SHADE_MAX_NOISE_Q
+NEQ_WORDS = 32                   # ROPE_NEQ_WORDS: the doubles rope_pose_normal_equations writes per frame
 # rope_shade_params (include/rope_s3d.h), 64 bytes a record
 SHADE_DTYPE = np.dtype([('light', '<f4', 3), ('ambient', '<f4'), ('gain', '<f4', 3), ('bg_depth', '<f4'), ('noise_q', '<i4'), ('bg_index', '<i4'),
                         ('albedo', 'u1', (6, 3)), ('bg_colour', 'u1', 3), ('reserved', 'u1', 3)])
@@ -34,7 +35,7 @@ ABI_SYMBOLS = (
     'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets',
     'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes', 'rope_frame_agreement',
     'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align',
-    'rope_shade_frames')
+    'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -155,6 +156,10 @@ def load_library(path: str = None):
     lib.rope_depth_align.argtypes = [vp, i32, i32, i32, vp, vp, vp, dbl, i32, i32, vp, vp, vp]
     lib.rope_shade_frames.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, i32, C.c_uint32,
                                       C.c_uint64, vp, vp, vp]
+    lib.rope_pose_normal_equations.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, i32, C.c_float,
+                                               vp, vp, vp]
+    lib.rope_pose_normal_workspace.argtypes = [i32, i32, i32]
+    lib.rope_pose_normal_workspace.restype = C.c_size_t
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_eval_views.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.rope_set_target_tsweep.argtypes = [vp, vp]
@@ -600,6 +605,49 @@ class Engine:
                 raise EngineError(f"rope_frame_agreement failed ({rc})")
             return sums.cpu().numpy().view(np.uint64)
 
+    def pose_normal_equations(self, render_depth, render_ids, frame_depth, joints, n_links: int, clip: float, intr) -> np.ndarray:
+        """rope_pose_normal_equations: N renders at N poses against the N depth frames -> (N, 32) float64, per frame [0] the pixels
+        both rendered and measured, [1] the sum over them of min(r^2, clip^2) with r = render - frame, [2] the inliers (on a moving
+        link, |r| <= clip, a normal, not grazing), [3] their sum of r^2, [4..9] J^T r, [10..30] the upper triangle of J^T J row by
+        row, [31] 0; J is the derivative of the rendered depth with respect to the joint angles (include/rope_s3d.h).
+        render_depth / frame_depth (N, H, W) float32 and render_ids (N, H, W) uint8 are torch tensors on this engine's device
+        (render_batch_device's); joints (N, n_joints, 6) float64, a numpy array or a tensor: unit axis and a point on the axis per
+        joint, in camera axes (x right, y down, z forward); intr: (fx, fy, cx, cy).  The kernels run on torch's current stream and
+        the sums are waited for here.  The same planes give the same bytes from run to run and however a batch is cut."""
+        import torch
+        for name, t, dt in (('render_depth', render_depth, torch.float32), ('render_ids', render_ids, torch.uint8),
+                            ('frame_depth', frame_depth, torch.float32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
+            if t.device.type != 'cuda' or t.device.index != self.device:
+                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
+            if t.shape != render_depth.shape:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {tuple(render_depth.shape)}")
+        N, H, W = render_depth.shape
+        dev = render_depth.device
+        if not isinstance(joints, torch.Tensor):
+            joints = torch.from_numpy(np.ascontiguousarray(joints, np.float64))
+        if joints.dtype != torch.float64 or joints.dim() != 3 or joints.shape[0] != N or joints.shape[2] != 6:
+            raise ValueError(f"joints: ({N}, n_joints, 6) float64 — axis and a point on it per joint, got {tuple(joints.shape)} {joints.dtype}")
+        n_joints = int(joints.shape[1])
+        if N == 0:
+            return np.zeros((0, NEQ_WORDS), np.float64)
+        fx, fy, cx, cy = (float(v) for v in intr)
+        with torch.cuda.device(dev):
+            joints = joints.to(dev).contiguous()
+            out = torch.empty((N, NEQ_WORDS), dtype=torch.float64, device=dev)
+            work = torch.empty(max(1, self._lib.rope_pose_normal_workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
+            rc = self._lib.rope_pose_normal_equations(C.c_void_p(render_depth.data_ptr()), C.c_void_p(render_ids.data_ptr()),
+                                                      C.c_void_p(frame_depth.data_ptr()), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
+                                                      C.c_void_p(joints.data_ptr()), n_joints, float(clip), C.c_void_p(out.data_ptr()),
+                                                      C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if rc == -1:
+                raise ValueError(f"rope_pose_normal_equations refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), n_links "
+                                 f"{n_links} (1 .. 6), {n_joints} joints (1 .. 6), clip {clip} (finite, positive), intrinsics {(fx, fy, cx, cy)}")
+            if rc:
+                raise EngineError(f"rope_pose_normal_equations failed ({rc})")
+            return out.cpu().numpy()
+
     def debug_targets(self, want_tsweep: bool = False):
         """rope_debug_targets: the resident set back on the host -> (tq (N,H,W) uint64, t32 (N,H,W) float32, tsweep planes or None,
         flags (N,8) uint8), for tests."""
@@ -609,6 +657,13 @@ class Engine:
         flags = np.empty((n, 8), np.uint8)
         self._check(self._lib.rope_debug_targets(self._ctx, _p(tq), _p(t32), _p(ts), _p(flags)), 'rope_debug_targets')
         return tq, t32, ts, flags
+
+    def resident_depth(self) -> np.ndarray:
+        """The whole-depth float32 planes of the resident set (the ones ROPE_LOSS_TSWEEP reads; a set staged with want_tsweep has
+        them) -> (N, H, W) float32 on the host: rope_debug_targets asked for that one plane stack and nothing else."""
+        ts = np.empty((self.n_targets, self.H, self.W), np.float32)
+        self._check(self._lib.rope_debug_targets(self._ctx, None, None, _p(ts), None), 'rope_debug_targets')
+        return ts
 
     def eval_targets(self, cand, frame_of, n_render: int, loss: int, crop=None) -> np.ndarray:
         """Row i of `cand` scored against the resident target frame_of[i] -> errors (R,)."""

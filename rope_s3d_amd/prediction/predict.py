@@ -149,7 +149,8 @@ class Predictor:
                  lookup_divisions=None,
                  lookup_table_budget: int = 32 << 30,
                  reference_table_aliasing: bool = False,
-                 device_targets: bool = False):
+                 device_targets: bool = False,
+                 refine: bool = False):
         """Reference parameters as in predict.py:38-70.  Extra keyword-only arguments:
 
         device            HIP device ordinal of the engine context
@@ -169,8 +170,16 @@ class Predictor:
                           the instance masks stay on the GPU): the targets are built there as well (rope_stage_targets_segmented)
                           instead of on the host from a copy of the masks.  Same planes, bit for bit, hence the same angles.
                           Without such a segmenter, and in run() / prepare(), the flag changes nothing.
+        refine            polish the stages' answer with a few Gauss-Newton steps on the depth residual against the frame's depth at
+                          the working resolution (prediction/refinement.py: PoseRefiner over do_angles), in run, run_batch and
+                          run_many; the RefineResult of the last call — one row per frame, with the formal sigma of every angle — is
+                          left in `last_refinement`.  Off by default: the stages, their trace and their angles are untouched.
+                          On the segmentation path the polish sees the body-masked depth (PreparedTarget.tgt_depth); with
+                          device_targets it sees the reduced depth before masking, since the mask never leaves the device — so
+                          there the two run_many paths give the same stage angles but may polish them differently.
         """
         self.device_targets = bool(device_targets)
+        self.refine, self.last_refinement, self._refiner = bool(refine), None, None
         self.ds_factor, self.preview = ds_factor, preview
         if preview:                       # headless: frames go to .viz.frame and, with save_to, an uncompressed AVI
             from .viz import ProjectionViz
@@ -422,6 +431,17 @@ class Predictor:
             return self._loadSynthetic(target_color, target_depth)
         return self._segmentLoad(target_color, target_depth)
 
+    def _polish(self, angles: np.ndarray, depths) -> np.ndarray:
+        """refine=True: the stages' angles (N, 6) polished against the frames' depth (N, H, W) at the working resolution ->
+        (N, 6); the RefineResult goes to last_refinement."""
+        from .refinement import PoseRefiner
+        if self._refiner is None:
+            self._refiner = PoseRefiner(self.renderer, self.camera_pose, self.intrinsics, self.do_angles)
+        elif np.any(self._refiner.camera_pose != self.camera_pose):
+            self._refiner.setCameraPose(self.camera_pose)
+        self.last_refinement = self._refiner.refine(np.asarray(angles, np.float64).reshape(-1, 6), depths)
+        return self.last_refinement.angles
+
     def run_batch(self, prepared: list, camera_pose=None) -> np.ndarray:
         """B prepared frames (Predictor.prepare) under ONE camera pose through the stage list in lockstep -> (B, 6): every step of a
         stage is one device batch holding the rows of all frames, each row scored against its own frame's target
@@ -432,14 +452,19 @@ class Predictor:
         self._setStages()
         if not self._batch_ok() or len(prepared) == 0:
             out = np.zeros((len(prepared), 6))
-            self.traces = []
+            self.traces, polished = [], []
             for i, prep in enumerate(prepared):
                 out[i] = self.run(None, None, prepared=prep)
                 self.traces.append(self.trace)
+                polished.append(self.last_refinement)
+            if self.refine and polished:
+                from .refinement import RefineResult
+                self.last_refinement = RefineResult.concatenate(polished)
             return out
-        ts = np.stack([np.asarray(p.tgt_depth, np.float32) for p in prepared]) if self._has_tsweep() else None
-        return self._run_planes(np.stack([p.tq for p in prepared]), np.stack([p.lookup_f32 for p in prepared]),
-                                np.stack([p.flags for p in prepared]), ts)
+        ts = np.stack([np.asarray(p.tgt_depth, np.float32) for p in prepared]) if self._has_tsweep() or self.refine else None
+        angles = self._run_planes(np.stack([p.tq for p in prepared]), np.stack([p.lookup_f32 for p in prepared]),
+                                  np.stack([p.flags for p in prepared]), ts if self._has_tsweep() else None)
+        return self._polish(angles, ts) if self.refine else angles
 
     def _plane_set(self, which: int, b: int, H: int, W: int, want_ts: bool):
         """One of the two sets of stacked target planes for `b` frames (page-locked host memory, kept between calls)."""
@@ -527,6 +552,7 @@ class Predictor:
         from concurrent.futures import ThreadPoolExecutor
         from ..engine import pinned_empty
         from ..utils import cpu_budget
+        from .refinement import RefineResult
         n = len(target_colors)
         out = np.zeros((n, 6))
         groups = self._groups(n, camera_poses, batch)
@@ -538,6 +564,7 @@ class Predictor:
         link_of_class = [self.link_names.index(c) if c in self.link_names else -1 for c in self.classes]
         cap = min(batch, n)
         depth_sets = [pinned_empty((cap, H, W), dtype) for _ in range(min(2, len(groups)))]   # two, taken in turn
+        polished = []
 
         def shrink(depths, colors, j0, j1, lo_):
             for j in range(j0, j1):
@@ -578,6 +605,7 @@ class Predictor:
             for k, (lo, hi) in enumerate(groups):
                 staging.result()
                 self.engine.commit_targets()            # waits for the staging kernels: group k resident, its host depth planes free again
+                kept = np.array(filled[k][0], np.float32) if self.refine else None      # the reduced depth, before its planes are written again
                 del filled[k]
                 if k + 2 < len(groups):
                     filled[k + 2] = submit(k + 2)
@@ -586,6 +614,11 @@ class Predictor:
                 if k + 1 < len(groups):
                     staging = stager.submit(stage, filled[k + 1])
                 out[lo:hi] = self._run_resident(hi - lo)
+                if self.refine:
+                    out[lo:hi] = self._polish(out[lo:hi], kept)
+                    polished.append(self.last_refinement)
+        if self.refine:
+            self.last_refinement = RefineResult.concatenate(polished)
         return out
 
     def _run_many_batched(self, target_colors, target_depths, camera_poses, batch: int) -> np.ndarray:
@@ -601,8 +634,9 @@ class Predictor:
         out = np.zeros((n, 6))
         groups = self._groups(n, camera_poses, batch)
         self._setStages()
-        want_ts = self._has_tsweep()
+        want_ts = self._has_tsweep() or self.refine      # refine: the frame's depth at the working resolution, kept beside the planes
         H, W = self.intrinsics.height, self.intrinsics.width
+        polished = []
 
         def fill(planes, k, i):
             tq, t32, fl, ts = planes
@@ -640,7 +674,7 @@ class Predictor:
                 planes, jobs = filled
                 for j in jobs:
                     j.result()
-                self.engine.stage_targets(*planes[:3], planes[3])
+                self.engine.stage_targets(*planes[:3], planes[3] if self._has_tsweep() else None)
 
             # Group k's stages run on the GPU while group k+1's planes go up on the engine's upload stream (as soon as its frames are
             # prepared: the uploader thread waits for them) and the workers write group k+2 into the host planes group k has left.
@@ -651,6 +685,7 @@ class Predictor:
             for k, (lo, hi) in enumerate(groups):
                 staging.result()
                 self.engine.commit_targets()            # group k resident; its host planes are free again
+                kept = np.array(filled[k][0][3]) if self.refine else None
                 del filled[k]
                 if k + 2 < len(groups):
                     filled[k + 2] = submit(k + 2)
@@ -659,6 +694,12 @@ class Predictor:
                 if k + 1 < len(groups):
                     staging = uploader.submit(stage, filled[k + 1])
                 out[lo:hi] = self._run_resident(hi - lo)
+                if self.refine:
+                    out[lo:hi] = self._polish(out[lo:hi], kept)
+                    polished.append(self.last_refinement)
+        if self.refine:
+            from .refinement import RefineResult
+            self.last_refinement = RefineResult.concatenate(polished)
         return out
 
     def default_batch(self) -> int:
@@ -682,18 +723,24 @@ class Predictor:
         if batch > 1 and n > 1 and self._batch_ok():
             return self._run_many_batched(target_colors, target_depths, camera_poses, batch)
         pose = (lambda i: None) if camera_poses is None else (lambda i: camera_poses[i])
+        polished = []
         if not prefetch or self.preview or n == 1:
             for i in range(n):
                 out[i] = self.run(target_colors[i], target_depths[i], pose(i))
-            return out
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=1) as pool:
-            nxt = pool.submit(self.prepare, target_colors[0], target_depths[0])
-            for i in range(n):
-                prep = nxt.result()
-                if i + 1 < n:
-                    nxt = pool.submit(self.prepare, target_colors[i + 1], target_depths[i + 1])
-                out[i] = self.run(None, None, pose(i), prepared=prep)
+                polished.append(self.last_refinement)
+        else:
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=1) as pool:
+                nxt = pool.submit(self.prepare, target_colors[0], target_depths[0])
+                for i in range(n):
+                    prep = nxt.result()
+                    if i + 1 < n:
+                        nxt = pool.submit(self.prepare, target_colors[i + 1], target_depths[i + 1])
+                    out[i] = self.run(None, None, pose(i), prepared=prep)
+                    polished.append(self.last_refinement)
+        if self.refine:
+            from .refinement import RefineResult
+            self.last_refinement = RefineResult.concatenate(polished)
         return out
 
     # ------------------------------------------------------------------ preview
@@ -736,4 +783,6 @@ class Predictor:
         self.trace = [(type(stage).__name__, trace[i].copy()) for i, stage in enumerate(self.stages)]
         for batch in evaluated:
             self._show(*batch)
+        if self.refine:
+            angles = self._polish(angles, np.asarray(self._target.tgt_depth, np.float32)[None])[0]
         return angles

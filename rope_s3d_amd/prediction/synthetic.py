@@ -15,11 +15,11 @@ from .predict import Predictor
 class SyntheticPredictor:
 
     def __init__(self, camera_pose, base_intrin, ds_factor, do_angles, noise, *, device: int = 0, seed: int = None,
-                 lookup_divisions=None):
+                 lookup_divisions=None, refine: bool = False):
         self.renderer = Renderer(camera_pose=camera_pose, camera_intrin=base_intrin, device=device)
         self.predictor = Predictor(camera_pose, ds_factor, do_angles=do_angles, base_intrin=base_intrin,
                                    color_dict=self.renderer.color_dict, device=device,
-                                   lookup_divisions=lookup_divisions)
+                                   lookup_divisions=lookup_divisions, refine=refine)
         self.urdf_reader = URDFReader()
         self.do_angles = do_angles
         self.rng = np.random.default_rng(seed)
@@ -80,8 +80,9 @@ class SyntheticPredictor:
         results = np.zeros((2, n, 6))
         results[0] = actual
         p._setStages()
-        want_ts = p._has_tsweep()
+        want_ts = p._has_tsweep() or p.refine            # refine: the whole reduced depth stays beside the targets, for the polish
         f = int(p.ds_factor)
+        polished = []
         blue_of_id, link_blue = r.blue_of_id, [int(p.color_dict[k][0]) for k in p.link_names]
         for lo in range(0, n, batch):
             hi = min(lo + batch, n)
@@ -93,5 +94,11 @@ class SyntheticPredictor:
                 p.engine.stage_targets_synthetic(depth_t, ids_t, f, blue_of_id, link_blue, LOOKUP_NUM_RENDERED, hi - lo, j0 - lo, want_ts)
             p.engine.commit_targets()
             results[1, lo:hi] = p._run_resident(hi - lo)
+            if p.refine:
+                results[1, lo:hi] = p._polish(results[1, lo:hi], p.engine.resident_depth())
+                polished.append(p.last_refinement)
             np.save(file, results)                          # one save per group
+        if p.refine:
+            from .refinement import RefineResult
+            p.last_refinement = RefineResult.concatenate(polished)
         return results
