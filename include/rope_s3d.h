@@ -700,6 +700,27 @@ int rope_pose_normal_equations(const float *render_depth_dev, const uint8_t *ren
                                double *out_dev, double *work_dev, void *stream);
 size_t rope_pose_normal_workspace(int n_frames, int H, int W);
 
+/* rope_camera_normal_equations: the same normal equations with respect to the CAMERA pose (prediction/refinement.py,
+ * CameraPoseRefiner; tests/camera_refine_ref.py restates the text below in numpy).  Every argument but two is
+ * rope_pose_normal_equations', work_dev has rope_pose_normal_workspace(n_frames, H, W) bytes, and the text above holds word for word
+ * — the arithmetic rule, steps 1 and 2, RENDERED, VALID, BOTH and r of step 3, the 32 words, determinism — with these changes:
+ *   twists_dev           n_frames x n_cols x 6 doubles, DEVICE, 8-byte aligned, in place of joints_dev: per column k its angular
+ *                        part w_k (3) and its linear part v_k (3), in the camera axes of P (x right, y down, z forward; rad and
+ *                        metres per unit of the column).  Per frame, as the joints are: one call may hold several trial cameras
+ *   n_cols               1 .. 6, in place of n_joints
+ *   3'. MOVING: id < n_links — every drawn link moves with every column, the base (link 0) too.
+ *   4'. INLIER: both, |r| <= clip, a normal, and the same test on nP nP >= 0.01 (nn PP), nP != 0.
+ *   5'. For an inlier and a column k < n_cols, a point of the surface has the velocity u = w_k x P + v_k per unit of the column, the
+ *      sum taken component by component after the cross product:
+ *        c = w_k x P;   u = (c.x + v_k.x, c.y + v_k.y, c.z + v_k.z);   J_k = (z dot(n, u)) / nP;
+ *      J_k = 0 for n_cols <= k < 6.  (The depth along the pixel's ray changes by that much: exact for a plane under the twist, the
+ *      normal's own rotation cancels at first order as in 5.)
+ * Words [4 + k] and every [10 .. 30] entry with a column >= n_cols are exactly 0.
+ * ROPE_E_ARG as above with n_cols in place of n_joints and twists_dev in place of joints_dev; out_dev is left untouched. */
+int rope_camera_normal_equations(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames, int H,
+                                 int W, int n_links, float fx, float fy, float cx, float cy, const double *twists_dev, int n_cols, float clip_m,
+                                 double *out_dev, double *work_dev, void *stream);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

@@ -5,10 +5,16 @@
 // (prediction/refinement.py).  Everything is float64 with one IEEE operation per written operation (-ffp-contract=off);
 // tests/refine_ref.py restates the contract in numpy.
 //
+// rope_camera_normal_equations is the same reduction with other columns: every frame brings up to six twists (w, v) of the camera
+// pose's parameters instead of joint axes, every drawn link moves with every column (the base, link 0, too), and a surface point P
+// has the velocity w x P + v per unit of a column.  The two entry points share one kernel body, neq_partial_body<CAMERA>; what
+// differs is the MOVING rule and the column of J, nothing in the shape or in the order of the sums.  tests/camera_refine_ref.py
+// restates that contract.
+//
 // Shape.  A workgroup takes NEQ_CHUNK consecutive pixels of one frame — pixel p = chunk NEQ_CHUNK + k NEQ_THREADS + t for thread t,
 // k = 0 .. 7, so a wave's loads are consecutive — and a thread reads its pixel's R, id and T and the R and id of its four
 // neighbours straight from memory (9 bytes a pixel from HBM, the neighbours from cache: they are other lanes' pixels or the rows
-// above and below).  The six axes of the frame are uniform per workgroup and stay in scalar registers.
+// above and below).  The six axes (or twists) of the frame are uniform per workgroup and stay in scalar registers.
 //
 // Determinism.  No floating-point atomics.  The pixels of a workgroup depend on H W alone, never on the batch or on an address.  A
 // thread adds its pixels in the order k = 0 .. 7; the 64 threads of a wave are added in a butterfly (xor 32, 16, .. 1: IEEE addition
@@ -46,8 +52,12 @@ __device__ __forceinline__ Vec3 cross(const Vec3 &a, const Vec3 &b)
 }
 __device__ __forceinline__ double dot(const Vec3 &a, const Vec3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
-// Workgroup blockIdx.x = frame * chunks + chunk.
-__global__ void __launch_bounds__(NEQ_THREADS)
+// Workgroup blockIdx.x = frame * chunks + chunk.  CAMERA = false: `joints` holds (axis, point) per joint and link l moves with the
+// joints j < l; CAMERA = true: `joints` holds (w, v) per column and every drawn link moves with every column.
+// Three waves a SIMD is what the joint columns get on their own (157 VGPRs); asked for, it keeps the twist columns there too (155
+// VGPRs; left to itself the allocator takes 170 and drops to two).
+template <bool CAMERA>
+__global__ void __launch_bounds__(NEQ_THREADS) __attribute__((amdgpu_waves_per_eu(3)))
 neq_partial_kernel(const float *__restrict__ render, const uint8_t *__restrict__ ids, const float *__restrict__ depth, int H, int W, int chunks,
                    int n_links, Camera cam, const double *__restrict__ joints, int n_joints, double clip, double *__restrict__ work)
 {
@@ -76,7 +86,11 @@ neq_partial_kernel(const float *__restrict__ render, const uint8_t *__restrict__
         const double r2 = r * r;
         acc[0] += 1.0;
         acc[1] += r2 <= clip2 ? r2 : clip2;                                             // a NaN counts as clip^2
-        if (id < 1 || id > n_joints || !(fabs(r) <= clip)) continue;                    // not MOVING, or beyond the truncation
+        if (CAMERA) {
+            if (!(fabs(r) <= clip)) continue;                                           // beyond the truncation; every drawn link is MOVING
+        } else {
+            if (id < 1 || id > n_joints || !(fabs(r) <= clip)) continue;                // not MOVING, or beyond the truncation
+        }
 
         const int y = p / W, x = p - y * W;
         const double kx = ((double)x - cam.cx) / cam.fx, ky = ((double)y - cam.cy) / cam.fy;
@@ -105,7 +119,13 @@ neq_partial_kernel(const float *__restrict__ render, const uint8_t *__restrict__
 #pragma unroll
         for (int j = 0; j < NEQ_JOINTS; j++) {
             J[j] = 0.0;
-            if (j < n_joints && j < id) {                                               // joint j moves the links behind it
+            if (CAMERA) {
+                if (j < n_joints) {                                                     // every column moves every drawn link
+                    const Vec3 w = {jf[6 * j], jf[6 * j + 1], jf[6 * j + 2]}, v = {jf[6 * j + 3], jf[6 * j + 4], jf[6 * j + 5]};
+                    const Vec3 c = cross(w, P);
+                    J[j] = (z * dot(n, Vec3{c.x + v.x, c.y + v.y, c.z + v.z})) / nP;  // the point moves by w x P + v
+                }
+            } else if (j < n_joints && j < id) {                                        // joint j moves the links behind it
                 const Vec3 a = {jf[6 * j], jf[6 * j + 1], jf[6 * j + 2]}, o = {jf[6 * j + 3], jf[6 * j + 4], jf[6 * j + 5]};
                 J[j] = (z * dot(n, cross(a, sub(P, o)))) / nP;
             }
@@ -165,6 +185,33 @@ long long neq_chunks(int n_frames, int H, int W)
     return chunks;
 }
 
+// the checks and the two launches both entry points share; `columns_dev, n_columns`: joints or twists
+template <bool CAMERA>
+int neq_launch(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames, int H, int W, int n_links,
+               float fx, float fy, float cx, float cy, const double *columns_dev, int n_columns, float clip_m, double *out_dev, double *work_dev,
+               void *stream)
+{
+    if (n_links < 1 || n_links > ROPE_MAX_LINKS || n_columns < 1 || n_columns > NEQ_JOINTS) return ROPE_E_ARG;
+    if (!isfinite(clip_m) || !(clip_m > 0.0f)) return ROPE_E_ARG;
+    if (!isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy) || fx == 0.0f || fy == 0.0f) return ROPE_E_ARG;
+    if (!render_depth_dev || !render_ids_dev || !frame_depth_dev || !columns_dev || !out_dev || !work_dev) return ROPE_E_ARG;
+    if (((uintptr_t)render_depth_dev & 3) || ((uintptr_t)frame_depth_dev & 3)) return ROPE_E_ARG;
+    if (((uintptr_t)columns_dev & 7) || ((uintptr_t)out_dev & 7) || ((uintptr_t)work_dev & 7)) return ROPE_E_ARG;
+    const long long chunks = neq_chunks(n_frames, H, W);
+    if (chunks == 0) return ROPE_E_ARG;
+
+    hipStream_t st = (hipStream_t)stream;
+    const Camera cam = {(double)fx, (double)fy, (double)cx, (double)cy};
+    hipLaunchKernelGGL(neq_partial_kernel<CAMERA>, dim3((unsigned)((long long)n_frames * chunks)), dim3(NEQ_THREADS),
+                       0, st, render_depth_dev, render_ids_dev, frame_depth_dev, H, W, (int)chunks, n_links, cam, columns_dev, n_columns,
+                       (double)clip_m, work_dev);
+    if (hipGetLastError() != hipSuccess) return ROPE_E_HIP;
+    const int per = NEQ_GATHER_THREADS / ROPE_NEQ_WORDS;
+    hipLaunchKernelGGL(neq_gather_kernel, dim3((unsigned)((n_frames + per - 1) / per)), dim3(NEQ_GATHER_THREADS), 0, st, work_dev, n_frames,
+                       (int)chunks, out_dev);
+    return hipGetLastError() == hipSuccess ? ROPE_OK : ROPE_E_HIP;
+}
+
 }  // namespace
 
 extern "C" size_t rope_pose_normal_workspace(int n_frames, int H, int W)
@@ -176,22 +223,14 @@ extern "C" int rope_pose_normal_equations(const float *render_depth_dev, const u
                                           int H, int W, int n_links, float fx, float fy, float cx, float cy, const double *joints_dev, int n_joints,
                                           float clip_m, double *out_dev, double *work_dev, void *stream)
 {
-    if (n_links < 1 || n_links > ROPE_MAX_LINKS || n_joints < 1 || n_joints > NEQ_JOINTS) return ROPE_E_ARG;
-    if (!isfinite(clip_m) || !(clip_m > 0.0f)) return ROPE_E_ARG;
-    if (!isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy) || fx == 0.0f || fy == 0.0f) return ROPE_E_ARG;
-    if (!render_depth_dev || !render_ids_dev || !frame_depth_dev || !joints_dev || !out_dev || !work_dev) return ROPE_E_ARG;
-    if (((uintptr_t)render_depth_dev & 3) || ((uintptr_t)frame_depth_dev & 3)) return ROPE_E_ARG;
-    if (((uintptr_t)joints_dev & 7) || ((uintptr_t)out_dev & 7) || ((uintptr_t)work_dev & 7)) return ROPE_E_ARG;
-    const long long chunks = neq_chunks(n_frames, H, W);
-    if (chunks == 0) return ROPE_E_ARG;
+    return neq_launch<false>(render_depth_dev, render_ids_dev, frame_depth_dev, n_frames, H, W, n_links, fx, fy, cx, cy, joints_dev, n_joints, clip_m,
+                             out_dev, work_dev, stream);
+}
 
-    hipStream_t st = (hipStream_t)stream;
-    const Camera cam = {(double)fx, (double)fy, (double)cx, (double)cy};
-    hipLaunchKernelGGL(neq_partial_kernel, dim3((unsigned)((long long)n_frames * chunks)), dim3(NEQ_THREADS), 0, st, render_depth_dev,
-                       render_ids_dev, frame_depth_dev, H, W, (int)chunks, n_links, cam, joints_dev, n_joints, (double)clip_m, work_dev);
-    if (hipGetLastError() != hipSuccess) return ROPE_E_HIP;
-    const int per = NEQ_GATHER_THREADS / ROPE_NEQ_WORDS;
-    hipLaunchKernelGGL(neq_gather_kernel, dim3((unsigned)((n_frames + per - 1) / per)), dim3(NEQ_GATHER_THREADS), 0, st, work_dev, n_frames,
-                       (int)chunks, out_dev);
-    return hipGetLastError() == hipSuccess ? ROPE_OK : ROPE_E_HIP;
+extern "C" int rope_camera_normal_equations(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames,
+                                            int H, int W, int n_links, float fx, float fy, float cx, float cy, const double *twists_dev, int n_cols,
+                                            float clip_m, double *out_dev, double *work_dev, void *stream)
+{
+    return neq_launch<true>(render_depth_dev, render_ids_dev, frame_depth_dev, n_frames, H, W, n_links, fx, fy, cx, cy, twists_dev, n_cols, clip_m,
+                            out_dev, work_dev, stream);
 }

@@ -35,7 +35,7 @@ ABI_SYMBOLS = (
     'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets',
     'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes', 'rope_frame_agreement',
     'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align',
-    'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace')
+    'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace', 'rope_camera_normal_equations')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -158,6 +158,7 @@ def load_library(path: str = None):
                                       C.c_uint64, vp, vp, vp]
     lib.rope_pose_normal_equations.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, i32, C.c_float,
                                                vp, vp, vp]
+    lib.rope_camera_normal_equations.argtypes = list(lib.rope_pose_normal_equations.argtypes)
     lib.rope_pose_normal_workspace.argtypes = [i32, i32, i32]
     lib.rope_pose_normal_workspace.restype = C.c_size_t
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
@@ -614,6 +615,21 @@ class Engine:
         (render_batch_device's); joints (N, n_joints, 6) float64, a numpy array or a tensor: unit axis and a point on the axis per
         joint, in camera axes (x right, y down, z forward); intr: (fx, fy, cx, cy).  The kernels run on torch's current stream and
         the sums are waited for here.  The same planes give the same bytes from run to run and however a batch is cut."""
+        return self._normal_equations('rope_pose_normal_equations', render_depth, render_ids, frame_depth, joints, 'joints',
+                                      'axis and a point on it per joint', n_links, clip, intr)
+
+    def camera_normal_equations(self, render_depth, render_ids, frame_depth, twists, n_links: int, clip: float, intr) -> np.ndarray:
+        """rope_camera_normal_equations: pose_normal_equations with respect to the camera pose -> (N, 32) float64 with the same
+        words.  twists (N, n_cols, 6) float64, a numpy array or a tensor: per column its angular part w and its linear part v in
+        camera axes; a surface point P moves by w x P + v per unit of the column, and EVERY drawn link moves with every column,
+        link 0 too (prediction/refinement.py: camera_twists).  Columns from n_cols on are exactly zero in [4..30].  Everything
+        else — the planes, intr, the stream, determinism, the empty batch — is pose_normal_equations'."""
+        return self._normal_equations('rope_camera_normal_equations', render_depth, render_ids, frame_depth, twists, 'twists',
+                                      'angular and linear part per column', n_links, clip, intr)
+
+    def _normal_equations(self, entry: str, render_depth, render_ids, frame_depth, columns, col_name: str, col_what: str, n_links: int,
+                          clip: float, intr) -> np.ndarray:
+        """The checks, the buffers and the call that rope_pose_normal_equations and rope_camera_normal_equations share."""
         import torch
         for name, t, dt in (('render_depth', render_depth, torch.float32), ('render_ids', render_ids, torch.uint8),
                             ('frame_depth', frame_depth, torch.float32)):
@@ -625,27 +641,27 @@ class Engine:
                 raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {tuple(render_depth.shape)}")
         N, H, W = render_depth.shape
         dev = render_depth.device
-        if not isinstance(joints, torch.Tensor):
-            joints = torch.from_numpy(np.ascontiguousarray(joints, np.float64))
-        if joints.dtype != torch.float64 or joints.dim() != 3 or joints.shape[0] != N or joints.shape[2] != 6:
-            raise ValueError(f"joints: ({N}, n_joints, 6) float64 — axis and a point on it per joint, got {tuple(joints.shape)} {joints.dtype}")
-        n_joints = int(joints.shape[1])
+        if not isinstance(columns, torch.Tensor):
+            columns = torch.from_numpy(np.ascontiguousarray(columns, np.float64))
+        if columns.dtype != torch.float64 or columns.dim() != 3 or columns.shape[0] != N or columns.shape[2] != 6:
+            raise ValueError(f"{col_name}: ({N}, n, 6) float64 — {col_what}, got {tuple(columns.shape)} {columns.dtype}")
+        n_columns = int(columns.shape[1])
         if N == 0:
             return np.zeros((0, NEQ_WORDS), np.float64)
         fx, fy, cx, cy = (float(v) for v in intr)
         with torch.cuda.device(dev):
-            joints = joints.to(dev).contiguous()
+            columns = columns.to(dev).contiguous()
             out = torch.empty((N, NEQ_WORDS), dtype=torch.float64, device=dev)
             work = torch.empty(max(1, self._lib.rope_pose_normal_workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
-            rc = self._lib.rope_pose_normal_equations(C.c_void_p(render_depth.data_ptr()), C.c_void_p(render_ids.data_ptr()),
-                                                      C.c_void_p(frame_depth.data_ptr()), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
-                                                      C.c_void_p(joints.data_ptr()), n_joints, float(clip), C.c_void_p(out.data_ptr()),
-                                                      C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = getattr(self._lib, entry)(C.c_void_p(render_depth.data_ptr()), C.c_void_p(render_ids.data_ptr()),
+                                           C.c_void_p(frame_depth.data_ptr()), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
+                                           C.c_void_p(columns.data_ptr()), n_columns, float(clip), C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
             if rc == -1:
-                raise ValueError(f"rope_pose_normal_equations refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), n_links "
-                                 f"{n_links} (1 .. 6), {n_joints} joints (1 .. 6), clip {clip} (finite, positive), intrinsics {(fx, fy, cx, cy)}")
+                raise ValueError(f"{entry} refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), n_links {n_links} "
+                                 f"(1 .. 6), {n_columns} {col_name} (1 .. 6), clip {clip} (finite, positive), intrinsics {(fx, fy, cx, cy)}")
             if rc:
-                raise EngineError(f"rope_pose_normal_equations failed ({rc})")
+                raise EngineError(f"{entry} failed ({rc})")
             return out.cpu().numpy()
 
     def debug_targets(self, want_tsweep: bool = False):

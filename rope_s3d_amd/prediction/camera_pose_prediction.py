@@ -122,8 +122,9 @@ class _CameraStageMachine:
 
     zp_div_from_stage = True      # CameraPredictor's zp_sweep reads a stale `div` instead (see run_stages)
 
-    def __init__(self, base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device):
+    def __init__(self, base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine=False):
         self.base_pose = np.array(base_pose, dtype=float)
+        self.refine, self.last_refinement, self._refiner = bool(refine), None, None
         self.ds_factor, self.preview = ds_factor, preview
         self.min_ang_inc = np.asarray(min_angle_inc, dtype=float)
         self.history_length = history_length
@@ -320,6 +321,18 @@ class _CameraStageMachine:
             self.trace.append((kind, pose.copy()))
         return pose
 
+    def _polish(self, pose: np.ndarray) -> np.ndarray:
+        """The continuous last step (refinement.CameraPoseRefiner) on the pose the stages ended on, against the down-sampled depth
+        frames of this run at the working resolution; `last_refinement` keeps its result.  With the switch off: the pose as it is."""
+        self.last_refinement = None
+        if not self.refine:
+            return pose
+        if self._refiner is None:
+            from .refinement import CameraPoseRefiner
+            self._refiner = CameraPoseRefiner(self.renderer, self.renderer.intrinsics)
+        self.last_refinement = self._refiner.refine(pose, self.robot_poses, np.asarray(self._tgt_depths, np.float32))
+        return self.last_refinement.pose.copy()
+
     def _start(self, og_images, target_depths, robot_poses, starting_camera_pose):
         og_images, target_depths = np.asarray(og_images), np.asarray(target_depths)
         if og_images.ndim == 3:
@@ -370,8 +383,10 @@ class ModellessCameraPredictor(_CameraStageMachine):
 
     def __init__(self, base_pose=DEFAULT_CAMERA_POSE, ds_factor: int = 8, preview: bool = False, save_to: str = None,
                  min_angle_inc=np.array([0.001, 0.001, 0.001, 0.002, 0.002, 0.002]), history_length=5,
-                 base_intrinsics='1280_720_color', *, device: int = 0):
-        super().__init__(base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device)
+                 base_intrinsics='1280_720_color', *, device: int = 0, refine: bool = False):
+        """`refine`: polish the pose the stages end on with refinement.CameraPoseRefiner and keep its CameraRefineResult (the
+        pooled formal sigma of the six parameters, every frame's own cost) in `last_refinement`."""
+        super().__init__(base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine)
 
     def _setStages(self):
         self.stages = modelless_stages()
@@ -385,7 +400,7 @@ class ModellessCameraPredictor(_CameraStageMachine):
         self.engine.set_frames(self.robot_poses, *self._frame_planes)
         if self.stages is None:
             self._setStages()
-        return self.run_stages(pose)
+        return self._polish(self.run_stages(pose))
 
     def _errors(self, poses):
         return modelless_error(self._sums(poses, LOSS_TSWEEP), self._n_pix)
@@ -411,10 +426,11 @@ class CameraPredictor(_CameraStageMachine):
 
     def __init__(self, base_pose=DEFAULT_CAMERA_POSE, ds_factor: int = 8, preview: bool = False, save_to: str = None,
                  min_angle_inc=np.array([0.001, 0.001, 0.001, 0.002, 0.002, 0.002]), history_length=5,
-                 base_intrinsics='1280_720_color', *, device: int = 0, segmenter: Optional[Callable] = None):
+                 base_intrinsics='1280_720_color', *, device: int = 0, segmenter: Optional[Callable] = None, refine: bool = False):
         """`segmenter`: callable(colour uint8 HxWx3) -> {'class_ids', 'rois', 'scores', 'masks' (H,W,K) bool}; stands in
-        for pixellib's segmentImage on "models/segmentation/multi/B.h5" (:603-606,687)."""
-        super().__init__(base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device)
+        for pixellib's segmentImage on "models/segmentation/multi/B.h5" (:603-606,687).  `refine`: as ModellessCameraPredictor's;
+        the polish is against the whole down-sampled depth frames, not the per-link planes."""
+        super().__init__(base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine)
         if segmenter is None:
             raise ValueError("CameraPredictor needs a segmenter (e.g. rope_s3d_amd.maskrcnn.MaskRCNNSegmenter)")
         self.seg = segmenter
@@ -474,7 +490,7 @@ class CameraPredictor(_CameraStageMachine):
         if self.stages is None:
             self._setStages()
         self._load_targets(segmentation_data, target_depths)
-        return self.run_stages(pose)
+        return self._polish(self.run_stages(pose))
 
     def _errors(self, poses):
         return camfull_error(self._sums(poses, LOSS_CAMFULL), self._n_pix, self._flags)

@@ -194,3 +194,125 @@ class PoseRefiner:
             steps += ok
             lam[~ok] *= 10.0
         return RefineResult(q, np.stack([formal_sigma(w, self.active) for w in words]), cost_before, cost, steps, words[:, 2].copy())
+
+
+# ---------------------------------------------------------------------------------------------- the camera pose
+@dataclass
+class CameraRefineResult:
+    """What CameraPoseRefiner.refine returns: one camera, pooled over the frames."""
+    pose: np.ndarray            # (6,) the refined [x, y, z, a3, a4, a5]; parameters outside do_params as they came
+    sigma: np.ndarray           # (6,) formal standard deviation, m and rad: inf = the views do not pin the parameter down, nan = not refined
+    cost_before: float          # pooled mean truncated squared residual at the start, m^2 (inf: nothing to compare)
+    cost_after: float           # the same at the refined pose; never larger than cost_before
+    steps_taken: int            # accepted steps, 0 .. iterations
+    inliers: float              # pixels of all frames that carried the final system
+    frame_cost: np.ndarray      # (N,) every frame's own mean truncated cost at the refined pose: a frame whose recorded joint
+    #                             angles do not fit the others stands out
+
+
+def camera_twists(pose6) -> np.ndarray:
+    """[x, y, z, a3, a4, a5] -> (6, 6): row k is the twist (w, v), in the kernel's camera axes (x right, y down, z forward), with
+    which a world-fixed point moves per unit of pose parameter k: dX_c / dp_k = w x X_c + v.
+
+    With M = camera_pose_matrix(pose) = [R | t], Rwc = diag(1, -1, -1) R^T and X_c = Rwc (X_w - t):
+      a translation t_k gives dX_c = -Rwc e_k: w = 0, v = -Rwc[:, k];
+      an angle turns R = Rz(yaw) Ry(pitch) Rx(roll) about a world axis a (yaw: z; pitch: Rz y; roll: Rz Ry x), dR = [a]x R, so
+      dX_c = -diag(1, -1, -1) R^T (a x (X_w - t)) = -(Rwc a) x X_c (diag(1, -1, -1) is a rotation, it goes through the cross
+      product): w = -Rwc a, v = 0."""
+    p = np.asarray(pose6, np.float64).reshape(6)
+    Rwc = np.diag([1.0, -1.0, -1.0]) @ camera_pose_matrix(p)[:3, :3].T
+    yaw, pitch = p[5], p[3]
+    cy, sy, cp, sp = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch)
+    axis = {5: np.array([0.0, 0.0, 1.0]), 3: np.array([-sy, cy, 0.0]), 4: np.array([cy * cp, sy * cp, -sp])}      # z; Rz y; Rz Ry x
+    out = np.zeros((6, 6))
+    for k in range(3):
+        out[k, 3:] = -Rwc[:, k]
+    for k in (3, 4, 5):
+        out[k, :3] = -(Rwc @ axis[k])
+    return out
+
+
+def pool_frames(words: np.ndarray) -> np.ndarray:
+    """(N, 32) -> (32,): the frames' words added in frame order, one float64 addition after the other (no pairwise summation: the
+    order is part of what tests/camera_refine_ref.py restates)."""
+    pooled = np.zeros(NEQ_WORDS)
+    for w in np.asarray(words, np.float64).reshape(-1, NEQ_WORDS):
+        pooled = pooled + w
+    return pooled
+
+
+class CameraPoseRefiner:
+    """A continuous last step for a CAMERA pose seen in N frames at known joint angles, and how sure it is: PoseRefiner's loop
+    with the six pose parameters as columns (camera_twists, rope_camera_normal_equations) and ONE system pooled over the frames.
+
+    renderer_or_engine  a simulation.render.Renderer or an Engine on which robot and camera are set (the camera's resolution is
+                        what counts: every render here brings its own P V, projection.camera_matrix's, the renderer's own camera
+                        is neither read nor moved)
+    intrinsics          projection.Intrinsics of the frames (the working resolution)
+    do_params           the parameters of [x, y, z, a3, a4, a5] to refine
+    clip, iterations, damping   as PoseRefiner's; damping is multiplied by 10 whenever a step is refused"""
+
+    def __init__(self, renderer_or_engine, intrinsics, do_params=(True,) * 6, clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3):
+        if not (np.isfinite(clip) and clip > 0):
+            raise ValueError(f"clip must be finite and positive, got {clip}")
+        if iterations < 0 or not (np.isfinite(damping) and damping >= 0):
+            raise ValueError("iterations and damping must not be negative")
+        do_params = np.asarray(do_params, bool).reshape(-1)
+        if len(do_params) != 6:
+            raise ValueError("do_params: six flags, one per pose parameter")
+        self.engine = renderer_or_engine.engine if hasattr(renderer_or_engine, 'render_ids_batch_device') else renderer_or_engine
+        self.intrinsics = intrinsics
+        self.active = [int(k) for k in np.flatnonzero(do_params)]
+        self.clip, self.iterations, self.damping = float(clip), int(iterations), float(damping)
+
+    @property
+    def n_links(self) -> int:
+        return min(int(self.engine.n_links), NUM_RENDER_LINKS)
+
+    def equations(self, pose, angles: np.ndarray, depth_t) -> np.ndarray:
+        """One render of the N frames' angles under the camera `pose` and one kernel call -> (N, 32), per frame."""
+        from ..projection import camera_matrix
+        intr = self.intrinsics
+        N = len(angles)
+        PV = np.tile(camera_matrix(pose, intr)[None], (N, 1, 1))
+        rd, ri = self.engine.render_batch_device(angles, self.n_links, PV)
+        twists = np.tile(camera_twists(pose)[None], (N, 1, 1))
+        return self.engine.camera_normal_equations(rd, ri, depth_t, twists, self.n_links, self.clip, (intr.fx, intr.fy, intr.cx, intr.cy))
+
+    def refine(self, camera_pose, angles, depth) -> CameraRefineResult:
+        """camera_pose (6,); angles (N, 6) the robot's joint angles in the frames; depth (N, H, W) metres at the refiner's
+        resolution, a numpy array or a torch tensor on the host or the device, 0 / NaN where nothing was measured.
+
+        sigma is formal_sigma's of the pooled system: it treats the pixels as independent measurements, and neighbouring pixels
+        of a depth frame are not, so it is FORMAL and optimistic — good for telling a parameter the views pin down from one they
+        do not (a camera seen head-on barely fixes its distance) and for ranking, not an error bar to be taken at face value."""
+        import torch
+        pose = np.array(camera_pose, np.float64).reshape(6)
+        q = np.ascontiguousarray(np.asarray(angles, np.float64).reshape(-1, 6))
+        N = len(q)
+        if N == 0:
+            sig = np.full(6, np.nan)
+            sig[self.active] = np.inf
+            return CameraRefineResult(pose, sig, np.inf, np.inf, 0, 0.0, np.zeros(0))
+        device = torch.device('cuda', self.engine.device)
+        if not isinstance(depth, torch.Tensor):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32))
+        depth_t = depth.to(device=device, dtype=torch.float32).contiguous()
+        if depth_t.dim() != 3 or depth_t.shape[0] != N:
+            raise ValueError(f"depth: ({N}, H, W), got {tuple(depth_t.shape)}")
+        lam = self.damping
+        words = self.equations(pose, q, depth_t)
+        pooled = pool_frames(words)
+        cost = float(mean_cost(pooled[None])[0])
+        cost_before, steps = cost, 0
+        for _ in range(self.iterations):
+            trial = pose + levenberg_step(pooled, self.active, lam)
+            w_t = self.equations(trial, q, depth_t)
+            p_t = pool_frames(w_t)
+            c_t = float(mean_cost(p_t[None])[0])
+            if c_t < cost:                                              # strictly smaller, or the pose is put back
+                pose, words, pooled, cost = trial, w_t, p_t, c_t
+                steps += 1
+            else:
+                lam *= 10.0
+        return CameraRefineResult(pose, formal_sigma(pooled, self.active), cost_before, cost, steps, float(pooled[2]), mean_cost(words))
