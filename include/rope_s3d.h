@@ -155,14 +155,25 @@ int rope_prepare_segmented(const void *depth, int depth_kind, int64_t depth_stri
                            const int32_t *link_of, int n_links, int n_lookup_links, uint64_t *tq, float *lookup_f32, double *tgt_depth,
                            uint8_t *flags);
 
-/* Candidate joint vectors (C x 6 doubles) into HBM; they stay resident until replaced. */
+/* Candidate joint vectors (C x 6 doubles) into HBM; they stay resident until replaced.
+ * The context keeps a host copy of the rows it was last given: an upload of the same C rows, bit for bit, while they are still
+ * resident copies, sorts and uploads nothing, and whatever rope_eval_resident kept of the last pass (below) stays good.  This is
+ * what a fixed grid scored through rope_eval against frame after frame comes to. */
 int rope_candidates_upload(rope_ctx *ctx, const double *cand, int C);
 
 /* FK + raster of the first n_render links + loss reduction + argmin for the resident
  * candidates, enqueued on the context's stream (no host sync).
  * Replaces, per candidate, render_at_pos + _error (predict.py:159-161,475-509) and, for the
  * lookup loss, the TF reduction over the pre-rendered table (predict.py:167-171).
- *   crop   r0,r1,c0,c1 inclusive image rows/cols; required for ROPE_LOSS_LOOKUP, else NULL */
+ *   crop   r0,r1,c0,c1 inclusive image rows/cols; required for ROPE_LOSS_LOOKUP, else NULL
+ * Kept from pass to pass: a batch of more than 256 rows that shares upstream layers leaves its link matrices, screen boxes, tile
+ * masks, queue weights and layer key tiles in the context — none depends on the target — and the next such pass with the same
+ * candidates, camera, robot, n_render, crop and strategy runs without the forward-kinematics, box and shared-layer launches: it
+ * only takes the layers' loss sums against the current target again (any loss; rope_set_target between the passes is the
+ * point).  Results are the same bits.  Dropped by: an upload of other rows, rope_set_camera (same values included),
+ * rope_set_robot[_mesh], rope_set_strategy, another n_render or crop, and every other entry that uses the per-candidate
+ * buffers (small batches, rope_eval_targets, rope_eval_views, the render entries, rope_coverage, rope_lookup_build,
+ * rope_debug_mvp).  ROPE_STRATEGY_NO_GEOMETRY_CACHE turns it off; rope_geometry_cache_stats counts. */
 int rope_eval_resident(rope_ctx *ctx, int n_render, int loss, const int32_t *crop);
 
 int rope_sync(rope_ctx *ctx);
@@ -415,7 +426,8 @@ int rope_predict_batch(rope_ctx *ctx, const rope_predict_args *args, int n_frame
 int rope_debug_mvp(rope_ctx *ctx, float *mvp_out, int C, int n_render);
 
 /* Time `reps` back-to-back rope_eval_resident passes with HIP events on the context's
- * stream; ms[0] = FK + bounds kernels, ms[1] = shared-layer raster launch (0 when layers are not in use),
+ * stream; ms[0] = FK + bounds kernels (a pass on kept geometry: the clearing launch), ms[1] = shared-layer raster launch (on kept
+ * geometry: the layer-sums kernel; 0 when layers are not in use),
  * ms[2] = raster+score launch, ms[3] = finalize+argmin, ms[4] = whole pass (averages per pass, milliseconds). */
 int rope_profile_eval(rope_ctx *ctx, int n_render, int loss, const int32_t *crop, int reps, float *ms);
 
@@ -427,10 +439,16 @@ int rope_profile_eval(rope_ctx *ctx, int n_render, int loss, const int32_t *crop
  *   8  large batches as one workgroup per (tile, candidate) pair instead of a queue of the pairs that have work
  *  16  always the raster kernels that can clip triangles at the near plane (by default only when the camera is within the
  *      robot's reach of it: they are several per cent slower, and without a triangle at the plane they draw the same image)
- *  32  small batches: forward kinematics and screen boxes as a launch of their own instead of inside the split raster's workgroups */
+ *  32  small batches: forward kinematics and screen boxes as a launch of their own instead of inside the split raster's workgroups
+ *  64  large batches: keep no geometry from pass to pass (rope_eval_resident) — every pass builds all of it, as the first one does */
 enum { ROPE_STRATEGY_NO_LAYERS = 1, ROPE_STRATEGY_NO_SPLIT = 2, ROPE_STRATEGY_NO_PARENTS = 4, ROPE_STRATEGY_NO_QUEUE = 8, ROPE_STRATEGY_CLIP_KERNELS = 16,
-       ROPE_STRATEGY_SEPARATE_GEOMETRY = 32 };
+       ROPE_STRATEGY_SEPARATE_GEOMETRY = 32, ROPE_STRATEGY_NO_GEOMETRY_CACHE = 64 };
 int rope_set_strategy(rope_ctx *ctx, int flags);
+
+/* Passes of rope_eval_resident that could keep geometry (more than 256 rows, shared layers, the single target) since the context
+ * was created: how many ran on what the pass before them left (hits) and how many built it (misses; with
+ * ROPE_STRATEGY_NO_GEOMETRY_CACHE all of them).  Either pointer may be NULL. */
+int rope_geometry_cache_stats(rope_ctx *ctx, uint64_t *hits, uint64_t *misses);
 
 /* ---- Segmentation stage (robotpose/prediction/predict.py:94-98,416: the Matterport Mask R-CNN in front of the engine).
  * The convolutions are library calls from PyTorch-ROCm (rope_s3d_amd/maskrcnn.py); the two box-shaped steps between them

@@ -65,7 +65,7 @@ extern "C" int rope_create(rope_ctx **out, int device)
     if (!c) return ROPE_E_NOMEM;
     c->device = device;
     if (const char *e = std::getenv("ROPE_SPLIT_TARGET")) c->split_target = std::max(1, std::atoi(e));     // tuning aid
-    if (const char *e = std::getenv("ROPE_STRATEGY")) c->strategy = std::atoi(e) & 63;                     // tuning aid: rope_set_strategy's bits
+    if (const char *e = std::getenv("ROPE_STRATEGY")) c->strategy = std::atoi(e) & 127;                     // tuning aid: rope_set_strategy's bits
     if (const char *e = std::getenv("ROPE_SPLIT_CAP")) c->split_cap = std::max(1, std::min(64, std::atoi(e)));
     if (const char *e = std::getenv("ROPE_SPLIT_MIN")) c->split_min = std::max(1, std::min(64, std::atoi(e)));
     if (const char *e = std::getenv("ROPE_GEO_ROWS")) c->geo_rows = std::max(0, std::min(256, std::atoi(e)));     // d_touched holds 256 rows
@@ -227,6 +227,9 @@ extern "C" int rope_set_robot(rope_ctx *c, const uint32_t *ml_header, int n_mesh
         reach = std::max(reach, chain + r);
     }
     HIP_TRY(c, hipSetDevice(c->device));
+    c->geo.drop();                                // boxes, masks, weights and layer tiles are this robot's no longer
+    c->shadow.drop();
+    c->robot_epoch++;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, c->d_header.reset(8 * (size_t)n_meshlets));
     HIP_TRY(c, c->d_verts.reset(3 * (size_t)n_ml_verts));
@@ -266,6 +269,8 @@ extern "C" int rope_set_camera(rope_ctx *c, const double *PV, int W, int H, doub
     if (W < 1 || H < 1 || W > 8192 || H > 8192) ARG_FAIL(c, "rope_set_camera: image size out of range");
     if (!(znear > 0.0) || !(zfar > znear)) ARG_FAIL(c, "rope_set_camera: need 0 < znear < zfar");
     HIP_TRY(c, hipSetDevice(c->device));
+    c->geo.drop();                                // whatever the values: the matrices are not compared
+    c->camera_epoch++;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const bool resized = !c->have_camera || W != c->fp.W || H != c->fp.H;
     // the new geometry in locals: the context keeps describing the old image until every buffer of the new one exists
@@ -359,6 +364,8 @@ static bool use_clip(const rope_ctx *c, bool views = false)
 int ensure_capacity(rope_ctx *c, int C)
 {
     if (C <= c->cap) return ROPE_OK;
+    c->geo.drop();                                // every per-candidate buffer is allocated anew
+    c->shadow.drop();
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     int cap = C < 64 ? 64 : C;
     HIP_TRY(c, c->d_cand.reset(6 * (size_t)cap));
@@ -396,6 +403,16 @@ extern "C" int rope_candidates_upload(rope_ctx *c, const double *cand, int C)
 int upload_candidates(rope_ctx *c, const double *cand, int C, bool group, const int32_t *frame_of)
 {
     if (!cand || C < 1 || C > 65535) ARG_FAIL(c, "rope_candidates_upload: need 1 <= C <= 65535");
+    // The rows that are resident already (a fixed grid scored against frame after frame through rope_eval): nothing to check, copy,
+    // sort or upload, and the candidate epoch — with it the geometry a pass may have kept — stands.  Only while the last upload
+    // still describes the context: the camera-pose and render entries take the rows away (cand_valid), a new capacity drops the shadow.
+    if (!frame_of && c->cand_valid && c->C == C && c->shadow.same(cand, C, group)) {
+        c->results_valid = false;
+        return ROPE_OK;
+    }
+    c->shadow.drop();
+    c->geo.drop();
+    c->cand_epoch++;
     for (size_t i = 0; i < 6 * (size_t)C; i++)
         if (!std::isfinite(cand[i]) || std::fabs(cand[i]) > 1.0e4) ARG_FAIL(c, "rope_candidates_upload: joint angle not finite or |q| > 1e4 rad");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -464,6 +481,7 @@ int upload_candidates(rope_ctx *c, const double *cand, int C, bool group, const 
     c->C = C;
     c->cand_valid = true;
     c->results_valid = false;
+    if (!frame_of) c->shadow.keep(cand, C, group);
     return ROPE_OK;
 }
 
@@ -520,6 +538,7 @@ static bool layers_pay(const rope_ctx *c)
 static int ensure_layers(rope_ctx *c)
 {
     size_t need = (size_t)c->n_layers * c->n_tiles * (TILE_W * TILE_H);
+    // (a re-grown buffer drops the kept geometry: sync_grow)
     return sync_grow(c, c->d_layers, need, c->d_layer_sums, (size_t)c->n_layers * c->n_tiles * ROPE_SUM_WORDS);
 }
 
@@ -539,6 +558,7 @@ static bool use_parents(const rope_ctx *c, int n_shared)
 // merged with its parent's tile.
 static int enqueue_layers(rope_ctx *c, RasterArgs la, int loss, int n_shared, const FrameParams &fp)
 {
+    c->geo.drop();                                // every writer of the layer tiles comes through here
     la.cand_of_row = c->d_layer_rep; la.layers = c->d_layers;
     if (use_parents(c, n_shared)) {
         const size_t need = (size_t)c->n_parents * c->n_tiles * (TILE_W * TILE_H);
@@ -580,9 +600,29 @@ static uint32_t *queue_weights(const rope_ctx *c)
     return (c->q_weighted && c->C > 256 && (size_t)c->C * busy_tiles <= (size_t)256 * 2 * c->n_cu) ? c->d_tile_tris : nullptr;     // C <= 256: fk_bounds_kernel, no weights
 }
 
+// What the buffers a large layered pass leaves behind depend on (GeometryKey): candidates, camera and robot by their epochs, the
+// pass's frame and n_render, and everything that decides which launches write them — the second sharing level, the queues and
+// their weights (functions of strategy, C, tiles and n_cu, recorded as taken), the clipping kernels — plus the capacities of the
+// buffers themselves.  The loss is not part of it: the one thing of these launches that depends on loss or target, the layers'
+// sums, is taken anew by every pass.
+static GeometryKey geometry_key(const rope_ctx *c, int n_render, int n_shared, const FrameParams &fp)
+{
+    static_assert(sizeof(FrameParams) <= sizeof(GeometryKey::frame), "GeometryKey::frame holds a FrameParams");
+    GeometryKey k = GeometryKey::make();
+    k.cand_epoch = c->cand_epoch; k.camera_epoch = c->camera_epoch; k.robot_epoch = c->robot_epoch;
+    k.cap_layers = c->d_layers.cap(); k.cap_layer_sums = c->d_layer_sums.cap(); k.cap_bounds = c->d_bounds.cap(); k.cap_mvp = c->d_mvp.cap();
+    k.q_segment = c->q_segment;
+    k.C = c->C; k.n_layers = c->n_layers; k.n_parents = c->n_parents; k.n_render = n_render; k.n_shared = n_shared;
+    k.strategy = c->strategy; k.n_cu = c->n_cu;
+    k.parents = use_parents(c, n_shared); k.queue = !(c->strategy & STRATEGY_NO_QUEUE); k.weighted = queue_weights(c) != nullptr; k.clip = use_clip(c);
+    k.set_frame(&fp, sizeof fp);
+    return k;
+}
+
 // forward kinematics + link matrices + screen boxes + tile masks (+ cleared sums) of the resident candidates
 static int enqueue_geometry(rope_ctx *c, int n_render, int n_shared, const FrameParams &fp, bool views)
 {
+    c->geo.drop();                                // every writer of d_mvp, d_bounds, the masks and the weights comes through here
     const double *PV = views ? c->dv_PV : c->d_PV, *cand = views ? c->dv_cand : c->cand_dev;
     const int32_t *view_of = views ? c->dv_view_of : nullptr;
     if (c->C <= 256) {                              // one fused launch, one workgroup per candidate
@@ -605,6 +645,15 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
     const bool layers = !views && want_layers(c) && layers_pay(c) && !(c->strategy & STRATEGY_NO_LAYERS);
     const int n_shared = layers ? std::min(3, n_render) : 0;
     if (layers) { int rc = ensure_layers(c); if (rc) return rc; }
+    // A large layered batch against the single target keeps its geometry for the next pass (rope_ctx::geo).  Every other pass
+    // drops it: it either goes through enqueue_geometry or — the small batches that do their own — reuses the same buffers' rows.
+    const bool in_scope = kind == EVAL_SINGLE && layers && c->C > 256 && !pl.frame_of;
+    const bool cacheable = in_scope && !(c->strategy & STRATEGY_NO_GEOMETRY_CACHE) && !ROPE_SKIP(fp, ~0);
+    GeometryKey key = GeometryKey::make();
+    if (cacheable) key = geometry_key(c, n_render, n_shared, fp);
+    const bool hit = cacheable && c->geo.holds(key);
+    c->geo.drop();                                  // a pass that fails half way leaves nothing behind; set again at the end
+    if (in_scope) (hit ? c->geo.hits : c->geo.misses)++;
     if (ev) HIP_TRY(c, hipEventRecord(ev[0], c->stream));
     // Few candidates (descent pairs, flips): one workgroup per (tile, candidate) would leave most of the chip idle,
     // so the meshlets of each tile are split over several workgroups that merge into a tile in global memory.
@@ -625,7 +674,8 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
     // And on frames of a few tiles only (the Predictor's 160x90 is two): on a 25-tile frame two thirds of the workgroups belong to tiles
     // the robot does not reach — the masks of the separate launch let them leave at once, here each would do the matrices first.
     const bool geo = split > 1 && !views && c->C <= c->geo_rows && c->n_tiles <= 4 && !(c->strategy & STRATEGY_SEPARATE_GEOMETRY);
-    if (!geo) { RopeRange r("rope:fk+bounds"); int rc = enqueue_geometry(c, n_render, n_shared, fp, views); if (rc) return rc; }
+    if (hit) HIP_TRY(c, launch_clear_pass(c->stream, c->d_sums, c->C, c->d_qctr));      // what is left of fk_mvp_kernel: cleared sums and queue counters
+    else if (!geo) { RopeRange r("rope:fk+bounds"); int rc = enqueue_geometry(c, n_render, n_shared, fp, views); if (rc) return rc; }
     c->mvp_valid = !geo;
     if (ev) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
     RasterArgs a = base_args(c, n_render);
@@ -662,7 +712,12 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
     if (layers) {
         RasterArgs la = a;
         la.layer_sums = c->d_layer_sums; la.tq = pl.tq; la.t32 = pl.t32; la.frame_of = pl.frame_of;
-        { RopeRange r("rope:shared-layers"); int rc = enqueue_layers(c, la, loss, n_shared, fp); if (rc) return rc; }
+        if (hit) {
+            // the key tiles are the last pass's; their loss sums against this pass's target are all the layer launch would add
+            RopeRange r("rope:layer-sums");
+            la.cand_of_row = c->d_layer_rep; la.layers = c->d_layers;
+            HIP_TRY(c, launch_layer_sums(loss, c->n_layers, c->stream, fp, la));
+        } else { RopeRange r("rope:shared-layers"); int rc = enqueue_layers(c, la, loss, n_shared, fp); if (rc) return rc; }
         a.l_begin = n_shared; a.layer_of = c->d_layer_of; a.layer_rep = c->d_layer_rep; a.layers = c->d_layers; a.layer_sums = c->d_layer_sums;
     }
     a.tq = pl.tq; a.t32 = pl.t32; a.tl = pl.tl; a.frame_of = pl.frame_of; a.sums = c->d_sums;
@@ -695,6 +750,7 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
     if (ev) HIP_TRY(c, hipEventRecord(ev[4], c->stream));
     c->last_n_render = n_render;
     c->results_valid = true;
+    if (cacheable) c->geo.filled(key);              // every launch of the pass is in the stream
     return ROPE_OK;
 }
 
@@ -1101,8 +1157,18 @@ extern "C" int rope_debug_mvp(rope_ctx *c, float *mvp_out, int C, int n_render)
 extern "C" int rope_set_strategy(rope_ctx *c, int flags)
 {
     if (!c) return ROPE_E_ARG;
-    if (flags & ~(STRATEGY_NO_LAYERS | STRATEGY_NO_SPLIT | STRATEGY_NO_PARENTS | STRATEGY_NO_QUEUE | STRATEGY_CLIP_KERNELS | STRATEGY_SEPARATE_GEOMETRY)) ARG_FAIL(c, "rope_set_strategy: unknown flag");
+    if (flags & ~(STRATEGY_NO_LAYERS | STRATEGY_NO_SPLIT | STRATEGY_NO_PARENTS | STRATEGY_NO_QUEUE | STRATEGY_CLIP_KERNELS | STRATEGY_SEPARATE_GEOMETRY |
+                  STRATEGY_NO_GEOMETRY_CACHE)) ARG_FAIL(c, "rope_set_strategy: unknown flag");
+    c->geo.drop();
     c->strategy = flags;
+    return ROPE_OK;
+}
+
+extern "C" int rope_geometry_cache_stats(rope_ctx *c, uint64_t *hits, uint64_t *misses)
+{
+    if (!c) return ROPE_E_ARG;
+    if (hits) *hits = c->geo.hits;
+    if (misses) *misses = c->geo.misses;
     return ROPE_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rope_buffers.h"
+#include "rope_geomcache.h"
 #include "rope_kernels.h"
 
 using namespace rope;
@@ -148,6 +149,15 @@ struct rope_ctx {
     DevBuf<uint64_t> d_sums;
     DevBuf<int32_t> d_best_idx;
     int last_n_render = 0;
+    // A fixed grid's geometry, kept from pass to pass: d_mvp, d_bounds, the masks, the queue weights and the layer key tiles (with
+    // d_parents behind them) are functions of robot, camera, candidates, n_render and launch structure only — never of the target.
+    // `geo` says which large layered EVAL_SINGLE pass built them; the next pass with the same key skips the geometry and layer
+    // launches and only takes the layers' loss sums again (layer_sums_kernel).  Dropped at the choke points every writer of those
+    // buffers goes through (enqueue_geometry, enqueue_layers, the grow paths, the robot / camera / strategy setters), set only when
+    // a whole cacheable pass has been enqueued.  `shadow`: the last uploaded rows, so that an upload of the same rows keeps the epoch.
+    GeometryCache geo;
+    CandidateShadow shadow;
+    uint64_t cand_epoch = 0, camera_epoch = 0, robot_epoch = 0;
 
     // small batches: per-candidate tiles in global memory that split workgroups merge into
     DevBuf<int> d_touched;                 // MODE_SPLIT_GEO: per (candidate, tile) the number of the pass that last drew into it
@@ -256,6 +266,7 @@ template <typename B, typename... R> static int grow_each(B &b, size_t n, R &...
 template <typename... A> static int sync_grow(rope_ctx *c, A &&...a)
 {
     if (!any_short(a...)) return ROPE_OK;
+    c->geo.drop();                                // whichever buffer grows: a re-grown one holds nothing, and the key need not name them all
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, grow_each(a...));
     return ROPE_OK;

@@ -91,7 +91,8 @@ struct FrameParams {
 #endif
 
 // Execution strategies that change the launch structure but never a result (rope_set_strategy)
-enum { STRATEGY_NO_LAYERS = 1, STRATEGY_NO_SPLIT = 2, STRATEGY_NO_PARENTS = 4, STRATEGY_NO_QUEUE = 8, STRATEGY_CLIP_KERNELS = 16, STRATEGY_SEPARATE_GEOMETRY = 32 };
+enum { STRATEGY_NO_LAYERS = 1, STRATEGY_NO_SPLIT = 2, STRATEGY_NO_PARENTS = 4, STRATEGY_NO_QUEUE = 8, STRATEGY_CLIP_KERNELS = 16, STRATEGY_SEPARATE_GEOMETRY = 32,
+       STRATEGY_NO_GEOMETRY_CACHE = 64 };
 
 struct RobotParams {
     const uint32_t *ml_header;            // n_meshlets x 8
@@ -177,6 +178,13 @@ hipError_t launch_raster_queue(int loss, int rows, int workgroups, hipStream_t s
 // the same for a MODE_LAYER launch (a.cand_of_row set): (layer, tile) pairs of the representatives' shared links, by their weight
 hipError_t launch_layer_queue(int loss, int rows, int workgroups, hipStream_t st, const FrameParams &fp, const RobotParams &rp,
                               const RasterArgs &a, uint32_t *items, size_t segment, int *counters, const uint32_t *tile_tris_lo, bool clip);
+// A pass that keeps the last one's geometry (rope_ctx::geo).  launch_clear_pass: what fk_mvp_kernel clears besides working out
+// matrices — the C rows of sums and the 2 x QUEUE_COUNTERS queue counters (or nullptr).  launch_layer_sums: the loss sums of every
+// stored layer tile against the current target, what the MODE_LAYER launch leaves in a.layer_sums — a.cand_of_row (layer ->
+// representative candidate), a.mask_lo, a.layers, a.layer_sums, a.tq / a.t32 and a.n_render are read; the sums of the (layer, tile)
+// pairs whose mask_lo bit is set are stored, the others are left alone (nobody reads them).
+hipError_t launch_clear_pass(hipStream_t st, uint64_t *sums, int C, int *queue_counters);
+hipError_t launch_layer_sums(int loss, int n_layers, hipStream_t st, const FrameParams &fp, const RasterArgs &a);
 // scores what a MODE_SPLIT launch merged into a.gtile; `slices` row slices per tile (a divisor of TILE_H)
 hipError_t launch_score_gtile(int loss, int rows, int slices, hipStream_t st, const FrameParams &fp, const RasterArgs &a);
 // "nothing rendered" sums of n_frames frames (planes back to back): empty_sums n_frames x n_tiles x SUM_WORDS of scratch,

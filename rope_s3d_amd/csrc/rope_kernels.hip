@@ -16,6 +16,8 @@
 //                             TABLE  rows of the stored lookup table (cropped sqrt-depth)
 //                             DUMP / COVER  single-pose render, crop search
 //   score_gtile_kernel      after SPLIT: scores the merged images in row bands and hands the buffer back empty
+//   clear_pass_kernel /     a pass over a grid whose geometry the context kept: clears the sums, and takes the stored layer
+//   layer_sums_kernel       tiles' loss sums against the new target — fk, bounds and LAYER do not run
 //   finalize_argmin_kernel  integer sums -> float64 errors, wave-shuffle argmin
 //   table_score_kernel      Lookup stage against the stored table: pure streaming
 //   camera-pose path        the same kernels with a view matrix per candidate (fk) and target planes per frame
@@ -1483,6 +1485,47 @@ score_gtile_kernel(FrameParams fp, RasterArgs ra)
         atomicAdd((unsigned long long *)&ra.sums[(size_t)cand * ROPE_SUM_WORDS + tid], (unsigned long long)lds_sums[tid]);
 }
 
+// A pass over a grid whose geometry the context kept (rope_ctx::geo) runs neither fk_mvp_kernel nor the MODE_LAYER launch.  What
+// is left of them is done by the two kernels below.
+
+// fk_mvp_kernel's clearing without its matrices: the rows' sums, which the scoring launch accumulates into, and the queue counters
+__global__ void __launch_bounds__(256)
+clear_pass_kernel(uint64_t *__restrict__ sums, size_t n_words, int *__restrict__ queue_counters)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_words) sums[i] = 0;
+    if (queue_counters && i < 2 * QUEUE_COUNTERS) queue_counters[i] = 0;
+}
+
+// The one product of the MODE_LAYER launch that depends on the target: per (layer, tile) the loss sums of the layer alone, relative
+// to "nothing rendered".  The layer's key tile is still in ra.layers from the pass that drew it — that launch stores the whole
+// merged tile, empties included, for every tile whose bit in the representative's mask_lo is set (raster_tile leaves early on that
+// bit alone when MODE == MODE_LAYER, never on an empty list, and the layer queue holds exactly the pairs with the bit), with and
+// without a parent level — so the sums are score_tile over that tile in global memory, as score_gtile_kernel takes them from a
+// merged tile.  Integer sums modulo 2^64, whatever the order: the same words, bit for bit, as raster_tile's own score_tile call.
+// Grid = (tiles, layers).  A streaming kernel: a thread reads four 16-byte groups of keys, and the target words of the groups that
+// hold anything; twelve waves a workgroup, no LDS beyond the sums, so a CU holds as many as its wave slots allow.
+template <int LOSS>
+__global__ void __launch_bounds__(NTHREADS)
+layer_sums_kernel(FrameParams fp, RasterArgs ra)
+{
+    __shared__ uint64_t lds_sums[ROPE_SUM_WORDS];
+    const int tid = threadIdx.x, tile_id = blockIdx.x, row = blockIdx.y, n_tiles = fp.tiles_x * fp.tiles_y;
+    const int cand = ra.cand_of_row[row];
+    if (!((ra.mask_lo[(size_t)cand * ra.mask_words + (tile_id >> 5)] >> (tile_id & 31)) & 1u)) return;      // nobody reads this pair's sums
+    const size_t frame = ra.frame_of ? (size_t)ra.frame_of[cand] : 0, plane = (size_t)fp.W * fp.H;
+    const uint64_t *__restrict__ tq = ra.tq ? ra.tq + frame * plane : nullptr;
+    const float *__restrict__ t32 = ra.t32 ? ra.t32 + frame * plane : nullptr;
+    if (tid < ROPE_SUM_WORDS) lds_sums[tid] = 0;
+    __syncthreads();
+    const size_t slot = (size_t)row * n_tiles + tile_id;
+    const int tx = tile_id % fp.tiles_x, ty = tile_id / fp.tiles_x;
+    score_tile<LOSS, true>(ra.layers + slot * (TILE_W * TILE_H), nullptr, ty * TILE_H, tx * TILE_W, fp, ra.n_render, tq, t32, nullptr, lds_sums,
+                           TileRect{0, TILE_H - 1, 0, TILE_W / 4 - 1, 4});
+    __syncthreads();
+    if (tid < ROPE_SUM_WORDS) ra.layer_sums[slot * ROPE_SUM_WORDS + tid] = lds_sums[tid];
+}
+
 // ------------------------------------------------------------- lookup table -----
 // Lookup stage against a stored table (predict.py:165-171): per row k of the table, the exact sums of |T - sqrtD_k| in Q32
 // over the crop.  The crop is the box of every pose of the grid; one pose covers a fraction of it, and where a row holds
@@ -1949,6 +1992,26 @@ hipError_t launch_score_gtile(int loss, int rows, int slices, hipStream_t st, co
     case ROPE_LOSS_LOOKUP: hipLaunchKernelGGL(score_gtile_kernel<ROPE_LOSS_LOOKUP>, grid, dim3(256), 0, st, fp, a); break;
     case ROPE_LOSS_CAMFULL: hipLaunchKernelGGL(score_gtile_kernel<ROPE_LOSS_CAMFULL>, grid, dim3(256), 0, st, fp, a); break;
     default: hipLaunchKernelGGL(score_gtile_kernel<ROPE_LOSS_TSWEEP>, grid, dim3(256), 0, st, fp, a); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_clear_pass(hipStream_t st, uint64_t *sums, int C, int *queue_counters)
+{
+    const size_t n_words = (size_t)C * ROPE_SUM_WORDS;
+    hipLaunchKernelGGL(clear_pass_kernel, dim3((unsigned)((std::max<size_t>(n_words, 2 * QUEUE_COUNTERS) + 255) / 256)), dim3(256), 0, st, sums, n_words, queue_counters);
+    return hipGetLastError();
+}
+
+hipError_t launch_layer_sums(int loss, int n_layers, hipStream_t st, const FrameParams &fp, const RasterArgs &a)
+{
+    const dim3 grid(fp.tiles_x * fp.tiles_y, n_layers);
+    switch (loss) {
+    case ROPE_LOSS_DEPTH: hipLaunchKernelGGL(layer_sums_kernel<ROPE_LOSS_DEPTH>, grid, dim3(NTHREADS), 0, st, fp, a); break;
+    case ROPE_LOSS_FULL: hipLaunchKernelGGL(layer_sums_kernel<ROPE_LOSS_FULL>, grid, dim3(NTHREADS), 0, st, fp, a); break;
+    case ROPE_LOSS_LOOKUP: hipLaunchKernelGGL(layer_sums_kernel<ROPE_LOSS_LOOKUP>, grid, dim3(NTHREADS), 0, st, fp, a); break;
+    case ROPE_LOSS_TSWEEP: hipLaunchKernelGGL(layer_sums_kernel<ROPE_LOSS_TSWEEP>, grid, dim3(NTHREADS), 0, st, fp, a); break;
+    default: return hipErrorInvalidValue;          // the camera-pose loss has no shared layers
     }
     return hipGetLastError();
 }

@@ -26,7 +26,7 @@ TQ_MAX = (1 << 39) - 1
 ABI_SYMBOLS = (
     'rope_create', 'rope_destroy', 'rope_last_error', 'rope_set_robot', 'rope_set_camera', 'rope_set_target',
     'rope_candidates_upload', 'rope_eval_resident', 'rope_sync', 'rope_results_download', 'rope_eval',
-    'rope_lookup_build', 'rope_lookup_score', 'rope_render', 'rope_render_batch', 'rope_render_masks', 'rope_trace_contours', 'rope_coverage', 'rope_debug_mvp', 'rope_profile_eval', 'rope_set_strategy',
+    'rope_lookup_build', 'rope_lookup_score', 'rope_render', 'rope_render_batch', 'rope_render_masks', 'rope_trace_contours', 'rope_coverage', 'rope_debug_mvp', 'rope_profile_eval', 'rope_set_strategy', 'rope_geometry_cache_stats',
     'rope_set_frames', 'rope_eval_views', 'rope_predict', 'rope_set_robot_mesh', 'rope_partition_mesh', 'rope_pack_target', 'rope_downsample_even',
     'rope_seg_nms', 'rope_seg_roi_align', 'rope_seg_bias_act', 'rope_seg_mask_overlaps',
     'rope_seg_rpn_targets', 'rope_seg_roi_targets', 'rope_seg_roi_align_float', 'rope_seg_roi_align_backward',
@@ -131,6 +131,7 @@ def load_library(path: str = None):
     lib.rope_debug_mvp.argtypes = [vp, vp, i32, i32]
     lib.rope_profile_eval.argtypes = [vp, i32, i32, vp, i32, vp]
     lib.rope_set_strategy.argtypes = [vp, i32]
+    lib.rope_geometry_cache_stats.argtypes = [vp, vp, vp]
     if hasattr(lib, 'rope_debug_skip'):                 # librope_hip_profile.so only (ROPE_HIP_LIB=...)
         lib.rope_debug_skip.argtypes = [vp, i32]
         lib.rope_debug_clock.argtypes = [vp, vp]
@@ -920,13 +921,19 @@ class Engine:
         self._check(self._lib.rope_debug_mvp(self._ctx, _p(out), int(C_), int(n_render)), 'rope_debug_mvp')
         return out
 
-    NO_LAYERS, NO_SPLIT, NO_PARENTS, NO_QUEUE, CLIP_KERNELS, SEPARATE_GEOMETRY = 1, 2, 4, 8, 16, 32
+    NO_LAYERS, NO_SPLIT, NO_PARENTS, NO_QUEUE, CLIP_KERNELS, SEPARATE_GEOMETRY, NO_GEOMETRY_CACHE = 1, 2, 4, 8, 16, 32, 64
 
     def set_strategy(self, flags: int):
         """rope_set_strategy: launch structure only (shared layers / small-batch split / second sharing level off);
         results are bit-identical for every value."""
         self._check(self._lib.rope_set_strategy(self._ctx, int(flags)), 'rope_set_strategy')
         self._strategy = int(flags)
+
+    def geometry_cache_stats(self):
+        """rope_geometry_cache_stats -> (hits, misses): large layered passes that ran on the geometry the pass before left / built it."""
+        hits, misses = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.rope_geometry_cache_stats(self._ctx, C.byref(hits), C.byref(misses)), 'rope_geometry_cache_stats')
+        return int(hits.value), int(misses.value)
 
     def debug_skip(self, mask: int):
         """Kernel-phase ablation; only the profiling build of the library has it (tools/build_variants.py profile)."""
