@@ -197,6 +197,18 @@ __device__ static inline void acc_sq(uint64_t *s, uint64_t dq)
     acc<NEG>(s[SUM_BB], (uint64_t)b * b);
 }
 
+// The same for the differences of the float losses, which reach 2^32 (a lookup target just below it where nothing is drawn):
+// a = dq >> 20 has up to 44 bits there, and the products are taken modulo 2^64 as the oracle takes them.
+template <bool NEG>
+__device__ static inline void acc_sq_wide(uint64_t *s, uint64_t dq)
+{
+    const uint64_t a = dq >> 20, b = dq & 0xFFFFFu;
+    acc<NEG>(s[SUM_S1], dq);
+    acc<NEG>(s[SUM_AA], a * a);
+    acc<NEG>(s[SUM_AB], a * b);
+    acc<NEG>(s[SUM_BB], b * b);
+}
+
 // Loss terms of one pixel given its z-buffer key.  `pix` indexes the H x W target planes.
 template <int LOSS, bool NEG = false>
 __device__ static inline void score_pixel(uint32_t key, size_t pix, int n_render, const uint64_t t /* tq[pix] */,
@@ -211,7 +223,7 @@ __device__ static inline void score_pixel(uint32_t key, size_t pix, int n_render
         if (LOSS == ROPE_LOSS_TSWEEP) a = sqrtf(a);
         float diff = fabsf(a - sqrtf(z));
         uint64_t dq = q32_of_f32(diff);
-        if (dq) acc_sq<NEG>(s, dq);
+        if (dq) acc_sq_wide<NEG>(s, dq);
         return;
     }
     if (LOSS == ROPE_LOSS_CAMFULL) {
@@ -1557,7 +1569,7 @@ crop_total_kernel(FrameParams fp, const float *__restrict__ t32, float *__restri
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             t[j] = c + j < cw ? src[j] : 0.0f;
-            acc_sq<false>(s, q32_of_f32(fabsf(t[j] - 0.0f)));
+            acc_sq_wide<false>(s, q32_of_f32(fabsf(t[j] - 0.0f)));
         }
         reinterpret_cast<float4 *>(t32c)[g] = make_float4(t[0], t[1], t[2], t[3]);
     }
@@ -1646,10 +1658,10 @@ table_fill_kernel(int cw, int ch, const float *__restrict__ table, const unsigne
 // One group against one cropped target: s += sum of |T - D| minus sum of |T| over its four samples (words S1, AA, AB, BB), modulo 2^64.
 __device__ static inline void table_group_delta(const float4 t, const float4 d, uint64_t *s)
 {
-    acc_sq<false>(s, q32_of_f32(fabsf(t.x - d.x))); acc_sq<true>(s, q32_of_f32(fabsf(t.x - 0.0f)));
-    acc_sq<false>(s, q32_of_f32(fabsf(t.y - d.y))); acc_sq<true>(s, q32_of_f32(fabsf(t.y - 0.0f)));
-    acc_sq<false>(s, q32_of_f32(fabsf(t.z - d.z))); acc_sq<true>(s, q32_of_f32(fabsf(t.z - 0.0f)));
-    acc_sq<false>(s, q32_of_f32(fabsf(t.w - d.w))); acc_sq<true>(s, q32_of_f32(fabsf(t.w - 0.0f)));
+    acc_sq_wide<false>(s, q32_of_f32(fabsf(t.x - d.x))); acc_sq_wide<true>(s, q32_of_f32(fabsf(t.x - 0.0f)));
+    acc_sq_wide<false>(s, q32_of_f32(fabsf(t.y - d.y))); acc_sq_wide<true>(s, q32_of_f32(fabsf(t.y - 0.0f)));
+    acc_sq_wide<false>(s, q32_of_f32(fabsf(t.z - d.z))); acc_sq_wide<true>(s, q32_of_f32(fabsf(t.z - 0.0f)));
+    acc_sq_wide<false>(s, q32_of_f32(fabsf(t.w - d.w))); acc_sq_wide<true>(s, q32_of_f32(fabsf(t.w - 0.0f)));
 }
 
 __global__ void __launch_bounds__(256)
