@@ -739,6 +739,34 @@ int rope_camera_normal_equations(const float *render_depth_dev, const uint8_t *r
                                  int W, int n_links, float fx, float fy, float cx, float cy, const double *twists_dev, int n_cols, float clip_m,
                                  double *out_dev, double *work_dev, void *stream);
 
+/* rope_bundle_normal_equations: the normal equations with respect to the joint angles AND the camera pose in ONE system of twelve
+ * column slots (csrc/rope_bundle.hip; prediction/refinement.py, BundleRefiner; tests/bundle_ref.py restates the text below in
+ * numpy).  The planes, n_links, fx .. cy, clip_m, out_dev, the stream, the arithmetic rule, steps 1 and 2, RENDERED, VALID, BOTH
+ * and r of step 3 and the text on determinism are rope_pose_normal_equations'; what differs:
+ *   joints_dev, n_joints n_frames x n_joints x 6 doubles as rope_pose_normal_equations takes them; n_joints 0 .. 6
+ *   twists_dev, n_cols   n_frames x n_cols x 6 doubles as rope_camera_normal_equations takes them; n_cols 0 .. 6
+ *                        n_joints + n_cols >= 1.  A pointer whose count is 0 is not read and may be null
+ *   out_dev              n_frames x ROPE_BNEQ_WORDS doubles; written completely
+ *   work_dev             rope_bundle_normal_workspace(n_frames, H, W) bytes, DEVICE, 8-byte aligned
+ *   Slots.  Slot c = j (0 .. 5) is joint j: J_c is step 5's J_j, so link l moves with the joints j < min(l, n_joints) and the base
+ *     with none.  Slot c = 6 + k (0 .. 5) is camera column k: J_c is step 5''s J_k.  J_c = 0 for a joint slot >= n_joints and for a
+ *     camera slot >= 6 + n_cols.
+ *   INLIER is rule 4': both, |r| <= clip, a normal, the test on nP — EVERY drawn link counts, the base too.  A base pixel has zero
+ *     joint entries and camera entries that are not: that is what tells joint 0 from a camera orbiting about joint 0's axis.
+ * Per frame:  [0] BOTH pixels   [1] the truncated cost sum   [2] inliers   [3] sum over inliers of r r   [4 + c] sum of J_c r, c < 12
+ *   [16 .. 93] sum of J_a J_b for a <= b, row by row over the twelve slots (0.0 0.1 .. 0.11 1.1 .. 11.11: 78 words)   [94], [95] 0.
+ *   Every entry with a slot that is 0 by the rule above is exactly 0.  On the same planes [0] .. [3] and the camera block are
+ *   rope_camera_normal_equations' sums and the joint block is rope_pose_normal_equations' (a base pixel adds zeros to it), each up
+ *   to the order of the summation.
+ * ROPE_E_ARG, with nothing enqueued and out_dev untouched, for every case of rope_pose_normal_equations but its n_joints rule, and
+ * for n_joints or n_cols outside 0 .. 6, both 0, a null or misaligned joints_dev with n_joints > 0, a null or misaligned twists_dev
+ * with n_cols > 0.  rope_bundle_normal_workspace (host only): the bytes of work_dev; 0 for a shape the call refuses. */
+#define ROPE_BNEQ_WORDS 96
+int rope_bundle_normal_equations(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames, int H,
+                                 int W, int n_links, float fx, float fy, float cx, float cy, const double *joints_dev, int n_joints,
+                                 const double *twists_dev, int n_cols, float clip_m, double *out_dev, double *work_dev, void *stream);
+size_t rope_bundle_normal_workspace(int n_frames, int H, int W);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

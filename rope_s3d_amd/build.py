@@ -9,7 +9,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB_PATH = os.path.join(_CSRC, 'librope_hip.so')
 _SOURCES = ['rope_kernels.hip', 'rope_abi.hip', 'rope_abi_targets.hip', 'rope_hostprep.cpp', 'rope_seg.hip', 'rope_masks.hip',
             'rope_predict.cpp', 'rope_meshlets.cpp', 'rope_contours.cpp', 'rope_train.hip', 'rope_targets.hip', 'rope_synth.hip',
-            'rope_eval.hip', 'rope_verify.hip', 'rope_feed.hip', 'rope_shade.hip', 'rope_refine.hip']
+            'rope_eval.hip', 'rope_verify.hip', 'rope_feed.hip', 'rope_shade.hip', 'rope_refine.hip', 'rope_bundle.hip']
 _DEPS = _SOURCES + ['rope_kernels.h', 'rope_buffers.h', 'rope_ctx.h', 'rope_geomcache.h', os.path.join('..', '..', 'include', 'rope_s3d.h')]
 
 # -ffp-contract=off: the arithmetic contract with the CPU oracle is "one IEEE operation per
@@ -93,17 +93,19 @@ def parse_resource_remarks(text: str) -> list:
     return records
 
 
-def resource_usage() -> list:
-    """What the compiler says every kernel of rope_kernels.hip needs in the shipped build: a device-only compile with HIPCC_FLAGS
+def resource_usage(source: str = 'rope_kernels.hip') -> list:
+    """What the compiler says every kernel of `source` (a file of _SOURCES; rope_kernels.hip unless asked) needs in the shipped build: a device-only compile with HIPCC_FLAGS
     (and ROPE_HIPCC_EXTRA, so that a variant is judged by the same rule) plus the resource-usage remarks, into a temporary
     directory — librope_hip.so is neither read nor written.  -> records {symbol, kernel, loss, mode, clip (None outside the raster
     templates), vgprs, agprs, sgprs, vgpr_spills, sgpr_spills, scratch_bytes (per lane), occupancy (waves/SIMD), lds_bytes}."""
+    if source not in _SOURCES:
+        raise ValueError(f"{source}: not a source of the library ({', '.join(_SOURCES)})")
     hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
     extra = os.environ.get('ROPE_HIPCC_EXTRA', '').split()
     flags = [f for f in HIPCC_FLAGS if f != '-shared']
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = [hipcc] + flags + [f'-DROPE_BUILD_ID="{source_hash()}"'] + extra + ['--cuda-device-only', '-c', _REMARK, 'rope_kernels.hip',
-                                                                                 '-o', os.path.join(tmp, 'rope_kernels.device.o')]
+        cmd = [hipcc] + flags + [f'-DROPE_BUILD_ID="{source_hash()}"'] + extra + ['--cuda-device-only', '-c', _REMARK, source,
+                                                                                 '-o', os.path.join(tmp, os.path.splitext(source)[0] + '.device.o')]
         r = subprocess.run(cmd, cwd=_CSRC, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"{' '.join(cmd)} failed ({r.returncode}):\n{r.stderr[-4000:]}")

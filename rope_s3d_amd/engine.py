@@ -17,6 +17,7 @@ SUM_WORDS = 23
 AGREE_WORDS = 28                 # ROPE_AGREE_WORDS (include/rope_s3d.h): the words rope_frame_agreement writes per frame
 SHADE_MAX_NOISE_Q = 1023         # ROPE_SHADE_MAX_NOISE_Q
 NEQ_WORDS = 32                   # ROPE_NEQ_WORDS: the doubles rope_pose_normal_equations writes per frame
+BNEQ_WORDS = 96                  # ROPE_BNEQ_WORDS: the doubles rope_bundle_normal_equations writes per frame
 # rope_shade_params (include/rope_s3d.h), 64 bytes a record
 SHADE_DTYPE = np.dtype([('light', '<f4', 3), ('ambient', '<f4'), ('gain', '<f4', 3), ('bg_depth', '<f4'), ('noise_q', '<i4'), ('bg_index', '<i4'),
                         ('albedo', 'u1', (6, 3)), ('bg_colour', 'u1', 3), ('reserved', 'u1', 3)])
@@ -35,7 +36,8 @@ ABI_SYMBOLS = (
     'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets',
     'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes', 'rope_frame_agreement',
     'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align',
-    'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace', 'rope_camera_normal_equations')
+    'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace', 'rope_camera_normal_equations',
+    'rope_bundle_normal_equations', 'rope_bundle_normal_workspace')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -162,6 +164,10 @@ def load_library(path: str = None):
     lib.rope_camera_normal_equations.argtypes = list(lib.rope_pose_normal_equations.argtypes)
     lib.rope_pose_normal_workspace.argtypes = [i32, i32, i32]
     lib.rope_pose_normal_workspace.restype = C.c_size_t
+    lib.rope_bundle_normal_equations.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, i32, vp, i32,
+                                                 C.c_float, vp, vp, vp]
+    lib.rope_bundle_normal_workspace.argtypes = [i32, i32, i32]
+    lib.rope_bundle_normal_workspace.restype = C.c_size_t
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_eval_views.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.rope_set_target_tsweep.argtypes = [vp, vp]
@@ -627,6 +633,54 @@ class Engine:
         else — the planes, intr, the stream, determinism, the empty batch — is pose_normal_equations'."""
         return self._normal_equations('rope_camera_normal_equations', render_depth, render_ids, frame_depth, twists, 'twists',
                                       'angular and linear part per column', n_links, clip, intr)
+
+    def bundle_normal_equations(self, render_depth, render_ids, frame_depth, joint_axes, twists, n_links: int, clip: float, intr) -> np.ndarray:
+        """rope_bundle_normal_equations: the joints' and the camera's columns in ONE system of twelve slots -> (N, 96) float64, per
+        frame [0] .. [3] as camera_normal_equations', [4 + c] J_c^T r, [16..93] the upper triangle of J^T J row by row over the
+        twelve slots, [94], [95] 0; slot j < 6 is joint j (pose_normal_equations' column), slot 6 + k camera column k
+        (camera_normal_equations'), and every drawn link is an inlier, the base too (include/rope_s3d.h).  joint_axes
+        (N, n_joints, 6) and twists (N, n_cols, 6) float64 as those two calls take them; either may be None (no such columns), not
+        both.  Everything else — the planes, intr, the stream, determinism, the empty batch — is pose_normal_equations'."""
+        import torch
+        for name, t, dt in (('render_depth', render_depth, torch.float32), ('render_ids', render_ids, torch.uint8),
+                            ('frame_depth', frame_depth, torch.float32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
+            if t.device.type != 'cuda' or t.device.index != self.device:
+                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
+            if t.shape != render_depth.shape:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {tuple(render_depth.shape)}")
+        N, H, W = render_depth.shape
+        dev = render_depth.device
+        if joint_axes is None and twists is None:
+            raise ValueError("joint_axes and twists: at least one of them")
+        cols = []
+        for name, c, what in (('joint_axes', joint_axes, 'axis and a point on it per joint'), ('twists', twists, 'angular and linear part per column')):
+            if c is not None and not isinstance(c, torch.Tensor):
+                c = torch.from_numpy(np.ascontiguousarray(c, np.float64))
+            if c is not None and (c.dtype != torch.float64 or c.dim() != 3 or c.shape[0] != N or c.shape[2] != 6):
+                raise ValueError(f"{name}: ({N}, n, 6) float64 — {what}, got {tuple(c.shape)} {c.dtype}")
+            cols.append(c)
+        counts = [0 if c is None else int(c.shape[1]) for c in cols]
+        if N == 0:
+            return np.zeros((0, BNEQ_WORDS), np.float64)
+        fx, fy, cx, cy = (float(v) for v in intr)
+        with torch.cuda.device(dev):
+            cols = [None if c is None or n == 0 else c.to(dev).contiguous() for c, n in zip(cols, counts)]
+            ptrs = [None if c is None else C.c_void_p(c.data_ptr()) for c in cols]
+            out = torch.empty((N, BNEQ_WORDS), dtype=torch.float64, device=dev)
+            work = torch.empty(max(1, self._lib.rope_bundle_normal_workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
+            rc = self._lib.rope_bundle_normal_equations(C.c_void_p(render_depth.data_ptr()), C.c_void_p(render_ids.data_ptr()),
+                                                        C.c_void_p(frame_depth.data_ptr()), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
+                                                        ptrs[0], counts[0], ptrs[1], counts[1], float(clip), C.c_void_p(out.data_ptr()),
+                                                        C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if rc == -1:
+                raise ValueError(f"rope_bundle_normal_equations refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), n_links "
+                                 f"{n_links} (1 .. 6), {counts[0]} joints and {counts[1]} twists (0 .. 6 each, not both 0), clip {clip} (finite, "
+                                 f"positive), intrinsics {(fx, fy, cx, cy)}")
+            if rc:
+                raise EngineError(f"rope_bundle_normal_equations failed ({rc})")
+            return out.cpu().numpy()
 
     def _normal_equations(self, entry: str, render_depth, render_ids, frame_depth, columns, col_name: str, col_what: str, n_links: int,
                           clip: float, intr) -> np.ndarray:

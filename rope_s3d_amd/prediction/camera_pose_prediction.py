@@ -124,7 +124,9 @@ class _CameraStageMachine:
 
     def __init__(self, base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine=False):
         self.base_pose = np.array(base_pose, dtype=float)
-        self.refine, self.last_refinement, self._refiner = bool(refine), None, None
+        if isinstance(refine, str) and refine != 'bundle':
+            raise ValueError(f"refine: True, False or 'bundle', got {refine!r}")
+        self.refine, self.last_refinement, self._refiner = refine if refine == 'bundle' else bool(refine), None, None
         self.ds_factor, self.preview = ds_factor, preview
         self.min_ang_inc = np.asarray(min_angle_inc, dtype=float)
         self.history_length = history_length
@@ -323,13 +325,16 @@ class _CameraStageMachine:
 
     def _polish(self, pose: np.ndarray) -> np.ndarray:
         """The continuous last step (refinement.CameraPoseRefiner) on the pose the stages ended on, against the down-sampled depth
-        frames of this run at the working resolution; `last_refinement` keeps its result.  With the switch off: the pose as it is."""
+        frames of this run at the working resolution; `last_refinement` keeps its result.  With the switch off: the pose as it is.
+        refine='bundle': refinement.BundleRefiner in 'frame' mode instead — S, L and U of every frame are unknowns beside the camera,
+        so an encoder error is not absorbed into the pose; the caller's recorded angles are not changed."""
         self.last_refinement = None
         if not self.refine:
             return pose
         if self._refiner is None:
-            from .refinement import CameraPoseRefiner
-            self._refiner = CameraPoseRefiner(self.renderer, self.renderer.intrinsics)
+            from .refinement import BundleRefiner, CameraPoseRefiner
+            self._refiner = (BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame') if self.refine == 'bundle'
+                             else CameraPoseRefiner(self.renderer, self.renderer.intrinsics))
         self.last_refinement = self._refiner.refine(pose, self.robot_poses, np.asarray(self._tgt_depths, np.float32))
         return self.last_refinement.pose.copy()
 
@@ -383,9 +388,10 @@ class ModellessCameraPredictor(_CameraStageMachine):
 
     def __init__(self, base_pose=DEFAULT_CAMERA_POSE, ds_factor: int = 8, preview: bool = False, save_to: str = None,
                  min_angle_inc=np.array([0.001, 0.001, 0.001, 0.002, 0.002, 0.002]), history_length=5,
-                 base_intrinsics='1280_720_color', *, device: int = 0, refine: bool = False):
-        """`refine`: polish the pose the stages end on with refinement.CameraPoseRefiner and keep its CameraRefineResult (the
-        pooled formal sigma of the six parameters, every frame's own cost) in `last_refinement`."""
+                 base_intrinsics='1280_720_color', *, device: int = 0, refine=False):
+        """`refine`: True polishes the pose the stages end on with refinement.CameraPoseRefiner and keeps its CameraRefineResult (the
+        pooled formal sigma of the six parameters, every frame's own cost) in `last_refinement`; 'bundle' polishes it together with
+        every frame's S, L and U (refinement.BundleRefiner, 'frame' mode) and keeps the BundleRefineResult."""
         super().__init__(base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine)
 
     def _setStages(self):
@@ -426,7 +432,7 @@ class CameraPredictor(_CameraStageMachine):
 
     def __init__(self, base_pose=DEFAULT_CAMERA_POSE, ds_factor: int = 8, preview: bool = False, save_to: str = None,
                  min_angle_inc=np.array([0.001, 0.001, 0.001, 0.002, 0.002, 0.002]), history_length=5,
-                 base_intrinsics='1280_720_color', *, device: int = 0, segmenter: Optional[Callable] = None, refine: bool = False):
+                 base_intrinsics='1280_720_color', *, device: int = 0, segmenter: Optional[Callable] = None, refine=False):
         """`segmenter`: callable(colour uint8 HxWx3) -> {'class_ids', 'rois', 'scores', 'masks' (H,W,K) bool}; stands in
         for pixellib's segmentImage on "models/segmentation/multi/B.h5" (:603-606,687).  `refine`: as ModellessCameraPredictor's;
         the polish is against the whole down-sampled depth frames, not the per-link planes."""

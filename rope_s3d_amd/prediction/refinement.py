@@ -95,6 +95,27 @@ def mean_cost(words: np.ndarray) -> np.ndarray:
     return np.where(w[:, 0] > 0, w[:, 1] / np.where(w[:, 0] > 0, w[:, 0], 1.0), np.inf)
 
 
+def joint_axes_camera(fk, Rwc, tc, angles: np.ndarray) -> np.ndarray:
+    """(N, 6) angles -> (N, 6, 6): per joint its unit axis and a point on it at those angles, in the kernel's camera axes
+    X_c = Rwc (X_w - tc)."""
+    angles = np.asarray(angles, np.float64).reshape(-1, 6)
+    N = len(angles)
+    out = np.empty((N, 6, 6))
+    R = np.broadcast_to(np.eye(3), (N, 3, 3))          # ForwardKinematics.calc's chain, all frames at once
+    t = np.zeros((N, 3))
+    eye = np.eye(3)
+    for j in range(6):
+        a = fk.axes[j]
+        K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+        s, c = np.sin(angles[:, j])[:, None, None], np.cos(angles[:, j])[:, None, None]
+        rot = c * eye + s * K + (1 - c) * np.outer(a, a)
+        t = t + R @ fk.fixed[j, :, 3]
+        R = R @ (fk.fixed[j, :, :3] @ rot)
+        out[:, j, :3] = (R @ a) @ Rwc.T
+        out[:, j, 3:] = (t - tc) @ Rwc.T
+    return out
+
+
 class PoseRefiner:
     """renderer_or_engine  a simulation.render.Renderer (its camera is moved to camera_pose here unless it stands there) — or an
                         Engine on which robot and camera are set already, all links rendered
@@ -137,22 +158,7 @@ class PoseRefiner:
 
     def joint_axes(self, angles: np.ndarray) -> np.ndarray:
         """(N, 6) angles -> (N, 6, 6): per joint its unit axis and a point on it, in camera axes, at those angles."""
-        angles = np.asarray(angles, np.float64).reshape(-1, 6)
-        N = len(angles)
-        out = np.empty((N, 6, 6))
-        R = np.broadcast_to(np.eye(3), (N, 3, 3))          # ForwardKinematics.calc's chain, all frames at once
-        t = np.zeros((N, 3))
-        eye = np.eye(3)
-        for j in range(6):
-            a = self.fk.axes[j]
-            K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-            s, c = np.sin(angles[:, j])[:, None, None], np.cos(angles[:, j])[:, None, None]
-            rot = c * eye + s * K + (1 - c) * np.outer(a, a)
-            t = t + R @ self.fk.fixed[j, :, 3]
-            R = R @ (self.fk.fixed[j, :, :3] @ rot)
-            out[:, j, :3] = (R @ a) @ self._Rwc.T
-            out[:, j, 3:] = (t - self._tc) @ self._Rwc.T
-        return out
+        return joint_axes_camera(self.fk, self._Rwc, self._tc, angles)
 
     def _render(self, angles):
         return self.engine.render_batch_device(np.ascontiguousarray(angles, np.float64), self.n_links, None)
@@ -316,3 +322,269 @@ class CameraPoseRefiner:
             else:
                 lam *= 10.0
         return CameraRefineResult(pose, formal_sigma(pooled, self.active), cost_before, cost, steps, float(pooled[2]), mean_cost(words))
+
+
+# ---------------------------------------------------------------------------------------------- angles and camera in one solve
+BNEQ_WORDS = 96
+BNEQ_SLOTS = 12
+
+
+@dataclass
+class BundleRefineResult:
+    """What BundleRefiner.refine returns: one camera and every frame's angles, from one system."""
+    pose: np.ndarray            # (6,) the refined [x, y, z, a3, a4, a5]; parameters outside do_params as they came
+    angles: np.ndarray          # (N, 6) the refined angles ('offset': the input angles plus the offsets); other joints as they came
+    offsets: np.ndarray         # (6,) 'offset' mode: the joints' zero offsets, 0 outside do_angles; nan in 'frame' mode
+    sigma_pose: np.ndarray      # (6,) formal standard deviation, m and rad, with the angles (or offsets) unknown as well
+    sigma_angles: np.ndarray    # (N, 6) 'frame' mode, rad; None in 'offset' mode
+    sigma_offsets: np.ndarray   # (6,) 'offset' mode, rad; None in 'frame' mode
+    cost_before: float          # pooled mean truncated squared residual at the start, m^2 (inf: nothing to compare)
+    cost_after: float           # the same at the end; never larger than cost_before
+    steps_taken: int            # accepted steps, 0 .. iterations
+    inliers: float              # pixels of all frames that carried the final system
+    frame_cost: np.ndarray      # (N,) every frame's own mean truncated cost at the end
+
+
+def unpack_bundle(words: np.ndarray):
+    """One frame's (or the pooled) 96 words -> (A (12, 12) = J^T J, g (12,) = J^T r); slots 0 .. 5 the joints, 6 .. 11 the camera."""
+    A = np.zeros((BNEQ_SLOTS, BNEQ_SLOTS))
+    A[np.triu_indices(BNEQ_SLOTS)] = words[16:94]
+    return A + np.triu(A, 1).T, np.array(words[4:16], np.float64)
+
+
+def pool_bundle(words: np.ndarray) -> np.ndarray:
+    """(N, 96) -> (96,): pool_frames for the bundle's words, added in frame order."""
+    pooled = np.zeros(BNEQ_WORDS)
+    for w in np.asarray(words, np.float64).reshape(-1, BNEQ_WORDS):
+        pooled = pooled + w
+    return pooled
+
+
+def _solve_finite(M, rhs):
+    """np.linalg.solve; None for a singular matrix or a solution that is not finite."""
+    try:
+        x = np.linalg.solve(M, rhs)
+    except np.linalg.LinAlgError:
+        return None
+    return x if np.isfinite(x).all() else None
+
+
+def _arrow_blocks(words, active_j, active_c):
+    """-> ([(idx_f, A_f, B_f, g_f)] per frame, kc, C, gc): idx_f the active joints of the frame with a positive diagonal, kc the
+    active camera parameters with a positive diagonal in the pooled camera block C (the frames' added in frame order)."""
+    Ap, gp = unpack_bundle(pool_bundle(words))
+    kc = [k for k in active_c if Ap[6 + k, 6 + k] > 0]
+    cc = [6 + k for k in kc]
+    frames = []
+    for w in words:
+        A, g = unpack_bundle(w)
+        idx = [j for j in active_j if A[j, j] > 0]
+        frames.append((idx, A[np.ix_(idx, idx)], A[np.ix_(idx, cc)], g[idx]))
+    return frames, kc, Ap[np.ix_(cc, cc)], gp[cc]
+
+
+def schur_step(words: np.ndarray, active_j, active_c, lam: float):
+    """The Levenberg step of the block-arrow system (every frame's joints, one camera) by its Schur complement, never assembled
+    densely -> (dq (N, 6), dc (6,)).  D_f = A_f + lam diag A_f; S = C + lam diag C - sum B_f^T D_f^-1 B_f;
+    dc = -S^-1 (gc - sum B_f^T D_f^-1 g_f); dq_f = -D_f^-1 (g_f + B_f dc).  A singular D_f: a zero step for that frame's joints (the
+    frame leaves the sums); a singular S: a zero step for the camera."""
+    words = np.asarray(words, np.float64).reshape(-1, BNEQ_WORDS)
+    frames, kc, C, gc = _arrow_blocks(words, active_j, active_c)
+    dq, dc = np.zeros((len(words), 6)), np.zeros(6)
+    S = C + lam * np.diag(np.diag(C))
+    rhs = gc.copy()
+    solved = []
+    for idx, A, B, g in frames:
+        X = _solve_finite(A + lam * np.diag(np.diag(A)), np.column_stack([B, g])) if idx else None       # D_f^-1 [B_f, g_f]
+        solved.append(X)
+        if X is not None:
+            S = S - B.T @ X[:, :-1]
+            rhs = rhs - B.T @ X[:, -1]
+    d = _solve_finite(S, -rhs) if kc else None
+    if d is None:
+        d = np.zeros(len(kc))
+    dc[kc] = d
+    for f, ((idx, A, B, g), X) in enumerate(zip(frames, solved)):
+        if X is not None:
+            dq[f, idx] = -(X[:, -1] + X[:, :-1] @ d)
+    return dq, dc
+
+
+def schur_sigma(words: np.ndarray, active_j, active_c):
+    """formal_sigma for the arrow system at lam = 0 -> (sigma_angles (N, 6), sigma_pose (6,)): s^2 = sum [3] / (sum [2] - p) with p
+    all live unknowns, cov_c = S0^-1 and cov_qf = A_f^-1 + A_f^-1 B_f S0^-1 B_f^T A_f^-1.  inf for an active unknown with a zero
+    diagonal, for fewer inliers than p + 1 and for a singular block; nan for what is not refined.  FORMAL, as formal_sigma's: the
+    pixels are taken as independent measurements, which neighbours in a depth frame are not."""
+    words = np.asarray(words, np.float64).reshape(-1, BNEQ_WORDS)
+    sq, sc = np.full((len(words), 6), np.nan), np.full(6, np.nan)
+    sq[:, list(active_j)] = np.inf
+    sc[list(active_c)] = np.inf
+    frames, kc, C, _ = _arrow_blocks(words, active_j, active_c)
+    pooled = pool_bundle(words)
+    p = len(kc) + sum(len(fr[0]) for fr in frames)
+    if p == 0 or pooled[2] < p + 1:
+        return sq, sc
+    s2 = pooled[3] / (pooled[2] - p)
+    S0 = C.copy()
+    solved = []
+    for idx, A, B, g in frames:
+        X = _solve_finite(A, np.column_stack([B, np.eye(len(idx))])) if idx else None                     # A_f^-1 [B_f, I]
+        solved.append(X)
+        if X is not None:
+            S0 = S0 - B.T @ X[:, :len(kc)]
+    covc = _solve_finite(S0, np.eye(len(kc))) if kc else np.zeros((0, 0))
+    if covc is None:
+        return sq, sc
+    var = s2 * np.diag(covc)
+    if np.isfinite(var).all() and (var >= 0).all():
+        sc[kc] = np.sqrt(var)
+    for f, ((idx, A, B, g), X) in enumerate(zip(frames, solved)):
+        if X is None:
+            continue
+        Y, Ainv = X[:, :len(kc)], X[:, len(kc):]
+        var = s2 * np.diag(Ainv + Y @ covc @ Y.T)
+        if np.isfinite(var).all() and (var >= 0).all():
+            sq[f, idx] = np.sqrt(var)
+    return sq, sc
+
+
+def bundle_columns_step(pooled: np.ndarray, active, lam: float) -> np.ndarray:
+    """levenberg_step's rule over the twelve slots of a pooled system -> (12,)."""
+    A, g = unpack_bundle(pooled)
+    idx = [c for c in active if A[c, c] > 0]
+    d = np.zeros(BNEQ_SLOTS)
+    if idx:
+        S = A[np.ix_(idx, idx)]
+        sol = _solve_finite(S + lam * np.diag(np.diag(S)), -g[idx])
+        if sol is not None:
+            d[idx] = sol
+    return d
+
+
+def bundle_columns_sigma(pooled: np.ndarray, active) -> np.ndarray:
+    """formal_sigma's rule over the twelve slots of a pooled system -> (12,)."""
+    A, _ = unpack_bundle(pooled)
+    out = np.full(BNEQ_SLOTS, np.nan)
+    out[list(active)] = np.inf
+    idx = [c for c in active if A[c, c] > 0]
+    p = len(idx)
+    if p == 0 or pooled[2] < p + 1:
+        return out
+    cov = _solve_finite(A[np.ix_(idx, idx)], np.eye(p))
+    if cov is None:
+        return out
+    var = (pooled[3] / (pooled[2] - p)) * np.diag(cov)
+    if np.isfinite(var).all() and (var >= 0).all():
+        out[idx] = np.sqrt(var)
+    return out
+
+
+class BundleRefiner:
+    """Joint angles AND camera pose of N frames of one fixed camera polished in ONE Gauss-Newton / Levenberg system
+    (rope_bundle_normal_equations, csrc/rope_bundle.hip): PoseRefiner takes the camera as exact and CameraPoseRefiner the angles,
+    and each absorbs the other's error; here neither half is assumed, and the formal sigmas say what the views pin down then.
+
+    renderer_or_engine  as CameraPoseRefiner's: every render brings its own P V, the renderer's camera is neither read nor moved
+    intrinsics          projection.Intrinsics of the frames (the working resolution)
+    do_angles           the joints to refine, letters of 'SLUBRT'
+    do_params           the parameters of [x, y, z, a3, a4, a5] to refine
+    joints              'frame': every frame's active joints are unknowns of their own (a block-arrow system, solved by its Schur
+                        complement); 'offset': ONE zero offset per active joint, added to every frame's input angles (kinematic
+                        calibration: a pooled 12-column system)
+    clip, iterations, damping   as PoseRefiner's; ONE damping for the whole system, multiplied by 10 whenever a step is refused.
+                        A step is kept only if the pooled cost sum [1] / sum [0] over all frames is strictly smaller."""
+
+    def __init__(self, renderer_or_engine, intrinsics, do_angles: str = 'SLU', do_params=(True,) * 6, joints: str = 'frame',
+                 clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3):
+        if not (np.isfinite(clip) and clip > 0):
+            raise ValueError(f"clip must be finite and positive, got {clip}")
+        if iterations < 0 or not (np.isfinite(damping) and damping >= 0):
+            raise ValueError("iterations and damping must not be negative")
+        if joints not in ('frame', 'offset'):
+            raise ValueError(f"joints: 'frame' or 'offset', got {joints!r}")
+        do_params = np.asarray(do_params, bool).reshape(-1)
+        if len(do_params) != 6:
+            raise ValueError("do_params: six flags, one per pose parameter")
+        self.engine = renderer_or_engine.engine if hasattr(renderer_or_engine, 'render_ids_batch_device') else renderer_or_engine
+        self.intrinsics = intrinsics
+        self.active_j = [int(j) for j in np.flatnonzero(str_to_arr(do_angles.upper()))]
+        self.active_c = [int(k) for k in np.flatnonzero(do_params)]
+        if not self.active_j and not self.active_c:
+            raise ValueError("nothing to refine: do_angles and do_params are both empty")
+        self.mode = joints
+        self.clip, self.iterations, self.damping = float(clip), int(iterations), float(damping)
+        self.fk = ForwardKinematics()
+        self.limits = np.asarray(self.fk.reader.joint_limits, np.float64)
+
+    @property
+    def n_links(self) -> int:
+        return min(int(self.engine.n_links), NUM_RENDER_LINKS)
+
+    def joint_axes(self, pose, angles: np.ndarray) -> np.ndarray:
+        """PoseRefiner.joint_axes under the camera `pose` -> (N, 6, 6)."""
+        M = camera_pose_matrix(np.asarray(pose, np.float64))
+        return joint_axes_camera(self.fk, np.diag([1.0, -1.0, -1.0]) @ M[:3, :3].T, M[:3, 3].copy(), angles)
+
+    def equations(self, pose, angles: np.ndarray, depth_t) -> np.ndarray:
+        """One render of the N frames' angles under the camera `pose`, the joint axes and the twists there and one kernel call ->
+        (N, 96), per frame."""
+        from ..projection import camera_matrix
+        intr = self.intrinsics
+        angles = np.ascontiguousarray(angles, np.float64)
+        N = len(angles)
+        PV = np.tile(camera_matrix(pose, intr)[None], (N, 1, 1))
+        rd, ri = self.engine.render_batch_device(angles, self.n_links, PV)
+        axes = self.joint_axes(pose, angles) if self.active_j else None
+        twists = np.tile(camera_twists(pose)[None], (N, 1, 1)) if self.active_c else None
+        return self.engine.bundle_normal_equations(rd, ri, depth_t, axes, twists, self.n_links, self.clip, (intr.fx, intr.fy, intr.cx, intr.cy))
+
+    def refine(self, camera_pose, angles, depth) -> BundleRefineResult:
+        """camera_pose (6,); angles (N, 6); depth (N, H, W) metres at the refiner's resolution, a numpy array or a torch tensor on
+        the host or the device, 0 / NaN where nothing was measured.  The sigmas are FORMAL (schur_sigma, formal_sigma): good for
+        telling what the views pin down and for ranking, not error bars to be taken at face value."""
+        import torch
+        pose = np.array(camera_pose, np.float64).reshape(6)
+        q0 = np.ascontiguousarray(np.array(angles, np.float64).reshape(-1, 6))
+        N = len(q0)
+        frame_mode = self.mode == 'frame'
+        slots = self.active_j + [6 + k for k in self.active_c]
+        if N == 0:
+            sp, so = np.full(6, np.nan), np.full(6, np.nan)
+            sp[self.active_c], so[self.active_j] = np.inf, np.inf
+            return BundleRefineResult(pose, q0, np.full(6, np.nan) if frame_mode else np.zeros(6), sp, np.zeros((0, 6)) if frame_mode else None,
+                                      None if frame_mode else so, np.inf, np.inf, 0, 0.0, np.zeros(0))
+        device = torch.device('cuda', self.engine.device)
+        if not isinstance(depth, torch.Tensor):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32))
+        depth_t = depth.to(device=device, dtype=torch.float32).contiguous()
+        if depth_t.dim() != 3 or depth_t.shape[0] != N:
+            raise ValueError(f"depth: ({N}, H, W), got {tuple(depth_t.shape)}")
+        q, off = q0.copy(), np.zeros(6)
+        lam = self.damping
+        words = self.equations(pose, q, depth_t)
+        pooled = pool_bundle(words)
+        cost = float(mean_cost(pooled[None, :NEQ_WORDS])[0])
+        cost_before, steps = cost, 0
+        for _ in range(self.iterations):
+            if frame_mode:
+                dq, dc = schur_step(words, self.active_j, self.active_c, lam)
+                t_pose, t_off, t_q = pose + dc, off, np.clip(q + dq, self.limits[:, 0], self.limits[:, 1])
+            else:
+                d = bundle_columns_step(pooled, slots, lam)
+                t_pose, t_off = pose + d[6:], off + d[:6]
+                t_q = np.clip(q0 + t_off, self.limits[:, 0], self.limits[:, 1])
+            w_t = self.equations(t_pose, t_q, depth_t)
+            p_t = pool_bundle(w_t)
+            c_t = float(mean_cost(p_t[None, :NEQ_WORDS])[0])
+            if c_t < cost:                                              # strictly smaller, or everything is put back
+                pose, off, q, words, pooled, cost = t_pose, t_off, t_q, w_t, p_t, c_t
+                steps += 1
+            else:
+                lam *= 10.0
+        frame_cost = mean_cost(words[:, :NEQ_WORDS])
+        if frame_mode:
+            sq, sc = schur_sigma(words, self.active_j, self.active_c)
+            return BundleRefineResult(pose, q, np.full(6, np.nan), sc, sq, None, cost_before, cost, steps, float(pooled[2]), frame_cost)
+        s = bundle_columns_sigma(pooled, slots)
+        return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), s[6:], None, s[:6], cost_before, cost, steps,
+                                  float(pooled[2]), frame_cost)
