@@ -120,7 +120,7 @@ def test_holes_take_a_single_plane_and_refuse_what_the_kernel_cannot_hold(engine
 
 # ---- targets from device planes
 
-def _reference(depth, ids, f, n_lookup):
+def _reference(depth, ids, f, n_lookup, link_blue=LINK_BLUE):
     """rope_prepare_synthetic per frame on the colour plane LUT[ids] -> (tq, t32, tsweep, flags)."""
     n, H0, W0 = depth.shape
     H, W = H0 // f, W0 // f
@@ -129,16 +129,16 @@ def _reference(depth, ids, f, n_lookup):
         color = np.zeros((H0, W0, 3), np.uint8)
         color[..., 0] = LUT[ids[i]]
         tgt = np.empty((H, W), np.float64)
-        assert eng.prepare_synthetic(color, depth[i], f, LINK_BLUE, n_lookup, tq[i], t32[i], flags[i], tgt)
+        assert eng.prepare_synthetic(color, depth[i], f, link_blue, n_lookup, tq[i], t32[i], flags[i], tgt)
         with np.errstate(all='ignore'):
             ts[i] = tgt
     return tq, t32, ts, flags
 
 
-def _device(e, depth, ids, f, n_lookup, want_ts, calls):
+def _device(e, depth, ids, f, n_lookup, want_ts, calls, link_blue=LINK_BLUE):
     n = len(depth)
     for lo, hi in calls:
-        e.stage_targets_synthetic(torch.from_numpy(depth[lo:hi]).cuda(), torch.from_numpy(ids[lo:hi]).cuda(), f, LUT, LINK_BLUE, n_lookup, n, lo, want_ts)
+        e.stage_targets_synthetic(torch.from_numpy(depth[lo:hi]).cuda(), torch.from_numpy(ids[lo:hi]).cuda(), f, LUT, link_blue, n_lookup, n, lo, want_ts)
     e.commit_targets()
     return e.debug_targets(want_ts)
 
@@ -178,8 +178,9 @@ def _made_up(rng, H, W, f):
     return np.stack([depth, depth_r, depth_z]), np.stack([ids, ids_r, ids_z])
 
 
-# context size, f: the issue's three, and two whose pixel count is no multiple of the kernel's 256 pixels per workgroup (160 x 120 is)
-GEOMETRIES = [(120, 160, 1), (120, 160, 2), (24, 40, 8), (100, 150, 1), (118, 158, 2)]
+# context size, f: the issue's three, and two whose pixel count is no multiple of the kernel's 256 pixels per workgroup (160 x 120 is);
+# factors 4 and 6 (the taps f/2 - 1 and f/2 at a factor that is no power of two) on a context of 30 x 24
+GEOMETRIES = [(120, 160, 1), (120, 160, 2), (24, 40, 8), (100, 150, 1), (118, 158, 2), (24, 30, 4), (24, 30, 6)]
 
 
 @pytest.mark.parametrize('want_ts', [False, True], ids=['lookup plane only', 'with the TensorSweep plane'])
@@ -200,6 +201,70 @@ def test_staged_planes_equal_the_host_function(engines, H, W, f, want_ts):
     assert all((want[0][i] >> np.uint64(40)).any() for i in range(5)) and np.isnan(want[2][2]).any() and (want[1] != want[2])[~np.isnan(want[2])].any()
     assert want[3][3].tolist()[1:6] == [0, 1, 3, 0, 0], f"absent, five of a hundred, six of a hundred: {want[3][3]}"
     assert not (want[3][4][1:6] & 2).any() and want[3][4].any(), "depth 0 inside every mask: no link has depth"
+
+
+# context size, f: outputs of one pixel, one row and one column — a single workgroup whose live lanes are fewer than a wave
+SLIVERS = [(1, 1, 1), (1, 1, 2), (1, 1, 6), (1, 37, 1), (1, 37, 2), (23, 1, 4), (23, 1, 1)]
+
+
+@pytest.mark.parametrize('H,W,f', SLIVERS, ids=[f'{w}x{h} from {w * f}x{h * f}' for h, w, f in SLIVERS])
+def test_staged_slivers_equal_the_host_function(engines, H, W, f):
+    """Twelve windows of H f x W f cut out of each of _made_up's three frames, spread over them, so that the 36 tiny frames between
+    them hold pixels of several links, with and without depth, and special depths."""
+    e_t = engines[1]
+    _camera(e_t, H, W)
+    md, mi = _made_up(np.random.default_rng(100 * H + W + f), 24, 40, f)
+    cuts = [np.s_[:, y * f:(y + H) * f, x * f:(x + W) * f] for y in (0, (24 - H) // 2, 24 - H) for x in (0, (40 - W) // 3, 2 * (40 - W) // 3, 40 - W)]
+    depth, ids = np.ascontiguousarray(np.concatenate([md[c] for c in cuts])), np.ascontiguousarray(np.concatenate([mi[c] for c in cuts]))
+    want = _reference(depth, ids, f, 4)
+    got = _device(e_t, depth, ids, f, 4, True, [(0, 5), (5, 36)])
+    _check(got, want, True)
+    assert got[0].shape == (36, H, W)
+    # asserted on the reference: pixels of three links at the least, a NaN depth; links absent, without depth and with it
+    assert len(np.unique(want[0] >> np.uint64(40))) >= 4 and np.isnan(want[2]).any()
+    assert {0, 1, 3} <= set(want[3].ravel().tolist())
+
+
+# link_blue, n_lookup_links: tables other than the six links of the renderer with four lookup links
+LINK_TABLES = {
+    'links 1 and 2 share a colour': ([LINK_BLUE[0], LINK_BLUE[1], LINK_BLUE[1], LINK_BLUE[3], LINK_BLUE[4], LINK_BLUE[5]], 4),
+    'a lookup link and a later link share a colour': ([LINK_BLUE[0], LINK_BLUE[1], LINK_BLUE[2], LINK_BLUE[3], LINK_BLUE[4], LINK_BLUE[2]], 4),
+    'one link': ([LINK_BLUE[2]], 1),
+    'one link, no lookup link': ([LINK_BLUE[2]], 0),
+    'no lookup links': (LINK_BLUE, 0),
+    'every link a lookup link': (LINK_BLUE, 6),
+    'three links, two of them lookup links': (LINK_BLUE[3:], 2),
+}
+
+
+@pytest.mark.parametrize('table', list(LINK_TABLES))
+def test_staged_planes_follow_the_link_table(engines, table):
+    link_blue, n_lookup = LINK_TABLES[table]
+    e_t = engines[1]
+    H, W, f = 24, 40, 2
+    _camera(e_t, H, W)
+    md, mi = _made_up(np.random.default_rng(17), H, W, f)
+    want = _reference(md, mi, f, n_lookup, link_blue)
+    got = _device(e_t, md, mi, f, n_lookup, True, [(0, 2), (2, 3)], link_blue)
+    _check(got, want, True)
+    # what the table changes, asserted on the reference
+    bits = want[0] >> np.uint64(40)
+    assert bits.any() and not (bits >> np.uint64(len(link_blue))).any() and not want[3][:, len(link_blue):].any()
+    if 'share' in table:
+        a, b = [l for l in range(6) if link_blue.count(link_blue[l]) == 2]
+        both = np.uint64((1 << a) | (1 << b))
+        assert ((bits & both) == both).any() and not ((bits & both) == np.uint64(1 << a)).any(), "both bits or neither"
+        assert np.array_equal(want[3][:, a], want[3][:, b]) and want[3][:, a].any(), "both links are counted"
+    if n_lookup == 0:
+        t32 = want[1]
+        assert np.isnan(t32).any() and not t32[~np.isnan(t32)].any(), "zeros where the depth is finite, NaN where it is not"
+    else:
+        assert want[1][~np.isnan(want[1])].any()
+    if n_lookup == len(link_blue):
+        hit = bits != 0
+        assert np.array_equal(want[1].view(np.uint32)[hit], want[2].view(np.uint32)[hit]), "every link pixel keeps its depth"
+    default = _reference(md, mi, f, 4)
+    assert not all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(want, default)), "the table changes nothing"
 
 
 def test_staging_refusals_are_those_of_the_segmented_call(engines):
