@@ -173,7 +173,13 @@ int rope_candidates_upload(rope_ctx *ctx, const double *cand, int C);
  * point).  Results are the same bits.  Dropped by: an upload of other rows, rope_set_camera (same values included),
  * rope_set_robot[_mesh], rope_set_strategy, another n_render or crop, and every other entry that uses the per-candidate
  * buffers (small batches, rope_eval_targets, rope_eval_views, the render entries, rope_coverage, rope_lookup_build,
- * rope_debug_mvp).  ROPE_STRATEGY_NO_GEOMETRY_CACHE turns it off; rope_geometry_cache_stats counts. */
+ * rope_debug_mvp).  ROPE_STRATEGY_NO_GEOMETRY_CACHE turns it off; rope_geometry_cache_stats counts.
+ * Kept fragments: the first pass that runs on kept geometry also stores, per row, the 4-sample groups in which the row's own links
+ * (3 .. n_render - 1) beat its shared layer, with their finished keys and the layer's — a function of the same geometry, of neither
+ * loss nor target — and every later pass of that grid scores by streaming them against the target instead of drawing the own links
+ * again.  The same bits again.  The store goes wherever the kept geometry goes, is built only if it fits rope_set_fragment_budget,
+ * and only for passes that go through the queues; ROPE_STRATEGY_NO_KEPT_FRAGMENTS turns it off; rope_fragment_store_stats counts.
+ * The pass that builds waits for the stream (it sizes the store on the host); no other pass does. */
 int rope_eval_resident(rope_ctx *ctx, int n_render, int loss, const int32_t *crop);
 
 int rope_sync(rope_ctx *ctx);
@@ -428,7 +434,9 @@ int rope_debug_mvp(rope_ctx *ctx, float *mvp_out, int C, int n_render);
 /* Time `reps` back-to-back rope_eval_resident passes with HIP events on the context's
  * stream; ms[0] = FK + bounds kernels (a pass on kept geometry: the clearing launch), ms[1] = shared-layer raster launch (on kept
  * geometry: the layer-sums kernel; 0 when layers are not in use),
- * ms[2] = raster+score launch, ms[3] = finalize+argmin, ms[4] = whole pass (averages per pass, milliseconds). */
+ * ms[2] = raster+score launch — on kept fragments: the streaming scorer, and in the pass that builds the store the build as well
+ * (it is recorded with the scorer, not in a slot of its own) —, ms[3] = finalize+argmin, ms[4] = whole pass (averages per pass,
+ * milliseconds). */
 int rope_profile_eval(rope_ctx *ctx, int n_render, int loss, const int32_t *crop, int reps, float *ms);
 
 /* Execution strategy: how a batch is laid out over launches.  Every value gives bit-identical results (the depth test is
@@ -440,15 +448,26 @@ int rope_profile_eval(rope_ctx *ctx, int n_render, int loss, const int32_t *crop
  *  16  always the raster kernels that can clip triangles at the near plane (by default only when the camera is within the
  *      robot's reach of it: they are several per cent slower, and without a triangle at the plane they draw the same image)
  *  32  small batches: forward kinematics and screen boxes as a launch of their own instead of inside the split raster's workgroups
- *  64  large batches: keep no geometry from pass to pass (rope_eval_resident) — every pass builds all of it, as the first one does */
+ *  64  large batches: keep no geometry from pass to pass (rope_eval_resident) — every pass builds all of it, as the first one does
+ *      (and keeps no fragments either)
+ * 128  large batches: keep no fragments — a pass on kept geometry draws every row's own links again */
 enum { ROPE_STRATEGY_NO_LAYERS = 1, ROPE_STRATEGY_NO_SPLIT = 2, ROPE_STRATEGY_NO_PARENTS = 4, ROPE_STRATEGY_NO_QUEUE = 8, ROPE_STRATEGY_CLIP_KERNELS = 16,
-       ROPE_STRATEGY_SEPARATE_GEOMETRY = 32, ROPE_STRATEGY_NO_GEOMETRY_CACHE = 64 };
+       ROPE_STRATEGY_SEPARATE_GEOMETRY = 32, ROPE_STRATEGY_NO_GEOMETRY_CACHE = 64, ROPE_STRATEGY_NO_KEPT_FRAGMENTS = 128 };
 int rope_set_strategy(rope_ctx *ctx, int flags);
 
 /* Passes of rope_eval_resident that could keep geometry (more than 256 rows, shared layers, the single target) since the context
  * was created: how many ran on what the pass before them left (hits) and how many built it (misses; with
  * ROPE_STRATEGY_NO_GEOMETRY_CACHE all of them).  Either pointer may be NULL. */
 int rope_geometry_cache_stats(rope_ctx *ctx, uint64_t *hits, uint64_t *misses);
+
+/* The kept fragments (rope_eval_resident): stores built and passes scored from one since the context was created; bytes and 4-sample
+ * groups of the store held now (0: none — not built yet, dropped, or refused by the budget).  Any pointer may be NULL. */
+int rope_fragment_store_stats(rope_ctx *ctx, uint64_t *builds, uint64_t *passes_served, uint64_t *bytes, uint64_t *groups);
+/* (row, tile) pairs of the store held now in which any group is kept (0: no store). */
+int rope_fragment_store_pairs(rope_ctx *ctx, uint64_t *pairs);
+/* Most bytes a fragment store may take; a grid whose count comes to more keeps none and is scored as without the store.  Default: the
+ * lookup table's budget, a tenth of 8 GiB.  Drops the store held (the next pass on kept geometry counts again). */
+int rope_set_fragment_budget(rope_ctx *ctx, uint64_t bytes);
 
 /* ---- Segmentation stage (robotpose/prediction/predict.py:94-98,416: the Matterport Mask R-CNN in front of the engine).
  * The convolutions are library calls from PyTorch-ROCm (rope_s3d_amd/maskrcnn.py); the two box-shaped steps between them

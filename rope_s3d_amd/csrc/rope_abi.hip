@@ -65,7 +65,7 @@ extern "C" int rope_create(rope_ctx **out, int device)
     if (!c) return ROPE_E_NOMEM;
     c->device = device;
     if (const char *e = std::getenv("ROPE_SPLIT_TARGET")) c->split_target = std::max(1, std::atoi(e));     // tuning aid
-    if (const char *e = std::getenv("ROPE_STRATEGY")) c->strategy = std::atoi(e) & 127;                     // tuning aid: rope_set_strategy's bits
+    if (const char *e = std::getenv("ROPE_STRATEGY")) c->strategy = std::atoi(e) & 255;                     // tuning aid: rope_set_strategy's bits
     if (const char *e = std::getenv("ROPE_SPLIT_CAP")) c->split_cap = std::max(1, std::min(64, std::atoi(e)));
     if (const char *e = std::getenv("ROPE_SPLIT_MIN")) c->split_min = std::max(1, std::min(64, std::atoi(e)));
     if (const char *e = std::getenv("ROPE_GEO_ROWS")) c->geo_rows = std::max(0, std::min(256, std::atoi(e)));     // d_touched holds 256 rows
@@ -227,7 +227,7 @@ extern "C" int rope_set_robot(rope_ctx *c, const uint32_t *ml_header, int n_mesh
         reach = std::max(reach, chain + r);
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    c->geo.drop();                                // boxes, masks, weights and layer tiles are this robot's no longer
+    c->drop_kept();                               // boxes, masks, weights and layer tiles are this robot's no longer
     c->shadow.drop();
     c->robot_epoch++;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -269,7 +269,7 @@ extern "C" int rope_set_camera(rope_ctx *c, const double *PV, int W, int H, doub
     if (W < 1 || H < 1 || W > 8192 || H > 8192) ARG_FAIL(c, "rope_set_camera: image size out of range");
     if (!(znear > 0.0) || !(zfar > znear)) ARG_FAIL(c, "rope_set_camera: need 0 < znear < zfar");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->geo.drop();                                // whatever the values: the matrices are not compared
+    c->drop_kept();                               // whatever the values: the matrices are not compared
     c->camera_epoch++;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const bool resized = !c->have_camera || W != c->fp.W || H != c->fp.H;
@@ -364,7 +364,7 @@ static bool use_clip(const rope_ctx *c, bool views = false)
 int ensure_capacity(rope_ctx *c, int C)
 {
     if (C <= c->cap) return ROPE_OK;
-    c->geo.drop();                                // every per-candidate buffer is allocated anew
+    c->drop_kept();                               // every per-candidate buffer is allocated anew
     c->shadow.drop();
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     int cap = C < 64 ? 64 : C;
@@ -411,7 +411,7 @@ int upload_candidates(rope_ctx *c, const double *cand, int C, bool group, const 
         return ROPE_OK;
     }
     c->shadow.drop();
-    c->geo.drop();
+    c->drop_kept();
     c->cand_epoch++;
     for (size_t i = 0; i < 6 * (size_t)C; i++)
         if (!std::isfinite(cand[i]) || std::fabs(cand[i]) > 1.0e4) ARG_FAIL(c, "rope_candidates_upload: joint angle not finite or |q| > 1e4 rad");
@@ -558,7 +558,7 @@ static bool use_parents(const rope_ctx *c, int n_shared)
 // merged with its parent's tile.
 static int enqueue_layers(rope_ctx *c, RasterArgs la, int loss, int n_shared, const FrameParams &fp)
 {
-    c->geo.drop();                                // every writer of the layer tiles comes through here
+    c->drop_kept();                               // every writer of the layer tiles comes through here
     la.cand_of_row = c->d_layer_rep; la.layers = c->d_layers;
     if (use_parents(c, n_shared)) {
         const size_t need = (size_t)c->n_parents * c->n_tiles * (TILE_W * TILE_H);
@@ -622,7 +622,7 @@ static GeometryKey geometry_key(const rope_ctx *c, int n_render, int n_shared, c
 // forward kinematics + link matrices + screen boxes + tile masks (+ cleared sums) of the resident candidates
 static int enqueue_geometry(rope_ctx *c, int n_render, int n_shared, const FrameParams &fp, bool views)
 {
-    c->geo.drop();                                // every writer of d_mvp, d_bounds, the masks and the weights comes through here
+    c->drop_kept();                               // every writer of d_mvp, d_bounds, the masks and the weights comes through here
     const double *PV = views ? c->dv_PV : c->d_PV, *cand = views ? c->dv_cand : c->cand_dev;
     const int32_t *view_of = views ? c->dv_view_of : nullptr;
     if (c->C <= 256) {                              // one fused launch, one workgroup per candidate
@@ -636,6 +636,77 @@ static int enqueue_geometry(rope_ctx *c, int n_render, int n_shared, const Frame
     const int lo_first = use_parents(c, n_shared) ? 2 : 0;
     HIP_TRY(c, launch_bounds(c->stream, c->C, fp, c->rp, n_render, n_shared, c->d_mvp, c->d_bounds, c->d_mask_lo, c->d_mask_hi, c->mask_words,
                              n_shared > 0 ? c->d_layer_of : nullptr, n_shared > 0 ? c->d_layer_rep : nullptr, queue_weights(c), c->d_tile_tris_lo, lo_first));
+    return ROPE_OK;
+}
+
+// One chunk of rows' own links into c->d_fscratch: the MODE_LAYER queue launch with a RasterArgs of its own — the row -> candidate map
+// is the identity from row0 on, "mask_lo" is the candidates' mask_hi (the tiles their own links reach), the weights are the own
+// links', and there is neither a parent level nor sums.  It runs on the layer queue's counters and segment, which a hit pass leaves idle.
+static int draw_own_links(rope_ctx *c, const RasterArgs &a, int loss, const FrameParams &fp, int row0, int rows)
+{
+    RasterArgs la = base_args(c, a.n_render);
+    la.l_begin = a.l_begin; la.l_end = a.n_render;
+    la.cand_of_row = c->d_frow + row0;
+    la.mask_lo = c->d_mask_hi;
+    la.layers = c->d_fscratch;
+    int *counters = c->d_qctr + QUEUE_COUNTERS;
+    HIP_TRY(c, hipMemsetAsync(counters, 0, QUEUE_COUNTERS * sizeof(int), c->stream));
+    const bool weighted = queue_weights(c) != nullptr;
+    HIP_TRY(c, launch_layer_queue(loss, rows, 2 * c->n_cu, c->stream, fp, c->rp, la, weighted ? c->d_qitems + QUEUE_CLASSES * c->q_segment : c->d_qitems.get(),
+                                  weighted ? c->q_segment : 0, counters, weighted ? c->d_tile_tris.get() : nullptr, use_clip(c)));
+    return ROPE_OK;
+}
+
+// The kept fragments of the grid whose geometry the context holds, built inside the first pass that hits it: the rows' own links
+// drawn chunk by chunk (draw_own_links) and counted, the counts scanned on the host — here the stream is waited for; the one pass
+// that builds pays that — and, when the store fits the budget, drawn once more and written to their places.  Two draws instead of
+// one so that nothing is allocated before its size is known.  The scratch and the counts are released at the end, kept or declined.  `a`: the pass's scoring arguments (masks, layers, l_begin).
+// Leaves c->frags serving `key`, or declined for it; the queue counters and sums the pass's own scoring launch needs are untouched.
+static int build_fragments(rope_ctx *c, const GeometryKey &key, const RasterArgs &a, int loss, const FrameParams &fp)
+{
+    RopeRange r("rope:fragments-build");
+    const int n_tiles = c->n_tiles, C = c->C;
+    const size_t tile_px = (size_t)TILE_W * TILE_H, n_slots = (size_t)C * n_tiles;
+    const FragmentChunks plan(C, n_tiles, std::min(n_slots, c->d_layers.cap() / tile_px));      // a scratch no larger than the layer buffer
+    if (!plan.rows) { c->frags.decline(key); return ROPE_OK; }
+    if (int rc = sync_grow(c, c->d_fscratch, (size_t)plan.rows * n_tiles * tile_px, c->d_fcount, n_slots, c->d_foffs, n_slots + 1, c->d_frow, (size_t)C)) return rc;
+    if (c->frow_filled < C) {                       // (a re-grown d_frow is larger than what was filled)
+        std::vector<int32_t> id((size_t)C);
+        for (int i = 0; i < C; i++) id[i] = i;
+        HIP_TRY(c, hipMemcpyAsync(c->d_frow, id.data(), id.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->frow_filled = C;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->d_fcount, 0, n_slots * sizeof(uint32_t), c->stream));
+    for (int k = 0; k < plan.chunks; k++) {
+        if (int rc = draw_own_links(c, a, loss, fp, plan.begin(k), plan.count(k, C))) return rc;
+        HIP_TRY(c, launch_fragment_count(c->stream, a, c->d_fscratch, plan.begin(k), plan.count(k, C), n_tiles, c->d_fcount));
+    }
+    std::vector<uint32_t> counts(n_slots);
+    std::vector<uint64_t> offs(n_slots + 1);
+    HIP_TRY(c, hipMemcpyAsync(counts.data(), c->d_fcount, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint64_t n_pairs = 0;
+    const uint64_t n_groups = FragmentStore::scan(counts.data(), n_slots, offs.data(), &n_pairs);
+    if (!c->frags.fits(n_groups, n_slots)) {
+        // over the budget: nothing is kept, and the building pass's own buffers — the scratch is as large as the layer buffer — go too
+        c->d_fscratch.release(); c->d_fcount.release(); c->d_foffs.release();       // the stream is idle
+        c->frags.decline(key);
+        return ROPE_OK;
+    }
+    const size_t room = (size_t)std::max<uint64_t>(n_groups, 1);
+    HIP_TRY(c, grow_each(c->d_fwhere, room, c->d_ffin, room, c->d_fbase, room));       // the stream is idle
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "offsets go up as they are");
+    HIP_TRY(c, hipMemcpyAsync(c->d_foffs, offs.data(), (n_slots + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));                                         // offs is local
+    for (int k = 0; k < plan.chunks; k++) {
+        if (int rc = draw_own_links(c, a, loss, fp, plan.begin(k), plan.count(k, C))) return rc;
+        HIP_TRY(c, launch_fragment_fill(c->stream, a, c->d_fscratch, plan.begin(k), plan.count(k, C), n_tiles, c->d_foffs, c->d_fwhere, c->d_ffin, c->d_fbase));
+    }
+    // the scratch and the counts are the build's alone: let them go, which means one more wait in the pass that waits anyway
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->d_fscratch.release(); c->d_fcount.release();
+    c->frags.built(key, n_groups, n_slots, n_pairs);
     return ROPE_OK;
 }
 
@@ -654,6 +725,11 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
     const bool hit = cacheable && c->geo.holds(key);
     c->geo.drop();                                  // a pass that fails half way leaves nothing behind; set again at the end
     if (in_scope) (hit ? c->geo.hits : c->geo.misses)++;
+    // Kept fragments (rope_ctx::frags): a hit may be scored from them, and builds them when they are not there yet; any other pass
+    // is about to write the geometry they were taken from.  Through the queues only (the build is a queue launch).
+    if (!hit) c->frags.drop();
+    const bool frag_scope = hit && loss != ROPE_LOSS_CAMFULL && !(c->strategy & (STRATEGY_NO_KEPT_FRAGMENTS | STRATEGY_NO_QUEUE));
+    const bool served_now = frag_scope && c->frags.serves(key);       // a later hit: the scorer writes every row's sums whole, nothing to clear
     if (ev) HIP_TRY(c, hipEventRecord(ev[0], c->stream));
     // Few candidates (descent pairs, flips): one workgroup per (tile, candidate) would leave most of the chip idle,
     // so the meshlets of each tile are split over several workgroups that merge into a tile in global memory.
@@ -674,7 +750,8 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
     // And on frames of a few tiles only (the Predictor's 160x90 is two): on a 25-tile frame two thirds of the workgroups belong to tiles
     // the robot does not reach — the masks of the separate launch let them leave at once, here each would do the matrices first.
     const bool geo = split > 1 && !views && c->C <= c->geo_rows && c->n_tiles <= 4 && !(c->strategy & STRATEGY_SEPARATE_GEOMETRY);
-    if (hit) HIP_TRY(c, launch_clear_pass(c->stream, c->d_sums, c->C, c->d_qctr));      // what is left of fk_mvp_kernel: cleared sums and queue counters
+    if (served_now) { }
+    else if (hit) HIP_TRY(c, launch_clear_pass(c->stream, c->d_sums, c->C, c->d_qctr));      // what is left of fk_mvp_kernel: cleared sums and queue counters
     else if (!geo) { RopeRange r("rope:fk+bounds"); int rc = enqueue_geometry(c, n_render, n_shared, fp, views); if (rc) return rc; }
     c->mvp_valid = !geo;
     if (ev) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
@@ -724,7 +801,19 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
     if (ev) HIP_TRY(c, hipEventRecord(ev[2], c->stream));
     {
         RopeRange r("rope:raster+score");
-        if (split > 1) {
+        bool served = false;
+        if (frag_scope) {
+            // first hit: build the store, inside this pass (and this interval of rope_profile_eval); when the count shows it would
+            // not fit the budget it is declined for this key and the pass, like every later one, runs as before
+            if (!served_now && !c->frags.refused(key)) { int rc = build_fragments(c, key, a, loss, fp); if (rc) return rc; }
+            if (c->frags.serves(key)) {
+                HIP_TRY(c, launch_fragment_score(loss, c->C, c->stream, fp, a, c->d_foffs, c->d_fwhere, c->d_ffin, c->d_fbase));
+                c->frags.passes_served++;
+                served = true;
+            }
+        }
+        if (served) { }
+        else if (split > 1) {
             int slices = 1;
             while (slices < 8 && c->C * c->n_tiles * slices * 2 <= c->score_target) slices *= 2;
             HIP_TRY(c, launch_score_gtile(loss, c->C, slices, c->stream, fp, a));
@@ -1158,8 +1247,8 @@ extern "C" int rope_set_strategy(rope_ctx *c, int flags)
 {
     if (!c) return ROPE_E_ARG;
     if (flags & ~(STRATEGY_NO_LAYERS | STRATEGY_NO_SPLIT | STRATEGY_NO_PARENTS | STRATEGY_NO_QUEUE | STRATEGY_CLIP_KERNELS | STRATEGY_SEPARATE_GEOMETRY |
-                  STRATEGY_NO_GEOMETRY_CACHE)) ARG_FAIL(c, "rope_set_strategy: unknown flag");
-    c->geo.drop();
+                  STRATEGY_NO_GEOMETRY_CACHE | STRATEGY_NO_KEPT_FRAGMENTS)) ARG_FAIL(c, "rope_set_strategy: unknown flag");
+    c->drop_kept();
     c->strategy = flags;
     return ROPE_OK;
 }
@@ -1169,6 +1258,31 @@ extern "C" int rope_geometry_cache_stats(rope_ctx *c, uint64_t *hits, uint64_t *
     if (!c) return ROPE_E_ARG;
     if (hits) *hits = c->geo.hits;
     if (misses) *misses = c->geo.misses;
+    return ROPE_OK;
+}
+
+extern "C" int rope_fragment_store_stats(rope_ctx *c, uint64_t *builds, uint64_t *passes_served, uint64_t *bytes, uint64_t *groups)
+{
+    if (!c) return ROPE_E_ARG;
+    if (builds) *builds = c->frags.builds;
+    if (passes_served) *passes_served = c->frags.passes_served;
+    if (bytes) *bytes = c->frags.bytes;
+    if (groups) *groups = c->frags.groups;
+    return ROPE_OK;
+}
+
+extern "C" int rope_fragment_store_pairs(rope_ctx *c, uint64_t *pairs)
+{
+    if (!c || !pairs) return ROPE_E_ARG;
+    *pairs = c->frags.pairs;
+    return ROPE_OK;
+}
+
+extern "C" int rope_set_fragment_budget(rope_ctx *c, uint64_t bytes)
+{
+    if (!c) return ROPE_E_ARG;
+    c->frags.drop();                                // what is held was admitted under the old budget, and a refusal was one of it too
+    c->frags.budget = bytes;
     return ROPE_OK;
 }
 

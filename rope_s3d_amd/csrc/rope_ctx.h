@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rope_buffers.h"
+#include "rope_fragstore.h"
 #include "rope_geomcache.h"
 #include "rope_kernels.h"
 
@@ -158,6 +159,19 @@ struct rope_ctx {
     GeometryCache geo;
     CandidateShadow shadow;
     uint64_t cand_epoch = 0, camera_epoch = 0, robot_epoch = 0;
+    // The third state: once a pass has run on kept geometry, the context also keeps what the scoring launch would draw again bit for
+    // bit — per row the 4-sample groups where the row's own links beat its layer, with their finished keys and the layer's
+    // (rope_fragstore.h) — and later passes of the same key stream them against the target (fragment_score_kernel) instead of
+    // launching score_queue_kernel and raster_queue_kernel<., SCORE>.  Built by the first hit (build_fragments, rope_abi.hip), chunk of
+    // rows by chunk of rows through d_fscratch; belongs to the same GeometryKey; depends on neither loss nor target.  Dropped
+    // wherever `geo` is dropped for good (drop_kept) and by every pass that is not a hit.
+    FragmentStore frags;
+    DevBuf<uint32_t> d_fscratch, d_fcount, d_fwhere;    // chunk's key tiles; groups per (row, tile); the store: where,
+    DevBuf<uint4> d_ffin, d_fbase;                      // finished keys, base keys
+    DevBuf<unsigned long long> d_foffs;                 // C x n_tiles + 1
+    DevBuf<int32_t> d_frow;                             // 0, 1, 2, ...: the building launch's row -> candidate map, from any row on
+    int frow_filled = 0;
+    void drop_kept() { geo.drop(); frags.drop(); }
 
     // small batches: per-candidate tiles in global memory that split workgroups merge into
     DevBuf<int> d_touched;                 // MODE_SPLIT_GEO: per (candidate, tile) the number of the pass that last drew into it
@@ -266,7 +280,7 @@ template <typename B, typename... R> static int grow_each(B &b, size_t n, R &...
 template <typename... A> static int sync_grow(rope_ctx *c, A &&...a)
 {
     if (!any_short(a...)) return ROPE_OK;
-    c->geo.drop();                                // whichever buffer grows: a re-grown one holds nothing, and the key need not name them all
+    c->drop_kept();                               // whichever buffer grows: a re-grown one holds nothing, and the key need not name them all
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, grow_each(a...));
     return ROPE_OK;

@@ -92,7 +92,7 @@ struct FrameParams {
 
 // Execution strategies that change the launch structure but never a result (rope_set_strategy)
 enum { STRATEGY_NO_LAYERS = 1, STRATEGY_NO_SPLIT = 2, STRATEGY_NO_PARENTS = 4, STRATEGY_NO_QUEUE = 8, STRATEGY_CLIP_KERNELS = 16, STRATEGY_SEPARATE_GEOMETRY = 32,
-       STRATEGY_NO_GEOMETRY_CACHE = 64 };
+       STRATEGY_NO_GEOMETRY_CACHE = 64, STRATEGY_NO_KEPT_FRAGMENTS = 128 };
 
 struct RobotParams {
     const uint32_t *ml_header;            // n_meshlets x 8
@@ -185,6 +185,18 @@ hipError_t launch_layer_queue(int loss, int rows, int workgroups, hipStream_t st
 // pairs whose mask_lo bit is set are stored, the others are left alone (nobody reads them).
 hipError_t launch_clear_pass(hipStream_t st, uint64_t *sums, int C, int *queue_counters);
 hipError_t launch_layer_sums(int loss, int n_layers, hipStream_t st, const FrameParams &fp, const RasterArgs &a);
+// The kept fragments of a fixed grid (rope_ctx::frags, rope_fragstore.h).  `own`: rows x n_tiles key tiles that a MODE_LAYER launch
+// over the own links of rows row0 .. row0 + rows - 1 left (a.cand_of_row = the identity from row0 on, a.mask_lo = the context's
+// mask_hi); `a` here carries the pass's own a.mask_lo / a.mask_hi / a.layer_of / a.layer_rep / a.layers.  launch_fragment_count: per
+// (row, tile) with the mask_hi bit the 16-byte groups in which an own key beats the layer's -> counts[row x n_tiles + tile] (C x n_tiles,
+// zeroed by the caller).  launch_fragment_fill: those groups to offs[row x n_tiles + tile] on (offs: C x n_tiles + 1, the counts' running
+// sum) as where = tile << 12 | group, the finished keys min(own, base) and the base keys.  launch_fragment_score: every row's sums
+// from its groups, the target in a.tq / a.t32 and a.layer_sums, stored whole into a.sums (no clearing before, no atomics).
+hipError_t launch_fragment_count(hipStream_t st, const RasterArgs &a, const uint32_t *own, int row0, int rows, int n_tiles, uint32_t *counts);
+hipError_t launch_fragment_fill(hipStream_t st, const RasterArgs &a, const uint32_t *own, int row0, int rows, int n_tiles,
+                                const unsigned long long *offs, uint32_t *where, uint4 *finished, uint4 *base_keys);
+hipError_t launch_fragment_score(int loss, int rows, hipStream_t st, const FrameParams &fp, const RasterArgs &a, const unsigned long long *offs,
+                                 const uint32_t *where, const uint4 *finished, const uint4 *base_keys);
 // scores what a MODE_SPLIT launch merged into a.gtile; `slices` row slices per tile (a divisor of TILE_H)
 hipError_t launch_score_gtile(int loss, int rows, int slices, hipStream_t st, const FrameParams &fp, const RasterArgs &a);
 // "nothing rendered" sums of n_frames frames (planes back to back): empty_sums n_frames x n_tiles x SUM_WORDS of scratch,

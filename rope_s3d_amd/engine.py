@@ -27,7 +27,7 @@ TQ_MAX = (1 << 39) - 1
 ABI_SYMBOLS = (
     'rope_create', 'rope_destroy', 'rope_last_error', 'rope_set_robot', 'rope_set_camera', 'rope_set_target',
     'rope_candidates_upload', 'rope_eval_resident', 'rope_sync', 'rope_results_download', 'rope_eval',
-    'rope_lookup_build', 'rope_lookup_score', 'rope_render', 'rope_render_batch', 'rope_render_masks', 'rope_trace_contours', 'rope_coverage', 'rope_debug_mvp', 'rope_profile_eval', 'rope_set_strategy', 'rope_geometry_cache_stats',
+    'rope_lookup_build', 'rope_lookup_score', 'rope_render', 'rope_render_batch', 'rope_render_masks', 'rope_trace_contours', 'rope_coverage', 'rope_debug_mvp', 'rope_profile_eval', 'rope_set_strategy', 'rope_geometry_cache_stats', 'rope_fragment_store_stats', 'rope_fragment_store_pairs', 'rope_set_fragment_budget',
     'rope_set_frames', 'rope_eval_views', 'rope_predict', 'rope_set_robot_mesh', 'rope_partition_mesh', 'rope_pack_target', 'rope_downsample_even',
     'rope_seg_nms', 'rope_seg_roi_align', 'rope_seg_bias_act', 'rope_seg_mask_overlaps',
     'rope_seg_rpn_targets', 'rope_seg_roi_targets', 'rope_seg_roi_align_float', 'rope_seg_roi_align_backward',
@@ -134,6 +134,9 @@ def load_library(path: str = None):
     lib.rope_profile_eval.argtypes = [vp, i32, i32, vp, i32, vp]
     lib.rope_set_strategy.argtypes = [vp, i32]
     lib.rope_geometry_cache_stats.argtypes = [vp, vp, vp]
+    lib.rope_fragment_store_stats.argtypes = [vp, vp, vp, vp, vp]
+    lib.rope_set_fragment_budget.argtypes = [vp, C.c_uint64]
+    lib.rope_fragment_store_pairs.argtypes = [vp, vp]
     if hasattr(lib, 'rope_debug_skip'):                 # librope_hip_profile.so only (ROPE_HIP_LIB=...)
         lib.rope_debug_skip.argtypes = [vp, i32]
         lib.rope_debug_clock.argtypes = [vp, vp]
@@ -975,7 +978,7 @@ class Engine:
         self._check(self._lib.rope_debug_mvp(self._ctx, _p(out), int(C_), int(n_render)), 'rope_debug_mvp')
         return out
 
-    NO_LAYERS, NO_SPLIT, NO_PARENTS, NO_QUEUE, CLIP_KERNELS, SEPARATE_GEOMETRY, NO_GEOMETRY_CACHE = 1, 2, 4, 8, 16, 32, 64
+    NO_LAYERS, NO_SPLIT, NO_PARENTS, NO_QUEUE, CLIP_KERNELS, SEPARATE_GEOMETRY, NO_GEOMETRY_CACHE, NO_KEPT_FRAGMENTS = 1, 2, 4, 8, 16, 32, 64, 128
 
     def set_strategy(self, flags: int):
         """rope_set_strategy: launch structure only (shared layers / small-batch split / second sharing level off);
@@ -988,6 +991,28 @@ class Engine:
         hits, misses = C.c_uint64(), C.c_uint64()
         self._check(self._lib.rope_geometry_cache_stats(self._ctx, C.byref(hits), C.byref(misses)), 'rope_geometry_cache_stats')
         return int(hits.value), int(misses.value)
+
+    def fragment_store_stats(self):
+        """rope_fragment_store_stats -> (builds, passes_served, bytes, groups): fragment stores built and passes scored from one so
+        far; size of the store held now (0, 0: none)."""
+        v = [C.c_uint64() for _ in range(4)]
+        self._check(self._lib.rope_fragment_store_stats(self._ctx, *(C.byref(x) for x in v)), 'rope_fragment_store_stats')
+        return tuple(int(x.value) for x in v)
+
+    def fragment_store_pairs(self) -> int:
+        """rope_fragment_store_pairs: (row, tile) pairs of the store held now that keep any group."""
+        v = C.c_uint64()
+        self._check(self._lib.rope_fragment_store_pairs(self._ctx, C.byref(v)), 'rope_fragment_store_pairs')
+        return int(v.value)
+
+    def set_fragment_budget(self, mib: float = None):
+        """rope_set_fragment_budget: most memory a grid's kept fragments may take, in MiB; None: the lookup table's default
+        (simulation.lookup.DEFAULT_LOOKUP_VRAM_MIB x GPU_MEMORY_ALLOWED_FOR_LOOKUP)."""
+        if mib is None:
+            from .constants import GPU_MEMORY_ALLOWED_FOR_LOOKUP
+            from .simulation.lookup import DEFAULT_LOOKUP_VRAM_MIB
+            mib = DEFAULT_LOOKUP_VRAM_MIB * GPU_MEMORY_ALLOWED_FOR_LOOKUP
+        self._check(self._lib.rope_set_fragment_budget(self._ctx, int(mib * (1 << 20))), 'rope_set_fragment_budget')
 
     def debug_skip(self, mask: int):
         """Kernel-phase ablation; only the profiling build of the library has it (tools/build_variants.py profile)."""
