@@ -30,6 +30,23 @@ def calibrate(args):
     f = int(args.ds_factor)
     h, w = full.shape[1] // f, full.shape[2] // f
     depth = np.stack([resize_linear(d, w, h) for d in full]).astype(np.float32) if f > 1 else full
+    mask, extra = None, {}
+    if args.silhouette > 0:
+        # the robot masks: the frames' colour images reduced as the depth is, read by the colour code of the set (ColorSegmenter, what
+        # Predictor(color_dict=...) sets reads its link masks with); masks made by a segmentation network are not taken here
+        if args.joints == 'fixed':
+            raise SystemExit("-silhouette goes with -joints frame or offset: -joints fixed is the camera-only polish, which has no such term")
+        if not ds.attrs.get('color_dict'):
+            raise SystemExit("-silhouette needs a dataset with a color_dict (colour-coded frames): its robot masks are read off the link colours")
+        from rope_s3d_amd.segmentation import ColorSegmenter
+        from rope_s3d_amd.urdf import URDFReader
+        seg = ColorSegmenter(['BG'] + list(URDFReader().mesh_names[:6]), ds.attrs['color_dict'])
+        colour = np.asarray(ds.og_img[:n], np.uint8)
+        mask = np.zeros((n, h, w), bool)
+        for i, c in enumerate(colour):
+            m = seg(resize_linear(c, w, h) if f > 1 else c)['masks']
+            mask[i] = m.any(axis=2)
+        extra = dict(silhouette=args.silhouette, radius=args.radius)
     renderer = Renderer('seg', pose0, str(ds.attrs['color_intrinsics']), intrinsic_ds_factor=f if f > 1 else None)
     try:
         if args.joints == 'fixed':
@@ -37,7 +54,7 @@ def calibrate(args):
             sigma_pose, out_angles = res.sigma, angles
         else:
             res = BundleRefiner(renderer, renderer.intrinsics, do_angles=args.do_angles, joints=args.joints, clip=args.clip,
-                                iterations=args.iterations).refine(pose0, angles, depth)
+                                iterations=args.iterations, **extra).refine(pose0, angles, depth, mask)
             sigma_pose, out_angles = res.sigma_pose, res.angles
     finally:
         renderer.engine.close()
@@ -45,9 +62,15 @@ def calibrate(args):
     rep = dict(dataset=args.dataset, frames=n, joints=args.joints, do_angles=args.do_angles, ds_factor=f, clip=args.clip, start_pose=pose0.tolist(),
                pose=res.pose.tolist(), sigma_pose=sigma_pose.tolist(), cost_before=float(res.cost_before), cost_after=float(res.cost_after),
                steps_taken=int(res.steps_taken), inliers=float(res.inliers), frame_cost=res.frame_cost.tolist(), worst_frames=worst.tolist())
+    if args.silhouette > 0:
+        rep.update(silhouette=args.silhouette, radius=args.radius, cost_silhouette_before=float(res.cost_silhouette_before),
+                   cost_silhouette_after=float(res.cost_silhouette_after), inliers_silhouette=float(res.inliers_silhouette))
     names = ('x', 'y', 'z', 'a3', 'a4', 'a5')
     print(f"{args.dataset}: {n} frames at {w} x {h}, joints {args.joints}, {res.steps_taken} steps, {res.inliers:.0f} inlier pixels")
     print(f"mean truncated cost {res.cost_before:.6e} -> {res.cost_after:.6e} m^2")
+    if args.silhouette > 0:
+        print(f"mean truncated outline cost {res.cost_silhouette_before:.6e} -> {res.cost_silhouette_after:.6e} pixels^2 "
+              f"(weight {args.silhouette:g}, radius {args.radius}, {res.inliers_silhouette:.0f} contour pixels)")
     for k in range(6):
         print(f"  {names[k]:>2} {pose0[k]:+.6f} -> {res.pose[k]:+.6f}  (change {res.pose[k] - pose0[k]:+.2e}, formal sigma {sigma_pose[k]:.2e})")
     if args.joints == 'offset':
@@ -81,5 +104,8 @@ if __name__ == "__main__":
     parser.add_argument('-ds_factor', type=int, default=4, help="Down-sampling of the frames.")
     parser.add_argument('-iterations', type=int, default=5, help="Rounds at most.")
     parser.add_argument('-clip', type=float, default=2 ** -5, help="Metres at which a residual is truncated.")
+    parser.add_argument('-silhouette', type=float, default=0.0,
+                        help="Weight of the outline term beside the depth term (0: off). Needs a colour-coded dataset (color_dict).")
+    parser.add_argument('-radius', type=int, default=8, help="Pixels at which the outline distance is truncated, 1 .. 16.")
     parser.add_argument('-json', type=str, default=None, help="File for the report.")
     calibrate(parser.parse_args())

@@ -786,6 +786,62 @@ int rope_bundle_normal_equations(const float *render_depth_dev, const uint8_t *r
                                  const double *twists_dev, int n_cols, float clip_m, double *out_dev, double *work_dev, void *stream);
 size_t rope_bundle_normal_workspace(int n_frames, int H, int W);
 
+/* ---- The silhouette term (csrc/rope_silhouette.hip; prediction/refinement.py, BundleRefiner(silhouette=...);
+ * tests/silhouette_ref.py restates the text below in numpy).  Depth along a ray barely changes when the robot slides across the
+ * image; its outline does, and needs no depth at all.  Same conventions as above: no context, plain device pointers, the HIP stream
+ * to launch on, nothing synchronised, allocated or copied in the call, no floating-point atomics.
+ *
+ * rope_mask_distance: the truncated signed SQUARED distance of every pixel to the boundary of its mask, in exact integers.
+ *   mask_dev             N planes H x W uint8, DEVICE: non-zero = robot
+ *   radius               R, 1 .. ROPE_SIL_MAX_RADIUS
+ *   sd2_dev              N planes H x W int32 out, DEVICE, 4-byte aligned; written completely
+ * For a pixel p, in(p) = mask[p] != 0:  m = the least dx dx + dy dy over the pixels q INSIDE THE IMAGE with |dx| <= R, |dy| <= R and
+ * in(q) != in(p).  Without such a q, or with m > R R:  m = R R + 1 (FAR).  sd2[p] = -m when in(p), else +m; never 0.  The image edge
+ * is not a boundary: a mask that fills the plane, or is empty, is FAR everywhere.
+ * ROPE_E_ARG, with nothing enqueued, for N < 0, H or W < 1, H W >= 2^31, a radius out of range, and with N > 0 a null mask_dev or
+ * sd2_dev or a misaligned sd2_dev.  N == 0 succeeds.  ROPE_E_HIP when the runtime refuses a launch.
+ *
+ * rope_silhouette_normal_equations: per frame, the Gauss-Newton normal equations of the distance between the render's OUTLINE and
+ * the mask's boundary, over the twelve column slots of rope_bundle_normal_equations and in its ROPE_BNEQ_WORDS layout, so that the
+ * same host solve takes either or a weighted sum of both.  The term is ONE-DIRECTIONAL: it measures the render's outline against
+ * the mask; a part of the mask that no outline of the render comes near pulls nothing.
+ *   render_depth_dev, render_ids_dev, n_frames, H, W, n_links, fx .. cy, joints_dev, n_joints (0 .. 6), twists_dev, n_cols (0 .. 6),
+ *   the twelve slots, out_dev and the stream are rope_bundle_normal_equations'; what differs:
+ *   sd2_dev              n_frames planes H x W int32 as rope_mask_distance writes them for the frames' masks, DEVICE, 4-byte aligned,
+ *                        in place of frame_depth_dev
+ *   radius               R, 1 .. ROPE_SIL_MAX_RADIUS, in place of clip_m: the truncation the field was made with
+ *   work_dev             rope_silhouette_normal_workspace(n_frames, H, W) bytes, DEVICE, 8-byte aligned
+ * Everything is float64 with ONE correctly rounded IEEE operation per written operation, in the order written; R[y][x] and fx .. cy
+ * are widened first.  id = ids[y][x]; u x v as above.
+ *   1. phi(q) = s (sqrt((double)m) - 0.5) with m = |sd2[q]| and s = -1 for sd2[q] < 0, else +1: the signed distance in pixels to the
+ *      boundary, which lies midway between an inside pixel and its outside neighbour.  A FAR pixel, |sd2[q]| > R R, uses m = R R + 1.
+ *   2. RENDERED: id < n_links.  CONTOUR: rendered, and at least one of the 4-neighbours INSIDE THE IMAGE is not rendered: a robot cut
+ *      by the frame's edge has no contour there.  NEAR: |sd2[p]| <= R R.  INLIER: contour and near.
+ *   3. e = phi(p) + 0.5: a contour pixel's centre sits half a pixel inside the render's outline, so a render that matches its mask
+ *      has e = 0 on every contour pixel.
+ *   4. gx = (phi(x + 1, y) - phi(x - 1, y)) / 2 when both neighbours are in the image; phi(x + 1, y) - phi(x, y) or
+ *      phi(x, y) - phi(x - 1, y) with the one that is; 0 when W == 1.  gy likewise along y.
+ *   5. P = (kx z, ky z, z), z = R[y][x], kx = (x - cx) / fx, ky = (y - cy) / fy: step 1 of rope_pose_normal_equations.
+ *   6. Joint slot j < min(id, n_joints): u = a x (P - o).  Camera slot 6 + k, k < n_cols: c = w_k x P, u = (c.x + v_k.x, c.y + v_k.y,
+ *      c.z + v_k.z), as in 5' above.
+ *   7. vx = (fx (u.x - kx u.z)) / z;  vy = (fy (u.y - ky u.z)) / z;  J_c = gx vx + gy vy: what e changes by per unit of the column,
+ *      the image velocity of the surface point along the field's gradient.  J_c = 0, exactly, for every other slot.
+ * Per frame:  [0] contour pixels   [1] sum over contour pixels of e e (a FAR pixel adds its clamped phi: the sum is truncated by
+ *   construction)   [2] inliers   [3] sum over inliers of e e   [4 + c] sum of J_c e   [16 .. 93] sum of J_a J_b, laid out as the
+ *   bundle's   [94], [95] 0.
+ * Determinism is rope_pose_normal_equations': a workgroup covers pixels that depend on H W alone, one partial a workgroup in
+ * work_dev, a second kernel adds a frame's partials in index order; the same bytes from run to run and however the frames are cut
+ * into calls.  The order of the summation is not part of the contract.
+ * ROPE_E_ARG, with nothing enqueued and out_dev untouched, for every case of rope_bundle_normal_equations with sd2_dev in place of
+ * frame_depth_dev, and for a radius out of range in place of its clip_m rule.  rope_silhouette_normal_workspace (host only): the
+ * bytes of work_dev; 0 for a shape the call refuses. */
+#define ROPE_SIL_MAX_RADIUS 16
+int rope_mask_distance(const uint8_t *mask_dev, int N, int H, int W, int radius, int32_t *sd2_dev, void *stream);
+int rope_silhouette_normal_equations(const float *render_depth_dev, const uint8_t *render_ids_dev, const int32_t *sd2_dev, int n_frames, int H,
+                                     int W, int n_links, float fx, float fy, float cx, float cy, const double *joints_dev, int n_joints,
+                                     const double *twists_dev, int n_cols, int radius, double *out_dev, double *work_dev, void *stream);
+size_t rope_silhouette_normal_workspace(int n_frames, int H, int W);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

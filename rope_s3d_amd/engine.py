@@ -18,6 +18,7 @@ AGREE_WORDS = 28                 # ROPE_AGREE_WORDS (include/rope_s3d.h): the wo
 SHADE_MAX_NOISE_Q = 1023         # ROPE_SHADE_MAX_NOISE_Q
 NEQ_WORDS = 32                   # ROPE_NEQ_WORDS: the doubles rope_pose_normal_equations writes per frame
 BNEQ_WORDS = 96                  # ROPE_BNEQ_WORDS: the doubles rope_bundle_normal_equations writes per frame
+SIL_MAX_RADIUS = 16              # ROPE_SIL_MAX_RADIUS: the largest truncation of rope_mask_distance's field, pixels
 # rope_shade_params (include/rope_s3d.h), 64 bytes a record
 SHADE_DTYPE = np.dtype([('light', '<f4', 3), ('ambient', '<f4'), ('gain', '<f4', 3), ('bg_depth', '<f4'), ('noise_q', '<i4'), ('bg_index', '<i4'),
                         ('albedo', 'u1', (6, 3)), ('bg_colour', 'u1', 3), ('reserved', 'u1', 3)])
@@ -37,7 +38,8 @@ ABI_SYMBOLS = (
     'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes', 'rope_frame_agreement',
     'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align',
     'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace', 'rope_camera_normal_equations',
-    'rope_bundle_normal_equations', 'rope_bundle_normal_workspace')
+    'rope_bundle_normal_equations', 'rope_bundle_normal_workspace',
+    'rope_mask_distance', 'rope_silhouette_normal_equations', 'rope_silhouette_normal_workspace')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -171,6 +173,11 @@ def load_library(path: str = None):
                                                  C.c_float, vp, vp, vp]
     lib.rope_bundle_normal_workspace.argtypes = [i32, i32, i32]
     lib.rope_bundle_normal_workspace.restype = C.c_size_t
+    lib.rope_mask_distance.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.rope_silhouette_normal_equations.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, i32, vp, i32,
+                                                     i32, vp, vp, vp]
+    lib.rope_silhouette_normal_workspace.argtypes = [i32, i32, i32]
+    lib.rope_silhouette_normal_workspace.restype = C.c_size_t
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_eval_views.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.rope_set_target_tsweep.argtypes = [vp, vp]
@@ -683,6 +690,83 @@ class Engine:
                                  f"positive), intrinsics {(fx, fy, cx, cy)}")
             if rc:
                 raise EngineError(f"rope_bundle_normal_equations failed ({rc})")
+            return out.cpu().numpy()
+
+    def mask_distance(self, mask_t, radius: int):
+        """rope_mask_distance: N masks -> (N, H, W) int32 on the device, the truncated signed squared distance of every pixel to
+        its mask's boundary: -m inside the mask, +m outside, m the least dx^2 + dy^2 to a pixel of the other state within radius
+        pixels and inside the image, radius^2 + 1 where there is none (include/rope_s3d.h).  mask_t (N, H, W) bool or uint8, a
+        contiguous torch tensor on this engine's device, non-zero = robot; radius 1 .. 16.  The kernel runs on torch's current
+        stream and nothing is waited for."""
+        import torch
+        if not isinstance(mask_t, torch.Tensor) or mask_t.dtype not in (torch.uint8, torch.bool) or mask_t.dim() != 3 or not mask_t.is_contiguous():
+            raise ValueError("mask: a contiguous (N, H, W) uint8 or bool tensor")
+        if mask_t.device.type != 'cuda' or mask_t.device.index != self.device:
+            raise ValueError(f"mask must be on cuda:{self.device}, got {mask_t.device}")
+        if int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
+            raise ValueError(f"radius: a whole number in 1 .. {SIL_MAX_RADIUS}, got {radius}")
+        N, H, W = mask_t.shape
+        dev = mask_t.device
+        with torch.cuda.device(dev):
+            sd2 = torch.empty((N, H, W), dtype=torch.int32, device=dev)
+            if N == 0:
+                return sd2
+            rc = self._lib.rope_mask_distance(C.c_void_p(mask_t.data_ptr()), int(N), int(H), int(W), int(radius), C.c_void_p(sd2.data_ptr()),
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc == -1:
+            raise ValueError(f"rope_mask_distance refused its arguments: {N} planes of {H} x {W} (fewer than 2^31 pixels), radius {radius}")
+        if rc:
+            raise EngineError(f"rope_mask_distance failed ({rc})")
+        return sd2
+
+    def silhouette_normal_equations(self, render_depth, render_ids, sd2, joint_axes, twists, n_links: int, radius: int, intr) -> np.ndarray:
+        """rope_silhouette_normal_equations: the outline of N renders against the distance fields of the N frames' masks -> (N, 96)
+        float64 in bundle_normal_equations' layout and slots, per frame [0] the contour pixels of the render, [1] their sum of e^2
+        (e the signed distance of the pixel's outer edge to the mask's boundary, pixels, truncated at radius), [2] the contour
+        pixels within radius of the boundary, [3] their sum of e^2, [4 + c] J_c^T e, [16..93] the upper triangle of J^T J, [94],
+        [95] 0 (include/rope_s3d.h).  sd2 (N, H, W) int32: mask_distance's of the same radius.  One-directional: the render's
+        outline is measured against the mask.  Everything else — the renders, joint_axes, twists, intr, the stream, determinism,
+        the empty batch — is bundle_normal_equations'."""
+        import torch
+        for name, t, dt in (('render_depth', render_depth, torch.float32), ('render_ids', render_ids, torch.uint8), ('sd2', sd2, torch.int32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
+            if t.device.type != 'cuda' or t.device.index != self.device:
+                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
+            if t.shape != render_depth.shape:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {tuple(render_depth.shape)}")
+        N, H, W = render_depth.shape
+        dev = render_depth.device
+        if joint_axes is None and twists is None:
+            raise ValueError("joint_axes and twists: at least one of them")
+        cols = []
+        for name, c, what in (('joint_axes', joint_axes, 'axis and a point on it per joint'), ('twists', twists, 'angular and linear part per column')):
+            if c is not None and not isinstance(c, torch.Tensor):
+                c = torch.from_numpy(np.ascontiguousarray(c, np.float64))
+            if c is not None and (c.dtype != torch.float64 or c.dim() != 3 or c.shape[0] != N or c.shape[2] != 6):
+                raise ValueError(f"{name}: ({N}, n, 6) float64 — {what}, got {tuple(c.shape)} {c.dtype}")
+            cols.append(c)
+        counts = [0 if c is None else int(c.shape[1]) for c in cols]
+        if int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
+            raise ValueError(f"radius: a whole number in 1 .. {SIL_MAX_RADIUS}, got {radius}")
+        if N == 0:
+            return np.zeros((0, BNEQ_WORDS), np.float64)
+        fx, fy, cx, cy = (float(v) for v in intr)
+        with torch.cuda.device(dev):
+            cols = [None if c is None or n == 0 else c.to(dev).contiguous() for c, n in zip(cols, counts)]
+            ptrs = [None if c is None else C.c_void_p(c.data_ptr()) for c in cols]
+            out = torch.empty((N, BNEQ_WORDS), dtype=torch.float64, device=dev)
+            work = torch.empty(max(1, self._lib.rope_silhouette_normal_workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
+            rc = self._lib.rope_silhouette_normal_equations(C.c_void_p(render_depth.data_ptr()), C.c_void_p(render_ids.data_ptr()),
+                                                            C.c_void_p(sd2.data_ptr()), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
+                                                            ptrs[0], counts[0], ptrs[1], counts[1], int(radius), C.c_void_p(out.data_ptr()),
+                                                            C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if rc == -1:
+                raise ValueError(f"rope_silhouette_normal_equations refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), "
+                                 f"n_links {n_links} (1 .. 6), {counts[0]} joints and {counts[1]} twists (0 .. 6 each, not both 0), radius "
+                                 f"{radius}, intrinsics {(fx, fy, cx, cy)}")
+            if rc:
+                raise EngineError(f"rope_silhouette_normal_equations failed ({rc})")
             return out.cpu().numpy()
 
     def _normal_equations(self, entry: str, render_depth, render_ids, frame_depth, columns, col_name: str, col_what: str, n_links: int,

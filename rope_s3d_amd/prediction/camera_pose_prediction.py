@@ -124,9 +124,10 @@ class _CameraStageMachine:
 
     def __init__(self, base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine=False):
         self.base_pose = np.array(base_pose, dtype=float)
-        if isinstance(refine, str) and refine != 'bundle':
-            raise ValueError(f"refine: True, False or 'bundle', got {refine!r}")
-        self.refine, self.last_refinement, self._refiner = refine if refine == 'bundle' else bool(refine), None, None
+        if isinstance(refine, str) and refine not in ('bundle', 'bundle+silhouette'):
+            raise ValueError(f"refine: True, False, 'bundle' or 'bundle+silhouette', got {refine!r}")
+        self.refine, self.last_refinement, self._refiner = refine if isinstance(refine, str) else bool(refine), None, None
+        self._robot_masks = None
         self.ds_factor, self.preview = ds_factor, preview
         self.min_ang_inc = np.asarray(min_angle_inc, dtype=float)
         self.history_length = history_length
@@ -327,15 +328,23 @@ class _CameraStageMachine:
         """The continuous last step (refinement.CameraPoseRefiner) on the pose the stages ended on, against the down-sampled depth
         frames of this run at the working resolution; `last_refinement` keeps its result.  With the switch off: the pose as it is.
         refine='bundle': refinement.BundleRefiner in 'frame' mode instead — S, L and U of every frame are unknowns beside the camera,
-        so an encoder error is not absorbed into the pose; the caller's recorded angles are not changed."""
+        so an encoder error is not absorbed into the pose; the caller's recorded angles are not changed.
+        refine='bundle+silhouette': the same with the outline term at weight 1 (BundleRefiner(silhouette=1)) against the robot masks
+        of this run (`_robot_masks`: the run's own, one per frame)."""
         self.last_refinement = None
         if not self.refine:
             return pose
         if self._refiner is None:
             from .refinement import BundleRefiner, CameraPoseRefiner
-            self._refiner = (BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame') if self.refine == 'bundle'
-                             else CameraPoseRefiner(self.renderer, self.renderer.intrinsics))
-        self.last_refinement = self._refiner.refine(pose, self.robot_poses, np.asarray(self._tgt_depths, np.float32))
+            if self.refine == 'bundle+silhouette':
+                self._refiner = BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame', silhouette=1.0)
+            else:
+                self._refiner = (BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame') if self.refine == 'bundle'
+                                 else CameraPoseRefiner(self.renderer, self.renderer.intrinsics))
+        if self.refine == 'bundle+silhouette':
+            self.last_refinement = self._refiner.refine(pose, self.robot_poses, np.asarray(self._tgt_depths, np.float32), self._robot_masks)
+        else:
+            self.last_refinement = self._refiner.refine(pose, self.robot_poses, np.asarray(self._tgt_depths, np.float32))
         return self.last_refinement.pose.copy()
 
     def _start(self, og_images, target_depths, robot_poses, starting_camera_pose):
@@ -391,7 +400,9 @@ class ModellessCameraPredictor(_CameraStageMachine):
                  base_intrinsics='1280_720_color', *, device: int = 0, refine=False):
         """`refine`: True polishes the pose the stages end on with refinement.CameraPoseRefiner and keeps its CameraRefineResult (the
         pooled formal sigma of the six parameters, every frame's own cost) in `last_refinement`; 'bundle' polishes it together with
-        every frame's S, L and U (refinement.BundleRefiner, 'frame' mode) and keeps the BundleRefineResult."""
+        every frame's S, L and U (refinement.BundleRefiner, 'frame' mode) and keeps the BundleRefineResult; 'bundle+silhouette' adds
+        the outline term.  This predictor has no segmentation: its robot mask is where the down-sampled depth frame holds a
+        measurement, which is the robot only for frames whose background carries no depth (synthetic sets, background removed)."""
         super().__init__(base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine)
 
     def _setStages(self):
@@ -402,6 +413,7 @@ class ModellessCameraPredictor(_CameraStageMachine):
         self._preview_targets(og_images[0], target_depths[0])
         self._tgt_depths = self._batch_downsample(target_depths, self.ds_factor)
         self._n_pix = float(self._tgt_depths.shape[1] * self._tgt_depths.shape[2])
+        self._robot_masks = np.asarray(self._tgt_depths) > 0 if self.refine == 'bundle+silhouette' else None
         self._frame_planes = (np.stack([pack_target(d) for d in self._tgt_depths]), self._tgt_depths.astype(np.float32))
         self.engine.set_frames(self.robot_poses, *self._frame_planes)
         if self.stages is None:
@@ -496,6 +508,9 @@ class CameraPredictor(_CameraStageMachine):
         if self.stages is None:
             self._setStages()
         self._load_targets(segmentation_data, target_depths)
+        if self.refine == 'bundle+silhouette':          # every frame's own links, merged: not the planes shared by all frames
+            self._robot_masks = np.stack([np.any([d[k]['mask'] for k in self.link_names if k in d] or [np.zeros(target_depths.shape[1:], bool)],
+                                                 axis=0) for d in segmentation_data])
         return self._polish(self.run_stages(pose))
 
     def _errors(self, poses):

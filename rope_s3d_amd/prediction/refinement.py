@@ -327,6 +327,7 @@ class CameraPoseRefiner:
 # ---------------------------------------------------------------------------------------------- angles and camera in one solve
 BNEQ_WORDS = 96
 BNEQ_SLOTS = 12
+SIL_MAX_RADIUS = 16             # ROPE_SIL_MAX_RADIUS
 
 
 @dataclass
@@ -343,6 +344,10 @@ class BundleRefineResult:
     steps_taken: int            # accepted steps, 0 .. iterations
     inliers: float              # pixels of all frames that carried the final system
     frame_cost: np.ndarray      # (N,) every frame's own mean truncated cost at the end
+    # the silhouette term (BundleRefiner(silhouette > 0)); the fields above keep their depth meaning, nan / 0 without depth frames
+    cost_silhouette_before: float = float('nan')    # pooled mean truncated squared outline distance at the start, pixels^2
+    cost_silhouette_after: float = float('nan')     # the same at the end
+    inliers_silhouette: float = 0.0                 # contour pixels of all frames that carried the final system
 
 
 def unpack_bundle(words: np.ndarray):
@@ -492,12 +497,25 @@ class BundleRefiner:
                         complement); 'offset': ONE zero offset per active joint, added to every frame's input angles (kinematic
                         calibration: a pooled 12-column system)
     clip, iterations, damping   as PoseRefiner's; ONE damping for the whole system, multiplied by 10 whenever a step is refused.
-                        A step is kept only if the pooled cost sum [1] / sum [0] over all frames is strictly smaller."""
+                        A step is kept only if the pooled cost sum [1] / sum [0] over all frames is strictly smaller.
+    silhouette          0 (the default): depth alone, exactly as before.  > 0: the weight of the outline term
+                        (rope_silhouette_normal_equations, csrc/rope_silhouette.hip) — refine then takes the frames' robot masks,
+                        and may go without depth frames altogether.  Both costs are normalised by their truncations, c_d = mean
+                        cost / clip^2 and c_s = mean outline cost / R'^2 with R' = sqrt(radius^2 + 1) - 0.5; a step is kept if
+                        c_d + silhouette c_s is strictly smaller, and the system solved is the sum of the two terms' words, each
+                        divided by its pixel count and truncation at the iterate held.  One-directional: the render's outline is
+                        measured against the mask
+    radius              1 .. 16 pixels: the truncation of the mask's distance field"""
 
     def __init__(self, renderer_or_engine, intrinsics, do_angles: str = 'SLU', do_params=(True,) * 6, joints: str = 'frame',
-                 clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3):
+                 clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3, silhouette: float = 0.0, radius: int = 8):
         if not (np.isfinite(clip) and clip > 0):
             raise ValueError(f"clip must be finite and positive, got {clip}")
+        if not (np.isfinite(silhouette) and silhouette >= 0):
+            raise ValueError(f"silhouette: a finite weight, 0 or more, got {silhouette}")
+        if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
+            raise ValueError(f"radius: a whole number of pixels in 1 .. {SIL_MAX_RADIUS}, got {radius}")
+        self.silhouette, self.radius = float(silhouette), int(radius)
         if iterations < 0 or not (np.isfinite(damping) and damping >= 0):
             raise ValueError("iterations and damping must not be negative")
         if joints not in ('frame', 'offset'):
@@ -538,11 +556,15 @@ class BundleRefiner:
         twists = np.tile(camera_twists(pose)[None], (N, 1, 1)) if self.active_c else None
         return self.engine.bundle_normal_equations(rd, ri, depth_t, axes, twists, self.n_links, self.clip, (intr.fx, intr.fy, intr.cx, intr.cy))
 
-    def refine(self, camera_pose, angles, depth) -> BundleRefineResult:
+    def refine(self, camera_pose, angles, depth, mask=None) -> BundleRefineResult:
         """camera_pose (6,); angles (N, 6); depth (N, H, W) metres at the refiner's resolution, a numpy array or a torch tensor on
-        the host or the device, 0 / NaN where nothing was measured.  The sigmas are FORMAL (schur_sigma, formal_sigma): good for
-        telling what the views pin down and for ranking, not error bars to be taken at face value."""
+        the host or the device, 0 / NaN where nothing was measured.  mask (N, H, W) bool or uint8, non-zero = robot, likewise: read
+        only with silhouette > 0, and required then; depth may then be None (the outline alone, for colour-only frames).  The
+        sigmas are FORMAL (schur_sigma, formal_sigma): good for telling what the views pin down and for ranking, not error bars to
+        be taken at face value."""
         import torch
+        if self.silhouette > 0:
+            return self._refine_with_silhouette(camera_pose, angles, depth, mask)
         pose = np.array(camera_pose, np.float64).reshape(6)
         q0 = np.ascontiguousarray(np.array(angles, np.float64).reshape(-1, 6))
         N = len(q0)
@@ -588,3 +610,119 @@ class BundleRefiner:
         s = bundle_columns_sigma(pooled, slots)
         return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), s[6:], None, s[:6], cost_before, cost, steps,
                                   float(pooled[2]), frame_cost)
+
+    # ------------------------------------------------------------------------------------------ depth and outline together
+    def equations_both(self, pose, angles: np.ndarray, depth_t, sd2_t):
+        """equations' render, axes and twists, handed to both kernels -> (depth words (N, 96) or None without depth_t, outline
+        words (N, 96))."""
+        from ..projection import camera_matrix
+        intr = self.intrinsics
+        angles = np.ascontiguousarray(angles, np.float64)
+        N = len(angles)
+        PV = np.tile(camera_matrix(pose, intr)[None], (N, 1, 1))
+        rd, ri = self.engine.render_batch_device(angles, self.n_links, PV)
+        axes = self.joint_axes(pose, angles) if self.active_j else None
+        twists = np.tile(camera_twists(pose)[None], (N, 1, 1)) if self.active_c else None
+        intr4 = (intr.fx, intr.fy, intr.cx, intr.cy)
+        w_d = None if depth_t is None else self.engine.bundle_normal_equations(rd, ri, depth_t, axes, twists, self.n_links, self.clip, intr4)
+        return w_d, self.engine.silhouette_normal_equations(rd, ri, sd2_t, axes, twists, self.n_links, self.radius, intr4)
+
+    def _refine_with_silhouette(self, camera_pose, angles, depth, mask) -> BundleRefineResult:
+        import torch
+        if mask is None:
+            raise ValueError("silhouette > 0: refine needs the frames' robot masks (mask=)")
+        pose = np.array(camera_pose, np.float64).reshape(6)
+        q0 = np.ascontiguousarray(np.array(angles, np.float64).reshape(-1, 6))
+        N = len(q0)
+        frame_mode = self.mode == 'frame'
+        slots = self.active_j + [6 + k for k in self.active_c]
+        nan = float('nan')
+        if N == 0:
+            sp, so = np.full(6, np.nan), np.full(6, np.nan)
+            sp[self.active_c], so[self.active_j] = np.inf, np.inf
+            return BundleRefineResult(pose, q0, np.full(6, np.nan) if frame_mode else np.zeros(6), sp, np.zeros((0, 6)) if frame_mode else None,
+                                      None if frame_mode else so, np.inf if depth is not None else nan, np.inf if depth is not None else nan, 0, 0.0,
+                                      np.zeros(0), np.inf, np.inf, 0.0)
+        device = torch.device('cuda', self.engine.device)
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(mask))
+        if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 3 or mask.shape[0] != N:
+            raise ValueError(f"mask: ({N}, H, W) bool or uint8, got {tuple(mask.shape)} {mask.dtype}")
+        mask_t = mask.to(device=device).ne(0).to(torch.uint8).contiguous()
+        depth_t = None
+        if depth is not None:
+            if not isinstance(depth, torch.Tensor):
+                depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32))
+            depth_t = depth.to(device=device, dtype=torch.float32).contiguous()
+            if depth_t.dim() != 3 or depth_t.shape != mask_t.shape:
+                raise ValueError(f"depth: {tuple(mask_t.shape)} as the masks, got {tuple(depth_t.shape)}")
+        sd2_t = self.engine.mask_distance(mask_t, self.radius)                          # once: the masks do not move
+        far = np.sqrt(self.radius * self.radius + 1.0) - 0.5                            # R'
+        norm_d, norm_s = self.clip * self.clip, far * far
+
+        def costs(p_d, p_s):
+            """pooled words -> (mean depth cost or nan, mean outline cost, the cost a step is judged by)"""
+            c_s = p_s[1] / p_s[0] if p_s[0] > 0 else np.inf
+            if p_d is None:
+                return nan, float(c_s), float(self.silhouette * (c_s / norm_s))
+            c_d = p_d[1] / p_d[0] if p_d[0] > 0 else np.inf
+            return float(c_d), float(c_s), float(c_d / norm_d + self.silhouette * (c_s / norm_s))
+
+        def weighted(w_d, a_d, w_s, a_s):
+            """a_d w_d + a_s w_s on the words of the system, [4 .. 93]; the rest 0"""
+            out = np.zeros_like(w_s)
+            out[..., 4:94] = a_s * w_s[..., 4:94] if w_d is None else a_d * w_d[..., 4:94] + a_s * w_s[..., 4:94]
+            return out
+
+        def system(w_d, p_d, w_s, p_s):
+            a_d = 1.0 / (p_d[0] * norm_d) if p_d is not None and p_d[0] > 0 else 0.0
+            a_s = self.silhouette / (p_s[0] * norm_s) if p_s[0] > 0 else 0.0
+            return weighted(w_d, a_d, w_s, a_s)
+
+        q, off = q0.copy(), np.zeros(6)
+        lam = self.damping
+        w_d, w_s = self.equations_both(pose, q, depth_t, sd2_t)
+        p_d, p_s = None if w_d is None else pool_bundle(w_d), pool_bundle(w_s)
+        cd, cs, cost = costs(p_d, p_s)
+        cd_before, cs_before, steps = cd, cs, 0
+        for _ in range(self.iterations):
+            words = system(w_d, p_d, w_s, p_s)
+            if frame_mode:
+                dq, dc = schur_step(words, self.active_j, self.active_c, lam)
+                t_pose, t_off, t_q = pose + dc, off, np.clip(q + dq, self.limits[:, 0], self.limits[:, 1])
+            else:
+                d = bundle_columns_step(pool_bundle(words), slots, lam)
+                t_pose, t_off = pose + d[6:], off + d[:6]
+                t_q = np.clip(q0 + t_off, self.limits[:, 0], self.limits[:, 1])
+            wt_d, wt_s = self.equations_both(t_pose, t_q, depth_t, sd2_t)
+            pt_d, pt_s = None if wt_d is None else pool_bundle(wt_d), pool_bundle(wt_s)
+            ct_d, ct_s, c_t = costs(pt_d, pt_s)
+            if c_t < cost:                                              # strictly smaller, or everything is put back
+                pose, off, q, w_d, w_s, p_d, p_s, cd, cs, cost = t_pose, t_off, t_q, wt_d, wt_s, pt_d, pt_s, ct_d, ct_s, c_t
+                steps += 1
+            else:
+                lam *= 10.0
+
+        # the sigmas: the information of the two terms added, each over its own s^2 = [3] / ([2] - p).  The sum goes through
+        # schur_sigma / bundle_columns_sigma with [2] = p + 1 and [3] = 1, which makes their own factor s^2 exactly 1.
+        terms = [(w, pl) for w, pl in ((w_d, p_d), (w_s, p_s)) if w is not None]
+        if frame_mode:
+            frames, kc, _, _ = _arrow_blocks(sum(w for w, _ in terms), self.active_j, self.active_c)
+            p = len(kc) + sum(len(fr[0]) for fr in frames)
+        else:
+            A, _ = unpack_bundle(sum(pl for _, pl in terms))
+            p = sum(1 for c in slots if A[c, c] > 0)
+        info = np.zeros_like(w_s)
+        for w, pl in terms:
+            if p > 0 and pl[2] >= p + 1 and pl[3] > 0:
+                info[:, 4:94] += w[:, 4:94] / (pl[3] / (pl[2] - p))
+        if info.any():
+            info[0, 2], info[0, 3] = p + 1.0, 1.0
+        inl_d = 0.0 if p_d is None else float(p_d[2])
+        frame_cost = np.full(N, np.nan) if w_d is None else mean_cost(w_d[:, :NEQ_WORDS])
+        if frame_mode:
+            sq, sc = schur_sigma(info, self.active_j, self.active_c)
+            return BundleRefineResult(pose, q, np.full(6, np.nan), sc, sq, None, cd_before, cd, steps, inl_d, frame_cost, cs_before, cs, float(p_s[2]))
+        s = bundle_columns_sigma(pool_bundle(info), slots)
+        return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), s[6:], None, s[:6], cd_before, cd, steps,
+                                  inl_d, frame_cost, cs_before, cs, float(p_s[2]))
