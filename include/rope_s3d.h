@@ -842,6 +842,88 @@ int rope_silhouette_normal_equations(const float *render_depth_dev, const uint8_
                                      const double *twists_dev, int n_cols, int radius, double *out_dev, double *work_dev, void *stream);
 size_t rope_silhouette_normal_workspace(int n_frames, int H, int W);
 
+/* ---- The polish, natively (csrc/rope_polish.hip; prediction/refinement.py, PoseRefiner(native=True); tests/polish_ref.py restates
+ * the text below with plain loops over Python floats).  What rope_pose_normal_equations leaves to its caller — the joint axes of a
+ * pose, the Levenberg step, the formal variances, and the loop around them — for a host that is not Python.
+ * Every float64 operation written below is ONE correctly rounded IEEE operation in the order written; nothing is fused.
+ * A frame's words w are rope_pose_normal_equations': A[i][j] = A[j][i] = w[10 + 6 i - i (i - 1) / 2 + (j - i)] for i <= j, g[j] = w[4 + j].
+ * idx: the joints j with bit j of active_mask set and A[j][j] > 0, ascending; p = |idx|.
+ * THE ELIMINATION of a p x p system M x = b:  for k = 0 .. p - 1: the pivot row is k, replaced by each r = k + 1 .. p - 1 in turn
+ * whose |M[r][k]| is greater than the greatest so far (the FIRST row with the largest magnitude; a NaN is never greater); a pivot
+ * M[r][k] that is 0 or not finite makes the system SINGULAR; rows k and r are swapped; for i > k: f = M[i][k] / M[k][k], for c > k
+ * ascending M[i][c] = M[i][c] - f M[k][c], and b[i] = b[i] - f b[k].  Then for i = p - 1 .. 0: s = b[i]; for c = i + 1 .. p - 1
+ * ascending s = s - M[i][c] x[c]; x[i] = s / M[i][i].
+ *
+ * rope_joint_axes: per frame the six joints' unit axis and a point on it in camera axes: n_frames x 6 x 6 doubles in joints_dev, the
+ * layout rope_pose_normal_equations takes.  One thread per frame.
+ *   ctx                  a context with its robot set (rope_set_robot / rope_set_robot_mesh): the chain is the context's joint_fixed
+ *                        and joint_axes and the renderer's own code (csrc/rope_fk.h): T = identity; for joint j = 0 .. 5:
+ *                        T = T (F_j Rot(a_j, q_j)), the transform of link j + 1, with the device's deterministic sine and cosine
+ *   q_dev                n_frames x 6 doubles, DEVICE, 8-byte aligned
+ *   Rwc, tc              9 and 3 HOST doubles, finite: X_c = Rwc (X_w - tc), camera axes x right, y down, z forward
+ *   joints_dev           n_frames x 36 doubles out, DEVICE, 8-byte aligned
+ * With dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z, after link j + 1's T:  a_w = (dot(T row r rotation part, a_j)) r = 0 .. 2;
+ * o = (T[r][3] - tc[r]);  axis[r] = dot(Rwc row r, a_w);  point[r] = dot(Rwc row r, o).
+ * It differs from the numpy mirror (refinement.joint_axes_camera) by the device's sine against libm's (<= 1 ulp) and the order of
+ * the 3 x 3 products.  ROPE_E_ARG, with nothing enqueued, without a robot, for n_frames < 1, a null or misaligned pointer, an Rwc or
+ * tc that is not finite.
+ *
+ * rope_levenberg_step: per frame refinement.levenberg_step and the clip to the limits.  One thread per frame.
+ *   words_dev            n_frames x ROPE_NEQ_WORDS doubles, DEVICE, 8-byte aligned
+ *   q_dev, lam_dev       n_frames x 6 and n_frames doubles, DEVICE, 8-byte aligned: the angles and each frame's damping (a negative
+ *                        or NaN damping is the caller's business)
+ *   active_mask          0 .. 63: bit j set = joint j is refined
+ *   limits               12 HOST doubles lo_0 hi_0 .. lo_5 hi_5, finite, lo <= hi
+ *   trial_dev            n_frames x 6 doubles out, DEVICE, 8-byte aligned; written completely
+ * M = A[idx][idx] with the diagonal M[k][k] = A_kk + lam A_kk; b = -g[idx]; x by the elimination.  d[idx[k]] = x[k], every other d[j] = 0;
+ * d = 0 for all six joints when p = 0, when the system is singular or when any x is not finite.
+ * v = q[j] + d[j];  v = lo_j if v < lo_j;  v = hi_j if v > hi_j;  trial[j] = v.
+ *
+ * rope_formal_variance: per frame the SQUARE of refinement.formal_sigma (the caller takes the root: how a device rounds a float64
+ * square root never enters).  One thread per frame.
+ *   words_dev, active_mask   as above;   var_dev   n_frames x 6 doubles out, DEVICE, 8-byte aligned; written completely
+ * var[j] = NaN for a joint outside active_mask.  Every active joint gets +inf when p = 0, when w[2] < p + 1, when the block is
+ * singular, or when any variance is not finite or is negative.  Otherwise var[idx[k]] = (w[3] / (w[2] - p)) x_k[k], x_k solving
+ * A[idx][idx] x = e_k by the elimination (no damping), and an active joint outside idx keeps +inf.
+ * The systems of a workgroup lie in LDS (64 frames x 42 or 48 doubles); no kernel of the file uses scratch
+ * (tests/test_polish_resources.py).
+ * Both: ROPE_E_ARG, with nothing enqueued and the output untouched, for n_frames < 1, a null or misaligned pointer, an active_mask
+ * outside 0 .. 63, and for the step limits that are null, not finite or have lo > hi.  ROPE_E_HIP when the runtime refuses the launch.
+ *
+ * rope_refine_poses: PoseRefiner.refine's loop.  Robot and camera are set on the context; n = min(n_links, 6) links are drawn.
+ *   q                    n_frames x 6 HOST doubles: the poses to polish (finite, |q| <= 1e4)
+ *   frame_depth_dev      n_frames planes H x W float32 metres, H x W the camera's (rope_set_camera), DEVICE, 4-byte aligned
+ *   camera_pose6         [x, y, z, a3, a4, a5] as rope_camera_matrix takes it.  With R its camera-to-world rotation (the same host
+ *                        code, libm's sine and cosine): Rwc row 0 = column 0 of R, rows 1 and 2 = the NEGATED columns 1 and 2 of R
+ *                        (diag(1, -1, -1) R^T), tc = (x, y, z)
+ *   fx, fy, cx, cy, clip_m   rope_pose_normal_equations';   active_mask, limits   rope_levenberg_step's
+ *   iterations           >= 0: rounds at most;   damping   finite, >= 0: every frame's lam at the start
+ *   work_dev             rope_refine_workspace(ctx, n_frames) bytes, DEVICE, 8-byte aligned
+ *   angles_out, var_out  n_frames x 6 HOST doubles;  cost_before, cost_after, inliers_out  n_frames HOST doubles;  steps_out n_frames
+ *                        int32;  words_out  n_frames x ROPE_NEQ_WORDS HOST doubles, the final systems, or NULL
+ * equations(a): rope_render_batch_device at the angles a (whole frame, n links), rope_joint_axes at a, rope_pose_normal_equations
+ * with n_links = n and n_joints = 6.  cost(w) = w[0] > 0 ? w[1] / w[0] : +inf.
+ *   words = equations(q); cost = cost_before = cost(words); lam = damping; steps = 0.  `iterations` times: trial =
+ *   rope_levenberg_step; w_t = equations(trial); per frame, if cost(w_t) < cost (strictly): q = trial, words = w_t, cost = cost(w_t),
+ *   steps += 1; else lam = lam 10.  Then var = rope_formal_variance(words), inliers = words[2], cost_after = cost.
+ * Systems, angles, damping, costs and step counts stay on the device between the rounds.  The raster path takes HOST rows, so each
+ * round brings its n_frames x 6 trial angles down once and waits for them; nothing else crosses.  The call runs on the context's
+ * stream and is complete when it returns.  Like rope_render_batch_device it uses the per-candidate buffers: resident candidates and
+ * the results of the last evaluation do not survive it.  The same inputs give the same bytes, in one call or with the frames cut
+ * into several.  ROPE_E_ARG, with nothing enqueued and no output written, for whatever its parts refuse, robot or camera not set,
+ * iterations < 0, a damping that is negative or not finite, n_frames above 65535.
+ * rope_refine_workspace (host only): the bytes of work_dev — the renders (5 bytes a pixel), rope_pose_normal_workspace, and some
+ * 900 bytes a frame of state; 0 without a camera or for a batch the call refuses. */
+int rope_joint_axes(rope_ctx *ctx, const double *q_dev, int n_frames, const double *Rwc, const double *tc, double *joints_dev, void *stream);
+int rope_levenberg_step(const double *words_dev, const double *q_dev, const double *lam_dev, int n_frames, int active_mask, const double *limits,
+                        double *trial_dev, void *stream);
+int rope_formal_variance(const double *words_dev, int n_frames, int active_mask, double *var_dev, void *stream);
+int rope_refine_poses(rope_ctx *ctx, const double *q, const float *frame_depth_dev, int n_frames, const double *camera_pose6, float fx, float fy,
+                      float cx, float cy, int active_mask, const double *limits, float clip_m, int iterations, double damping, void *work_dev,
+                      double *angles_out, double *var_out, double *cost_before, double *cost_after, int32_t *steps_out, double *inliers_out,
+                      double *words_out);
+size_t rope_refine_workspace(rope_ctx *ctx, int n_frames);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

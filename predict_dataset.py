@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Predict every frame of a dataset (same command line as the reference's predict_dataset.py:58-64).
 
-    python predict_dataset.py <dataset> [-angs SLU] [-refine [-sigma FILE.npy]]
+    python predict_dataset.py <dataset> [-angs SLU] [-refine | -refine_native [-sigma FILE.npy]]
     python -m torch.distributed.run --nproc-per-node N ... predict_dataset.py <dataset>    # frames shard over N GPUs
 
 Frames are independent, so rank r predicts a contiguous block of frames on its own GPU and
@@ -69,13 +69,14 @@ def run(args):
         kwargs['lookup_divisions'] = int(args.lookup_divisions)
     if getattr(args, 'device_targets', False):
         kwargs['device_targets'] = True
-    refine = bool(getattr(args, 'refine', False))
+    native = bool(getattr(args, 'refine_native', False))
+    refine = bool(getattr(args, 'refine', False)) or native
     if getattr(args, 'sigma', None) and not refine:
         raise SystemExit("-sigma needs -refine: the sigmas come out of the refinement's normal equations")
     if refine:
         if int(getattr(args, 'predictors', 1) or 1) > 1:
             raise SystemExit("-refine runs with one Predictor (-predictors 1)")
-        kwargs['refine'] = True                               # Gauss-Newton polish of every prediction (prediction/refinement.py)
+        kwargs['refine'] = 'native' if native else True       # Gauss-Newton polish of every prediction (prediction/refinement.py)
     am = Predictor(ds_factor=args.ds_factor, camera_pose=ds.camera_pose[0], preview=False, base_intrin=ds.intrinsics,
                    do_angles=args.angs, model_ds=args.dataset, device=gpu, **kwargs)
     # Frames are independent (predict_dataset.py:43-44 is a plain loop; fresh state per frame, predict.py:144-148): ONE Predictor
@@ -165,6 +166,7 @@ if __name__ == "__main__":
                         help="With -segmenter maskrcnn: the network's masks stay on the GPU and the targets are built there "
                              "(Predictor(device_targets=True)); other segmenters do not offer that and run as without the flag.")
     parser.add_argument('-refine', action='store_true', help="Polish every prediction with Gauss-Newton steps on the depth residual (Predictor(refine=True)).")
+    parser.add_argument('-refine_native', action='store_true', help="-refine through rope_refine_poses: the loop and the solves inside the library (Predictor(refine='native')).")
     parser.add_argument('-sigma', type=str, default=None, help="With -refine: save the (n, 6) formal sigmas of the angles (rad; inf = not seen, nan = not refined) to this .npy.")
     parser.add_argument('-weights', type=str, default=None, help="weights for -segmenter maskrcnn: the reference's trained Keras .h5 or a torch state_dict (random weights otherwise).")
     run(parser.parse_args())

@@ -107,8 +107,9 @@ if __name__ == "__main__":
     parser.add_argument('-ds_factor', type=int, default=8)
     parser.add_argument('-frames', type=int, default=None)
     parser.add_argument('-refine', action='store_true', help="polish every prediction (Predictor(refine=True)) and print its largest formal sigma beside the deviation")
+    parser.add_argument('-refine_native', action='store_true', help="-refine through rope_refine_poses: the loop and the solves inside the library (Predictor(refine='native'))")
     args = parser.parse_args()
-    extra = {'refine': True} if args.refine else {}
+    extra = {'refine': 'native'} if args.refine_native else {'refine': True} if args.refine else {}
     if args.replay:
         ds = Dataset(args.replay)
         cam = DatasetCamera(ds)

@@ -251,6 +251,7 @@ struct rope_ctx {
 
 void rope_range_push(const char *name);                  // roctx ranges (rope_abi.hip); also used by rope_predict.cpp (per stage)
 void rope_range_pop();
+void rope_pose_rotation(const double *pose, double R[3][3]);    // rope_hostprep.cpp: camera-to-world rotation of [x, y, z, a3, a4, a5]
 struct RopeRange {
     explicit RopeRange(const char *name) { rope_range_push(name); }
     ~RopeRange() { rope_range_pop(); }

@@ -147,6 +147,23 @@ extern "C" int rope_prepare_synthetic(const uint8_t *color, int64_t color_stride
     return ROPE_OK;
 }
 
+// The camera-to-world rotation of a pose [x, y, z, a3, a4, a5]: rope_camera_matrix's R below, and what rope_refine_poses
+// (rope_polish.hip) turns into the kernels' camera axes.  One IEEE double operation per written step, sin / cos from libm.
+void rope_pose_rotation(const double *pose, double R[3][3])
+{
+    const double yaw = pose[5], pitch = pose[3], roll = pose[4] + 3.141592653589793 / 2;
+    const double c0 = std::cos(yaw), c1 = std::cos(pitch), c2 = std::cos(roll), s0 = std::sin(yaw), s1 = std::sin(pitch), s2 = std::sin(roll);
+    R[0][0] = c0 * c1;
+    R[1][0] = c1 * s0;
+    R[2][0] = -1 * s1;
+    R[0][1] = c0 * s1 * s2 - c2 * s0;
+    R[1][1] = c0 * c2 + (s0 * s1) * s2;
+    R[2][1] = c1 * s2;
+    R[0][2] = s0 * s2 + c0 * c2 * s1;
+    R[1][2] = c2 * s0 * s1 - c0 * s2;
+    R[2][2] = c1 * c2;
+}
+
 // Host only: camera pose + pinhole intrinsics -> P·V, the matrix rope_set_camera takes.  Every step is one IEEE double operation in
 // the written order (the library is built with -ffp-contract=off), sin / cos from libm.
 //   pose   [x, y, z, a3, a4, a5] as Renderer.setCameraPose takes it (render.py:107-111): roll = a4 + pi/2, pitch = a3, yaw = a5,
@@ -158,18 +175,8 @@ extern "C" int rope_camera_matrix(const double *pose, double fx, double fy, doub
                                   double *PV)
 {
     if (!pose || !PV || W < 1 || H < 1 || !(znear > 0.0) || !(zfar > znear)) return ROPE_E_ARG;
-    const double yaw = pose[5], pitch = pose[3], roll = pose[4] + 3.141592653589793 / 2;
-    const double c0 = std::cos(yaw), c1 = std::cos(pitch), c2 = std::cos(roll), s0 = std::sin(yaw), s1 = std::sin(pitch), s2 = std::sin(roll);
     double R[3][3];
-    R[0][0] = c0 * c1;
-    R[1][0] = c1 * s0;
-    R[2][0] = -1 * s1;
-    R[0][1] = c0 * s1 * s2 - c2 * s0;
-    R[1][1] = c0 * c2 + (s0 * s1) * s2;
-    R[2][1] = c1 * s2;
-    R[0][2] = s0 * s2 + c0 * c2 * s1;
-    R[1][2] = c2 * s0 * s1 - c0 * s2;
-    R[2][2] = c1 * c2;
+    rope_pose_rotation(pose, R);
     double V[4][4] = {};
     for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++) V[i][j] = R[j][i];

@@ -39,7 +39,8 @@ ABI_SYMBOLS = (
     'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align',
     'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace', 'rope_camera_normal_equations',
     'rope_bundle_normal_equations', 'rope_bundle_normal_workspace',
-    'rope_mask_distance', 'rope_silhouette_normal_equations', 'rope_silhouette_normal_workspace')
+    'rope_mask_distance', 'rope_silhouette_normal_equations', 'rope_silhouette_normal_workspace',
+    'rope_joint_axes', 'rope_levenberg_step', 'rope_formal_variance', 'rope_refine_poses', 'rope_refine_workspace')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -178,6 +179,13 @@ def load_library(path: str = None):
                                                      i32, vp, vp, vp]
     lib.rope_silhouette_normal_workspace.argtypes = [i32, i32, i32]
     lib.rope_silhouette_normal_workspace.restype = C.c_size_t
+    lib.rope_joint_axes.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    lib.rope_levenberg_step.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
+    lib.rope_formal_variance.argtypes = [vp, i32, i32, vp, vp]
+    lib.rope_refine_poses.argtypes = [vp, vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp, C.c_float, i32, dbl,
+                                      vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rope_refine_workspace.argtypes = [vp, i32]
+    lib.rope_refine_workspace.restype = C.c_size_t
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_eval_views.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.rope_set_target_tsweep.argtypes = [vp, vp]
@@ -805,6 +813,145 @@ class Engine:
             if rc:
                 raise EngineError(f"{entry} failed ({rc})")
             return out.cpu().numpy()
+
+    # -- the native polish (csrc/rope_polish.hip) ----------------------------------------------------
+    def _polish_tensor(self, name: str, t, cols, N=None):
+        """A float64 numpy array or tensor -> a contiguous float64 tensor (N, cols) (or (N,) for cols None) on this engine's device,
+        checked the way _normal_equations checks its columns."""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            t = torch.from_numpy(np.ascontiguousarray(t, np.float64))
+        shape = tuple(t.shape)
+        if t.dtype != torch.float64 or t.dim() != (1 if cols is None else 2) or (cols is not None and shape[1] != cols) or \
+                (N is not None and shape[0] != N):
+            raise ValueError(f"{name}: ({'N' if N is None else N}{'' if cols is None else f', {cols}'}) float64, got {shape} {t.dtype}")
+        if t.device.type == 'cuda' and t.device.index != self.device:
+            raise ValueError(f"{name} must be on cuda:{self.device} or on the host, got {t.device}")
+        return t.to(torch.device('cuda', self.device)).contiguous()
+
+    @staticmethod
+    def _active_mask(active_mask) -> int:
+        if isinstance(active_mask, bool) or int(active_mask) != active_mask or not 0 <= int(active_mask) <= 63:
+            raise ValueError(f"active_mask: bit j set = joint j is refined, 0 .. 63, got {active_mask!r}")
+        return int(active_mask)
+
+    @staticmethod
+    def _limits(limits) -> np.ndarray:
+        limits = np.ascontiguousarray(limits, np.float64)
+        if limits.shape != (6, 2) or not np.isfinite(limits).all() or (limits[:, 0] > limits[:, 1]).any():
+            raise ValueError("limits: (6, 2) finite [lo, hi] per joint with lo <= hi")
+        return limits
+
+    def joint_axes_device(self, q, Rwc, tc):
+        """rope_joint_axes: (N, 6) angles, a float64 numpy array or tensor -> (N, 6, 6) float64 tensor on this engine's device: per
+        joint its unit axis and a point on it in the camera axes X_c = Rwc (X_w - tc), by the chain the renders are drawn with
+        (include/rope_s3d.h) — what pose_normal_equations takes as `joints`.  Rwc (3, 3) and tc (3,) are host float64.  The kernel
+        runs on torch's current stream and nothing is waited for."""
+        import torch
+        q_t = self._polish_tensor('q', q, 6)
+        Rwc, tc = np.ascontiguousarray(Rwc, np.float64), np.ascontiguousarray(tc, np.float64)
+        if Rwc.shape != (3, 3) or tc.shape != (3,) or not (np.isfinite(Rwc).all() and np.isfinite(tc).all()):
+            raise ValueError("Rwc: (3, 3) and tc: (3,), finite float64")
+        N = q_t.shape[0]
+        dev = q_t.device
+        with torch.cuda.device(dev):
+            out = torch.empty((N, 6, 6), dtype=torch.float64, device=dev)
+            if N == 0:
+                return out
+            self._check(self._lib.rope_joint_axes(self._ctx, C.c_void_p(q_t.data_ptr()), int(N), _p(Rwc), _p(tc), C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'rope_joint_axes')
+        return out
+
+    def levenberg_step(self, words, q, lam, active_mask: int, limits):
+        """rope_levenberg_step: per frame (A + lam diag A) d = -g on the joints of active_mask with a positive diagonal, by Gaussian
+        elimination with partial pivoting, and trial = clip(q + d, limits) -> (N, 6) float64 tensor on the device; d = 0 for a
+        frame with no such joint, a singular system or a solution that is not finite (include/rope_s3d.h).  words (N, 32), q (N, 6),
+        lam (N,): float64 numpy arrays or tensors; limits (6, 2).  Runs on torch's current stream; nothing is waited for."""
+        import torch
+        words_t = self._polish_tensor('words', words, NEQ_WORDS)
+        N = words_t.shape[0]
+        q_t, lam_t = self._polish_tensor('q', q, 6, N), self._polish_tensor('lam', lam, None, N)
+        mask, limits = self._active_mask(active_mask), self._limits(limits)
+        dev = words_t.device
+        with torch.cuda.device(dev):
+            trial = torch.empty((N, 6), dtype=torch.float64, device=dev)
+            if N == 0:
+                return trial
+            rc = self._lib.rope_levenberg_step(C.c_void_p(words_t.data_ptr()), C.c_void_p(q_t.data_ptr()), C.c_void_p(lam_t.data_ptr()), int(N), mask,
+                                               _p(limits), C.c_void_p(trial.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc:
+            raise EngineError(f"rope_levenberg_step failed ({rc})")
+        return trial
+
+    def formal_variance(self, words, active_mask: int):
+        """rope_formal_variance: per frame s^2 diag(A^-1) on the joints of active_mask with a positive diagonal, s^2 = [3] / ([2] - p)
+        -> (N, 6) float64 tensor on the device: the SQUARE of refinement.formal_sigma — nan outside active_mask, inf where the
+        frame does not pin the joints down (include/rope_s3d.h).  Runs on torch's current stream; nothing is waited for."""
+        import torch
+        words_t = self._polish_tensor('words', words, NEQ_WORDS)
+        mask = self._active_mask(active_mask)
+        N = words_t.shape[0]
+        dev = words_t.device
+        with torch.cuda.device(dev):
+            var = torch.empty((N, 6), dtype=torch.float64, device=dev)
+            if N == 0:
+                return var
+            rc = self._lib.rope_formal_variance(C.c_void_p(words_t.data_ptr()), int(N), mask, C.c_void_p(var.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc:
+            raise EngineError(f"rope_formal_variance failed ({rc})")
+        return var
+
+    def refine_workspace(self, n_frames: int) -> int:
+        """rope_refine_workspace: the bytes of device scratch refine_poses needs for n_frames frames of the camera's size; 0 for a
+        batch one call does not take."""
+        return int(self._lib.rope_refine_workspace(self._ctx, int(n_frames)))
+
+    def refine_poses(self, q, frame_depth, camera_pose, intr, active_mask: int, limits, clip: float, iterations: int, damping: float,
+                     want_words: bool = False):
+        """rope_refine_poses: PoseRefiner.refine's loop inside the library — render, joint axes, normal equations, Levenberg steps
+        kept only when the cost falls, formal variances — with the systems and the solves on the device.
+        q (N, 6) host angles; frame_depth (N, H, W) float32 tensor on this engine's device, H x W the camera's; camera_pose
+        [x, y, z, a3, a4, a5]; intr (fx, fy, cx, cy); active_mask bit j = joint j; limits (6, 2).
+        -> dict(angles (N, 6), var (N, 6) — formal_sigma squared —, cost_before, cost_after, inliers (N,) float64, steps (N,) int32
+        [, words (N, 32) the final systems]).  Runs on the context's stream, after torch's current stream has finished with the
+        frames, and is complete on return.  Like render_batch_device it takes the per-candidate buffers."""
+        import torch
+        q = np.ascontiguousarray(q, np.float64).reshape(-1, 6)
+        N = len(q)
+        t = frame_depth
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
+            raise ValueError("frame_depth: a contiguous (N, H, W) torch.float32 tensor")
+        if t.device.type != 'cuda' or t.device.index != self.device:
+            raise ValueError(f"frame_depth must be on cuda:{self.device}, got {t.device}")
+        if tuple(t.shape) != (N, self.H, self.W):
+            raise ValueError(f"frame_depth: ({N}, {self.H}, {self.W}) as the poses and the camera, got {tuple(t.shape)}")
+        mask, limits = self._active_mask(active_mask), self._limits(limits)
+        pose = np.ascontiguousarray(camera_pose, np.float64).reshape(6)
+        if int(iterations) != iterations or iterations < 0 or not (np.isfinite(damping) and damping >= 0):
+            raise ValueError("iterations and damping must not be negative")
+        out = dict(angles=np.empty((N, 6)), var=np.empty((N, 6)), cost_before=np.empty(N), cost_after=np.empty(N), inliers=np.empty(N),
+                   steps=np.empty(N, np.int32))
+        if want_words:
+            out['words'] = np.empty((N, NEQ_WORDS))
+        if N == 0:
+            return out
+        nbytes = self.refine_workspace(N)
+        if nbytes == 0:
+            raise ValueError(f"rope_refine_poses takes no batch of {N} frames of {self.H} x {self.W} in one call")
+        fx, fy, cx, cy = (float(v) for v in intr)
+        dev = t.device
+        with torch.cuda.device(dev):
+            work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()            # the frames are ready, and `work` is no longer anyone else's
+            rc = self._lib.rope_refine_poses(self._ctx, _p(q), C.c_void_p(t.data_ptr()), int(N), _p(pose), fx, fy, cx, cy, mask, _p(limits),
+                                             float(clip), int(iterations), float(damping), C.c_void_p(work.data_ptr()), _p(out['angles']),
+                                             _p(out['var']), _p(out['cost_before']), _p(out['cost_after']), _p(out['steps']), _p(out['inliers']),
+                                             _p(out.get('words')))
+        if rc == -1:
+            raise ValueError(f"rope_refine_poses refused its arguments: {self._lib.rope_last_error(self._ctx).decode()}")
+        self._check(rc, 'rope_refine_poses')
+        return out
 
     def debug_targets(self, want_tsweep: bool = False):
         """rope_debug_targets: the resident set back on the host -> (tq (N,H,W) uint64, t32 (N,H,W) float32, tsweep planes or None,

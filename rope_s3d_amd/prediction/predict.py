@@ -177,9 +177,14 @@ class Predictor:
                           On the segmentation path the polish sees the body-masked depth (PreparedTarget.tgt_depth); with
                           device_targets it sees the reduced depth before masking, since the mask never leaves the device — so
                           there the two run_many paths give the same stage angles but may polish them differently.
+                          'native': the same polish through rope_refine_poses (PoseRefiner(native=True)): the loop, the solves and
+                          the sigmas inside the library instead of on the host.  True keeps the host loop.
         """
         self.device_targets = bool(device_targets)
         self.refine, self.last_refinement, self._refiner = bool(refine), None, None
+        self.refine_native = isinstance(refine, str) and refine == 'native'
+        if isinstance(refine, str) and not self.refine_native:
+            raise ValueError(f"refine: False, True or 'native', got {refine!r}")
         self.ds_factor, self.preview = ds_factor, preview
         if preview:                       # headless: frames go to .viz.frame and, with save_to, an uncompressed AVI
             from .viz import ProjectionViz
@@ -436,7 +441,7 @@ class Predictor:
         (N, 6); the RefineResult goes to last_refinement."""
         from .refinement import PoseRefiner
         if self._refiner is None:
-            self._refiner = PoseRefiner(self.renderer, self.camera_pose, self.intrinsics, self.do_angles)
+            self._refiner = PoseRefiner(self.renderer, self.camera_pose, self.intrinsics, self.do_angles, native=self.refine_native)
         elif np.any(self._refiner.camera_pose != self.camera_pose):
             self._refiner.setCameraPose(self.camera_pose)
         self.last_refinement = self._refiner.refine(np.asarray(angles, np.float64).reshape(-1, 6), depths)

@@ -124,10 +124,16 @@ class PoseRefiner:
     do_angles           the joints to refine, letters of 'SLUBRT'
     clip                metres at which a residual is truncated (the Verifier's tol means the same)
     iterations          rounds at most: iterations + 1 renders and kernel calls a batch
-    damping             the Levenberg factor a frame starts with; multiplied by 10 for a frame whenever its step is refused"""
+    damping             the Levenberg factor a frame starts with; multiplied by 10 for a frame whenever its step is refused
+    native              False (the default): the loop below, on the host, numpy's LAPACK for the solves.  True: refine is one
+                        Engine.refine_poses call per chunk of frames (rope_refine_poses, csrc/rope_polish.hip) — the same loop with
+                        the joint axes, the solves, accept / reject, damping and the variances on the device.  Same fields, same
+                        meanings; the numbers differ by the rounding of another elimination order and of the device's sine"""
+
+    NATIVE_WORK_BYTES = 512 << 20           # device scratch one native call may ask for: the frames are cut to fit
 
     def __init__(self, renderer_or_engine, camera_pose, intrinsics, do_angles: str = 'SLU', clip: float = 2 ** -5, iterations: int = 5,
-                 damping: float = 1e-3):
+                 damping: float = 1e-3, native: bool = False):
         if not (np.isfinite(clip) and clip > 0):
             raise ValueError(f"clip must be finite and positive, got {clip}")
         if iterations < 0 or not (np.isfinite(damping) and damping >= 0):
@@ -137,6 +143,7 @@ class PoseRefiner:
         self.intrinsics = intrinsics
         self.active = [int(j) for j in np.flatnonzero(str_to_arr(do_angles.upper()))]
         self.clip, self.iterations, self.damping = float(clip), int(iterations), float(damping)
+        self.native = bool(native)
         self.fk = ForwardKinematics()
         self.limits = np.asarray(self.fk.reader.joint_limits, np.float64)
         self.setCameraPose(camera_pose)
@@ -186,6 +193,8 @@ class PoseRefiner:
         depth_t = depth.to(device=device, dtype=torch.float32).contiguous()
         if depth_t.dim() != 3 or depth_t.shape[0] != N:
             raise ValueError(f"depth: ({N}, H, W), got {tuple(depth_t.shape)}")
+        if self.native:
+            return self._refine_native(q, depth_t)
         lam = np.full(N, self.damping)
         words = self.equations(q, depth_t)
         cost = mean_cost(words)
@@ -200,6 +209,19 @@ class PoseRefiner:
             steps += ok
             lam[~ok] *= 10.0
         return RefineResult(q, np.stack([formal_sigma(w, self.active) for w in words]), cost_before, cost, steps, words[:, 2].copy())
+
+
+    def _refine_native(self, q: np.ndarray, depth_t) -> RefineResult:
+        """refine through rope_refine_poses: one call per chunk of frames whose scratch fits NATIVE_WORK_BYTES."""
+        intr, N = self.intrinsics, len(q)
+        mask = sum(1 << j for j in self.active)
+        chunk = max(1, min(N, self.NATIVE_WORK_BYTES // max(1, self.engine.refine_workspace(1))))
+        parts = []
+        for lo in range(0, N, chunk):
+            r = self.engine.refine_poses(q[lo:lo + chunk], depth_t[lo:lo + chunk], self.camera_pose, (intr.fx, intr.fy, intr.cx, intr.cy), mask,
+                                         self.limits, self.clip, self.iterations, self.damping)
+            parts.append(RefineResult(r['angles'], np.sqrt(r['var']), r['cost_before'], r['cost_after'], r['steps'].astype(np.int64), r['inliers']))
+        return parts[0] if len(parts) == 1 else RefineResult.concatenate(parts)
 
 
 # ---------------------------------------------------------------------------------------------- the camera pose

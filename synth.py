@@ -10,7 +10,7 @@ def run(args):
     pose = DEFAULT_CAMERA_POSE
     if args.dataset not in (None, 'none'):
         pose = Dataset(args.dataset).camera_pose[0]
-    synth = SyntheticPredictor(pose, args.intrinsics, args.ds_factor, args.angs, noise=args.noise, refine=bool(getattr(args, 'refine', False)))
+    synth = SyntheticPredictor(pose, args.intrinsics, args.ds_factor, args.angs, noise=args.noise, refine='native' if getattr(args, 'refine_native', False) else bool(getattr(args, 'refine', False)))
     res = synth.run_batch(args.num, args.file, batch=getattr(args, 'batch', None))    # a namespace made without -batch (the suite's CLI test builds one) means the loop
     from rope_s3d_amd.prediction.analysis import Grapher
     Grapher(args.angs, res[1], res[0]).plot()
@@ -24,6 +24,7 @@ if __name__ == "__main__":
     parser.add_argument('-noise', action="store_true", help="Adds semi-realistic noise to depth images.")
     parser.add_argument('-batch', type=int, default=None, help="Frames per group kept on the GPU from render to prediction (default: one frame at a time).")
     parser.add_argument('-refine', action="store_true", help="Polish every prediction with Gauss-Newton steps on the depth residual (PoseRefiner).")
+    parser.add_argument('-refine_native', action="store_true", help="The same polish through rope_refine_poses: loop and solves inside the library (PoseRefiner(native=True)).")
     parser.add_argument('-ds_factor', type=int, default=8, choices=[1, 2, 4, 6, 8, 10, 12], help="Downsampling factor.")
     parser.add_argument('-angs', type=str, default='SLU', help="The joints to predict.")
     parser.add_argument('-intrinsics', type=str, default='1280_720_color', help="Base camera instrinsics to use.")
