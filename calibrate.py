@@ -31,6 +31,8 @@ def calibrate(args):
     h, w = full.shape[1] // f, full.shape[2] // f
     depth = np.stack([resize_linear(d, w, h) for d in full]).astype(np.float32) if f > 1 else full
     mask, extra = None, {}
+    if args.silhouette > 0 and args.native:
+        raise SystemExit("-native polishes on the depth term alone: it does not go with -silhouette")
     if args.silhouette > 0:
         # the robot masks: the frames' colour images reduced as the depth is, read by the colour code of the set (ColorSegmenter, what
         # Predictor(color_dict=...) sets reads its link masks with); masks made by a segmentation network are not taken here
@@ -49,17 +51,22 @@ def calibrate(args):
         extra = dict(silhouette=args.silhouette, radius=args.radius)
     renderer = Renderer('seg', pose0, str(ds.attrs['color_intrinsics']), intrinsic_ds_factor=f if f > 1 else None)
     try:
-        if args.joints == 'fixed':
+        if args.joints == 'fixed' and args.native:
+            # the camera alone through rope_refine_bundle: 'frame' mode with no joint refined
+            res = BundleRefiner(renderer, renderer.intrinsics, do_angles='', joints='frame', clip=args.clip, iterations=args.iterations,
+                                native=True).refine(pose0, angles, depth)
+            sigma_pose, out_angles = res.sigma_pose, angles
+        elif args.joints == 'fixed':
             res = CameraPoseRefiner(renderer, renderer.intrinsics, clip=args.clip, iterations=args.iterations).refine(pose0, angles, depth)
             sigma_pose, out_angles = res.sigma, angles
         else:
             res = BundleRefiner(renderer, renderer.intrinsics, do_angles=args.do_angles, joints=args.joints, clip=args.clip,
-                                iterations=args.iterations, **extra).refine(pose0, angles, depth, mask)
+                                iterations=args.iterations, native=args.native, **extra).refine(pose0, angles, depth, mask)
             sigma_pose, out_angles = res.sigma_pose, res.angles
     finally:
         renderer.engine.close()
     worst = np.argsort(-res.frame_cost)[:min(5, n)]
-    rep = dict(dataset=args.dataset, frames=n, joints=args.joints, do_angles=args.do_angles, ds_factor=f, clip=args.clip, start_pose=pose0.tolist(),
+    rep = dict(dataset=args.dataset, frames=n, joints=args.joints, native=bool(args.native), do_angles=args.do_angles, ds_factor=f, clip=args.clip, start_pose=pose0.tolist(),
                pose=res.pose.tolist(), sigma_pose=sigma_pose.tolist(), cost_before=float(res.cost_before), cost_after=float(res.cost_after),
                steps_taken=int(res.steps_taken), inliers=float(res.inliers), frame_cost=res.frame_cost.tolist(), worst_frames=worst.tolist())
     if args.silhouette > 0:
@@ -107,5 +114,7 @@ if __name__ == "__main__":
     parser.add_argument('-silhouette', type=float, default=0.0,
                         help="Weight of the outline term beside the depth term (0: off). Needs a colour-coded dataset (color_dict).")
     parser.add_argument('-radius', type=int, default=8, help="Pixels at which the outline distance is truncated, 1 .. 16.")
+    parser.add_argument('-native', action='store_true',
+                        help="Run the loop inside the library (rope_refine_bundle): the solves on the device. Depth term only.")
     parser.add_argument('-json', type=str, default=None, help="File for the report.")
     calibrate(parser.parse_args())

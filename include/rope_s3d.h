@@ -924,6 +924,117 @@ int rope_refine_poses(rope_ctx *ctx, const double *q, const float *frame_depth_d
                       double *words_out);
 size_t rope_refine_workspace(rope_ctx *ctx, int n_frames);
 
+/* ---- The camera polish and the bundle polish, natively (csrc/rope_bundle_polish.hip; prediction/refinement.py,
+ * BundleRefiner(native=True); tests/bundle_polish_ref.py restates the text below with plain loops over Python floats).  What
+ * rope_bundle_normal_equations leaves to its caller: the twists of a camera pose, the pool over the frames, the Levenberg step of
+ * the block-arrow system ('frame' mode) and of the pooled twelve columns ('offset' mode), their formal variances and the loop.
+ * Every float64 operation written below is ONE correctly rounded IEEE operation in the order written; nothing is fused.
+ * Words w (a frame's, or the pooled ones) are rope_bundle_normal_equations': A[i][j] = A[j][i] = w[16 + 12 i - i (i - 1) / 2 + (j - i)]
+ * for i <= j over the twelve slots, g[c] = w[4 + c]; slots 0 .. 5 the joints, 6 .. 11 the camera.
+ * THE ELIMINATION is rope_levenberg_step's rule for p <= 12 rows and SEVERAL right-hand sides b_0 .. b_(m-1): the pivot search and
+ * the row swap as written there, the swap taking every right-hand side along; for i > k: f = M[i][k] / M[k][k], for c > k ascending
+ * M[i][c] = M[i][c] - f M[k][c], then for every right-hand side in ascending order b[i] = b[i] - f b[k].  The back substitution
+ * runs per right-hand side, in ascending order, as written there.  A system is NOT FINITE when any x of any right-hand side is not.
+ * A sum "from the first product" over an ascending index is s = t_0; s = s + t_1; ...; an empty one is 0.0.
+ * kc: the camera slots 6 + k with bit k of camera_mask set and a positive POOLED diagonal, ascending; nk = |kc|.
+ * idx_f: the joints j with bit j of joint_mask set and a positive diagonal in frame f's OWN words, ascending; p_f = |idx_f|.
+ *
+ * rope_camera_twists (host only): pose6 [x, y, z, a3, a4, a5] -> Rwc9 and tc3 as rope_refine_poses derives them (R =
+ *   rope_camera_matrix's camera-to-world rotation, libm's sine and cosine; Rwc row 0 = column 0 of R, rows 1 and 2 the NEGATED columns
+ *   1 and 2; tc = (x, y, z)) and twists36, six rows (w, v) as rope_camera_normal_equations takes them (refinement.camera_twists):
+ *   row k < 3: w = 0, v[r] = -Rwc[r][k].  Row 3 + k: v = 0, w[r] = -((Rwc[r][0] a.x + Rwc[r][1] a.y) + Rwc[r][2] a.z) with the axis
+ *   a = (-sy, cy, 0) for a3, (cy cp, sy cp, -sp) for a4, (0, 0, 1) for a5; cy, sy = cos, sin of a5, cp, sp = cos, sin of a3 (libm).
+ *   ROPE_E_ARG for a null pointer or a pose that is not finite; nothing is written then.
+ *
+ * rope_bundle_pool: pooled[k] = ((0.0 + w_0[k]) + w_1[k]) + ... over the frames in order, k < 96; one thread a word.  Bit-equal to
+ *   refinement.pool_bundle.  words_dev n_frames x 96 and pooled_dev 96 doubles, DEVICE, 8-byte aligned.
+ *
+ * rope_bundle_schur_step: refinement.schur_step, then pose + dc and the clip of q + dq to the limits.
+ *   words_dev, pooled_dev   as above (pooled_dev = rope_bundle_pool of words_dev)
+ *   q_dev, pose_dev, lam_dev   n_frames x 6, 6 and 1 doubles, DEVICE, 8-byte aligned: the angles, the camera pose, ONE damping
+ *   joint_mask, camera_mask    0 .. 63 each;   limits   12 HOST doubles as rope_levenberg_step takes them
+ *   work_dev             rope_bundle_schur_workspace(n_frames) bytes, DEVICE, 8-byte aligned (88 doubles a frame and 48)
+ *   trial_q_dev, trial_pose_dev   n_frames x 6 and 6 doubles out, DEVICE, 8-byte aligned; written completely
+ *   1. Per frame with p_f > 0: D = A[idx][idx] with the diagonal a + lam a; right-hand sides the nk columns B[r][a] = A[idx[r]][kc[a]]
+ *      and then g[idx]; X = D^-1 [B | g] by the elimination.  The frame is OUT when p_f = 0, D is singular or X is not finite.
+ *   2. Per frame that is in: P[a][b] = sum over r ascending from the first product of B[r][a] X[r][b], b over the nk columns and g.
+ *   3. S[a][b] = C[a][b] (C = pooled A[kc][kc]), the diagonal c + lam c; rhs[a] = pooled g[kc[a]].  Then for the frames that are in,
+ *      in ascending order, S[a][b] = S[a][b] - P_f[a][b] and rhs[a] = rhs[a] - P_f[a][g].
+ *   4. d solves S d = -rhs by the elimination; d = 0 when nk = 0, S is singular or d is not finite.  dc[kc[a] - 6] = d[a], else 0.
+ *   5. Frame in: dq[idx[r]] = -(X[r][g] + s), s the sum over a ascending from the first product of X[r][a] d[a]; every other dq is 0.
+ *   6. trial_pose[k] = pose[k] + dc[k];  trial_q = q + dq clipped as rope_levenberg_step clips.
+ *   The per-frame work is one kernel (a frame a thread, the 6 x 13 system in LDS), steps 3 and 4 one workgroup (a thread an entry of
+ *   S and rhs over the frames in order, then one thread solves), steps 5 and 6 per frame again.
+ *
+ * rope_bundle_schur_variance: the SQUARE of refinement.schur_sigma (the caller takes the root).
+ *   var_q_dev, var_pose_dev   n_frames x 6 and 6 doubles out, DEVICE, 8-byte aligned; written completely; work_dev as above
+ *   NaN for an unknown whose mask bit is clear; every other unknown is +inf unless given below.  p = nk + sum of p_f.
+ *   Nothing more when p = 0 or pooled[2] < p + 1.  s2 = pooled[3] / (pooled[2] - p).
+ *   Per frame with p_f > 0: X = A[idx][idx]^-1 [B | I] (no damping); OUT when singular or not finite.  Y = the B part, Ainv the I part;
+ *   P[a][b] as above over the nk columns.  S0 = C less the P of the frames that are in, in ascending order.  cov = S0^-1 [I] by the
+ *   elimination; when nk > 0 and S0 is singular or cov not finite, nothing more.  var_pose[kc[a] - 6] = s2 cov[a][a] when ALL of them
+ *   are finite and not negative.  Frame in: t_a = sum over b from the first product of cov[a][b] Y[r][b]; u = sum over a from the first
+ *   product of Y[r][a] t_a; var_q[idx[r]] = s2 (Ainv[r][r] + u) when all of the frame's are finite and not negative.
+ *
+ * rope_bundle_columns_step: refinement.bundle_columns_step over slot_mask (0 .. 4095, bit c = slot c) and what follows it.
+ *   idx = the slots of slot_mask with a positive pooled diagonal; M = A[idx][idx], the diagonal a + lam a; b = -g[idx]; x by the
+ *   elimination; d[idx[k]] = x[k], d = 0 altogether when idx is empty, M singular or x not finite.
+ *   trial_pose[k] = pose[k] + d[6 + k];  trial_off[j] = off[j] + d[j];  trial_q[f][j] = q0[f][j] + trial_off[j], clipped.
+ *   pose_dev, off_dev 6 doubles, q0_dev n_frames x 6, outputs likewise; the 12 x 13 system lies in LDS and one thread solves it.
+ * rope_bundle_columns_variance: the SQUARE of refinement.bundle_columns_sigma -> 12 doubles: NaN outside slot_mask; +inf when idx is
+ *   empty, pooled[2] < p + 1, A[idx][idx] is singular, A^-1 (right-hand sides I) not finite, or any variance not finite or negative;
+ *   else var[idx[k]] = (pooled[3] / (pooled[2] - p)) x_k[k], and a slot of slot_mask outside idx keeps +inf.
+ * All of the above: ROPE_E_ARG, with nothing enqueued and the outputs untouched, for n_frames < 1, a null or misaligned pointer, a
+ * mask out of range, limits that are null, not finite or have lo > hi.  ROPE_E_HIP when the runtime refuses a launch.  Nothing is
+ * synchronised.  No kernel of the file uses scratch (tests/test_bundle_polish_resources.py).
+ *
+ * rope_refine_bundle: BundleRefiner.refine's depth loop.  Robot and camera are set on the context; n = min(n_links, 6) links.
+ *   mode                 ROPE_BUNDLE_FRAME or ROPE_BUNDLE_OFFSET
+ *   camera_pose6, q      6 and n_frames x 6 HOST doubles: the start (finite, |q| <= 1e4)
+ *   frame_depth_dev      n_frames planes H x W float32 metres, H x W the camera's, DEVICE, 4-byte aligned
+ *   fx, fy, cx, cy, znear, zfar   rope_camera_matrix's, as doubles; znear and zfar those of rope_set_camera.  The equations take
+ *                        fx .. cy rounded to float32
+ *   joint_mask, camera_mask   0 .. 63, not both 0.  joint_mask 0 is the camera polish alone
+ *   limits, clip_m, iterations, damping   rope_refine_poses';  ONE damping for the whole system
+ *   work_dev             rope_refine_bundle_workspace(ctx, n_frames) bytes, DEVICE, 8-byte aligned
+ *   pose_out, offsets_out, var_pose_out   6 HOST doubles each;  angles_out, frame_cost_out  n_frames x 6 and n_frames;
+ *   var_joints_out       FRAME: n_frames x 6 (the angles'); OFFSET: 6 (the offsets');  costs_out  3: cost before, after, pooled inliers;
+ *   steps_out            1 int32;  words_out  n_frames x 96 HOST doubles, the final systems, or NULL
+ * equations(pose, a): rope_camera_twists(pose); a render of the rows a, every row under P V = rope_camera_matrix(pose, fx .. zfar)
+ *   (rope_render_batch_device; the context's own camera is not moved); rope_joint_axes at a when joint_mask != 0 (n_joints 6, else 0);
+ *   the twists for every frame when camera_mask != 0 (n_cols 6, else 0); rope_bundle_normal_equations; rope_bundle_pool.
+ *   cost(pooled) = pooled[0] > 0 ? pooled[1] / pooled[0] : +inf.
+ *   words, pooled = equations(pose, q); cost = cost_before; lam = damping; off = 0; q0 = q.  `iterations` times: the trial by
+ *   rope_bundle_schur_step (FRAME; off stays) or rope_bundle_columns_step with slot_mask = joint_mask | camera_mask << 6 (OFFSET);
+ *   the equations there; a kernel keeps the trial when its pooled cost is strictly smaller (words, pooled, q, off, pose, cost,
+ *   steps += 1), else lam = lam 10.  Then the variances, frame_cost[f] = cost(words_f), offsets = off (NaN in FRAME).
+ * Between rounds only the trial pose and the trial angles come down (the raster path takes HOST rows); one copy at the end brings
+ * the results.  The call runs on the context's stream, is complete when it returns, uses the per-candidate buffers as
+ * rope_render_batch_device does, and gives the same bytes for the same inputs.  The silhouette term is not part of it.
+ * ROPE_E_ARG, with nothing enqueued and no output written, for whatever its parts refuse, robot or camera not set, a mode that is
+ * neither, both masks 0, iterations < 0, a damping that is negative or not finite, n_frames above 65535.
+ * rope_refine_bundle_workspace (host only): the bytes of work_dev; 0 without a camera or for a batch the call refuses. */
+#define ROPE_BUNDLE_FRAME 0
+#define ROPE_BUNDLE_OFFSET 1
+int rope_camera_twists(const double *pose6, double *Rwc9, double *tc3, double *twists36);
+int rope_bundle_pool(const double *words_dev, int n_frames, double *pooled_dev, void *stream);
+size_t rope_bundle_schur_workspace(int n_frames);
+int rope_bundle_schur_step(const double *words_dev, const double *pooled_dev, const double *q_dev, const double *pose_dev, const double *lam_dev,
+                           int n_frames, int joint_mask, int camera_mask, const double *limits, void *work_dev, double *trial_q_dev,
+                           double *trial_pose_dev, void *stream);
+int rope_bundle_schur_variance(const double *words_dev, const double *pooled_dev, int n_frames, int joint_mask, int camera_mask, void *work_dev,
+                               double *var_q_dev, double *var_pose_dev, void *stream);
+int rope_bundle_columns_step(const double *pooled_dev, const double *lam_dev, int slot_mask, const double *pose_dev, const double *off_dev,
+                             const double *q0_dev, int n_frames, const double *limits, double *trial_pose_dev, double *trial_off_dev,
+                             double *trial_q_dev, void *stream);
+int rope_bundle_columns_variance(const double *pooled_dev, int slot_mask, double *var_dev, void *stream);
+int rope_refine_bundle(rope_ctx *ctx, int mode, const double *camera_pose6, const double *q, const float *frame_depth_dev, int n_frames, double fx,
+                       double fy, double cx, double cy, double znear, double zfar, int joint_mask, int camera_mask, const double *limits,
+                       float clip_m, int iterations, double damping, void *work_dev, double *pose_out, double *angles_out, double *offsets_out,
+                       double *var_pose_out, double *var_joints_out, double *costs_out, int32_t *steps_out, double *frame_cost_out,
+                       double *words_out);
+size_t rope_refine_bundle_workspace(rope_ctx *ctx, int n_frames);
+
 /* Phase-skipping switches for kernel ablations (rope_debug_skip) exist only in the profiling build of the library
  * (librope_hip_profile.so, `python tools/build_variants.py profile`, -DROPE_PROFILE); this library does not export them. */
 

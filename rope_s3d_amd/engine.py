@@ -40,7 +40,9 @@ ABI_SYMBOLS = (
     'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace', 'rope_camera_normal_equations',
     'rope_bundle_normal_equations', 'rope_bundle_normal_workspace',
     'rope_mask_distance', 'rope_silhouette_normal_equations', 'rope_silhouette_normal_workspace',
-    'rope_joint_axes', 'rope_levenberg_step', 'rope_formal_variance', 'rope_refine_poses', 'rope_refine_workspace')
+    'rope_joint_axes', 'rope_levenberg_step', 'rope_formal_variance', 'rope_refine_poses', 'rope_refine_workspace',
+    'rope_camera_twists', 'rope_bundle_pool', 'rope_bundle_schur_workspace', 'rope_bundle_schur_step', 'rope_bundle_schur_variance',
+    'rope_bundle_columns_step', 'rope_bundle_columns_variance', 'rope_refine_bundle', 'rope_refine_bundle_workspace')
 
 TARGET_TILE_W, TARGET_TILE_H = 64, 32      # ROPE_TARGET_TILE_W / _H (csrc/rope_kernels.h): the output tile of rope_stage_targets_segmented's kernel
 
@@ -186,6 +188,18 @@ def load_library(path: str = None):
                                       vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rope_refine_workspace.argtypes = [vp, i32]
     lib.rope_refine_workspace.restype = C.c_size_t
+    lib.rope_camera_twists.argtypes = [vp, vp, vp, vp]
+    lib.rope_bundle_pool.argtypes = [vp, i32, vp, vp]
+    lib.rope_bundle_schur_workspace.argtypes = [i32]
+    lib.rope_bundle_schur_workspace.restype = C.c_size_t
+    lib.rope_bundle_schur_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.rope_bundle_schur_variance.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    lib.rope_bundle_columns_step.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.rope_bundle_columns_variance.argtypes = [vp, i32, vp, vp]
+    lib.rope_refine_bundle.argtypes = [vp, i32, vp, vp, vp, i32, dbl, dbl, dbl, dbl, dbl, dbl, i32, i32, vp, C.c_float, i32, dbl, vp,
+                                       vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rope_refine_bundle_workspace.argtypes = [vp, i32]
+    lib.rope_refine_bundle_workspace.restype = C.c_size_t
     lib.rope_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.rope_eval_views.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.rope_set_target_tsweep.argtypes = [vp, vp]
@@ -268,6 +282,16 @@ def trace_contours(mask: np.ndarray, bit: int, box=None, min_points: int = 0) ->
 def build_id() -> str:
     """rope_build_id of the loaded library: the hash of the sources it was built from."""
     return load_library().rope_build_id().decode()
+
+
+def camera_twists(pose6):
+    """rope_camera_twists (host only, no GPU): [x, y, z, a3, a4, a5] -> (Rwc (3, 3), tc (3,), twists (6, 6)): the kernels' camera
+    axes X_c = Rwc (X_w - tc) as rope_refine_poses derives them, and refinement.camera_twists with a written operation order."""
+    pose = np.ascontiguousarray(pose6, np.float64).reshape(6)
+    Rwc, tc, tw = np.empty((3, 3)), np.empty(3), np.empty((6, 6))
+    if load_library().rope_camera_twists(_p(pose), _p(Rwc), _p(tc), _p(tw)) != 0:
+        raise ValueError(f"camera pose: six finite numbers, got {pose}")
+    return Rwc, tc, tw
 
 
 def pinned_empty(shape, dtype) -> np.ndarray:
@@ -952,6 +976,142 @@ class Engine:
             raise ValueError(f"rope_refine_poses refused its arguments: {self._lib.rope_last_error(self._ctx).decode()}")
         self._check(rc, 'rope_refine_poses')
         return out
+
+    # -- the native camera and bundle polish (csrc/rope_bundle_polish.hip) ----------------------------
+    def _bundle_call(self, name: str, N: int, outs, call):
+        """The launch the bundle exports share: outputs allocated on the device, the call on torch's current stream."""
+        import torch
+        dev = torch.device('cuda', self.device)
+        with torch.cuda.device(dev):
+            tensors = [torch.empty(shape, dtype=torch.float64, device=dev) for shape in outs]
+            if N > 0:
+                work = torch.empty(max(1, self._lib.rope_bundle_schur_workspace(int(N)) // 8), dtype=torch.float64, device=dev)
+                rc = call(C.c_void_p(work.data_ptr()), [C.c_void_p(t.data_ptr()) for t in tensors],
+                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                if rc:
+                    raise EngineError(f"{name} failed ({rc})")
+        return tensors
+
+    def bundle_pool(self, words):
+        """rope_bundle_pool: (N, 96) words -> (96,) float64 tensor on the device, the frames added in frame order, bit-equal to
+        refinement.pool_bundle.  Runs on torch's current stream; nothing is waited for."""
+        import torch
+        w = self._polish_tensor('words', words, BNEQ_WORDS)
+        if w.shape[0] == 0:
+            return torch.zeros(BNEQ_WORDS, dtype=torch.float64, device=w.device)
+        return self._bundle_call('rope_bundle_pool', w.shape[0], [(BNEQ_WORDS,)],
+                                 lambda work, o, s: self._lib.rope_bundle_pool(C.c_void_p(w.data_ptr()), int(w.shape[0]), o[0], s))[0]
+
+    def bundle_schur_step(self, words, pooled, q, pose, lam: float, joint_mask: int, camera_mask: int, limits):
+        """rope_bundle_schur_step: refinement.schur_step on the device, then pose + dc and clip(q + dq) -> (trial_q (N, 6),
+        trial_pose (6,)) float64 tensors on the device (include/rope_s3d.h).  words (N, 96), pooled (96,), q (N, 6), pose (6,): float64
+        numpy arrays or tensors; lam ONE damping; limits (6, 2).  Runs on torch's current stream; nothing is waited for."""
+        import torch
+        w = self._polish_tensor('words', words, BNEQ_WORDS)
+        N = w.shape[0]
+        p_t, q_t, pose_t = self._polish_tensor('pooled', pooled, None, BNEQ_WORDS), self._polish_tensor('q', q, 6, N), self._polish_tensor('pose', pose, None, 6)
+        lam_t = torch.tensor([float(lam)], dtype=torch.float64, device=w.device)
+        jm, cm, limits = self._active_mask(joint_mask), self._active_mask(camera_mask), self._limits(limits)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        out = self._bundle_call('rope_bundle_schur_step', N, [(N, 6), (6,)], lambda work, o, s: self._lib.rope_bundle_schur_step(
+            vp(w), vp(p_t), vp(q_t), vp(pose_t), vp(lam_t), int(N), jm, cm, _p(limits), work, o[0], o[1], s))
+        return out[0], out[1]
+
+    def bundle_schur_variance(self, words, pooled, joint_mask: int, camera_mask: int):
+        """rope_bundle_schur_variance: the SQUARE of refinement.schur_sigma -> (var_q (N, 6), var_pose (6,)) float64 tensors on the
+        device: nan for what is not refined, inf where the views do not pin an unknown down.  Nothing is waited for."""
+        w = self._polish_tensor('words', words, BNEQ_WORDS)
+        N = w.shape[0]
+        p_t = self._polish_tensor('pooled', pooled, None, BNEQ_WORDS)
+        jm, cm = self._active_mask(joint_mask), self._active_mask(camera_mask)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        out = self._bundle_call('rope_bundle_schur_variance', N, [(N, 6), (6,)], lambda work, o, s: self._lib.rope_bundle_schur_variance(
+            vp(w), vp(p_t), int(N), jm, cm, work, o[0], o[1], s))
+        return out[0], out[1]
+
+    @staticmethod
+    def _slot_mask(slot_mask) -> int:
+        if isinstance(slot_mask, bool) or int(slot_mask) != slot_mask or not 0 <= int(slot_mask) <= 4095:
+            raise ValueError(f"slot_mask: bit c set = slot c is refined, 0 .. 4095, got {slot_mask!r}")
+        return int(slot_mask)
+
+    def bundle_columns_step(self, pooled, lam: float, slot_mask: int, pose, off, q0, limits):
+        """rope_bundle_columns_step: refinement.bundle_columns_step on the device and what follows it -> (trial_pose (6,),
+        trial_off (6,), trial_q (N, 6)) float64 tensors on the device: pose + d[6:], off + d[:6], clip(q0 + trial_off)."""
+        import torch
+        p_t = self._polish_tensor('pooled', pooled, None, BNEQ_WORDS)
+        q_t = self._polish_tensor('q0', q0, 6)
+        N = q_t.shape[0]
+        pose_t, off_t = self._polish_tensor('pose', pose, None, 6), self._polish_tensor('off', off, None, 6)
+        lam_t = torch.tensor([float(lam)], dtype=torch.float64, device=p_t.device)
+        sm, limits = self._slot_mask(slot_mask), self._limits(limits)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        out = self._bundle_call('rope_bundle_columns_step', N, [(6,), (6,), (N, 6)], lambda work, o, s: self._lib.rope_bundle_columns_step(
+            vp(p_t), vp(lam_t), sm, vp(pose_t), vp(off_t), vp(q_t), int(N), _p(limits), o[0], o[1], o[2], s))
+        return out[0], out[1], out[2]
+
+    def bundle_columns_variance(self, pooled, slot_mask: int):
+        """rope_bundle_columns_variance: the SQUARE of refinement.bundle_columns_sigma -> (12,) float64 tensor on the device."""
+        p_t = self._polish_tensor('pooled', pooled, None, BNEQ_WORDS)
+        sm = self._slot_mask(slot_mask)
+        return self._bundle_call('rope_bundle_columns_variance', 1, [(12,)], lambda work, o, s: self._lib.rope_bundle_columns_variance(
+            C.c_void_p(p_t.data_ptr()), sm, o[0], s))[0]
+
+    def refine_bundle_workspace(self, n_frames: int) -> int:
+        """rope_refine_bundle_workspace: the bytes of device scratch refine_bundle needs for n_frames frames; 0 for a batch one
+        call does not take."""
+        return int(self._lib.rope_refine_bundle_workspace(self._ctx, int(n_frames)))
+
+    def refine_bundle(self, mode: str, camera_pose, q, frame_depth, intr, znear: float, zfar: float, joint_mask: int, camera_mask: int,
+                      limits, clip: float, iterations: int, damping: float, want_words: bool = False):
+        """rope_refine_bundle: BundleRefiner.refine's depth loop inside the library — render, joint axes, twists, bundle normal
+        equations, pool, the Schur ('frame') or twelve-column ('offset') Levenberg step kept only when the pooled cost falls, the
+        formal variances — with everything but the render's rows on the device (include/rope_s3d.h).
+        camera_pose (6,) and q (N, 6) host; frame_depth (N, H, W) float32 tensor on this engine's device, H x W the camera's; intr
+        (fx, fy, cx, cy); znear, zfar those of set_camera.
+        -> dict(pose (6,), angles (N, 6), offsets (6,) — nan in 'frame' mode —, var_pose (6,), var_joints ((N, 6) 'frame', (6,)
+        'offset'), cost_before, cost_after, inliers (float), steps (int), frame_cost (N,) [, words (N, 96)]).  Complete on return."""
+        import torch
+        if mode not in ('frame', 'offset'):
+            raise ValueError(f"mode: 'frame' or 'offset', got {mode!r}")
+        q = np.ascontiguousarray(q, np.float64).reshape(-1, 6)
+        N = len(q)
+        t = frame_depth
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
+            raise ValueError("frame_depth: a contiguous (N, H, W) torch.float32 tensor")
+        if t.device.type != 'cuda' or t.device.index != self.device:
+            raise ValueError(f"frame_depth must be on cuda:{self.device}, got {t.device}")
+        if N < 1 or tuple(t.shape) != (N, self.H, self.W):
+            raise ValueError(f"frame_depth: ({N}, {self.H}, {self.W}) as the poses and the camera, N >= 1, got {tuple(t.shape)}")
+        jm, cm, limits = self._active_mask(joint_mask), self._active_mask(camera_mask), self._limits(limits)
+        if jm == 0 and cm == 0:
+            raise ValueError("joint_mask and camera_mask: not both 0")
+        pose = np.ascontiguousarray(camera_pose, np.float64).reshape(6)
+        if int(iterations) != iterations or iterations < 0 or not (np.isfinite(damping) and damping >= 0):
+            raise ValueError("iterations and damping must not be negative")
+        frame_mode = mode == 'frame'
+        o = dict(pose=np.empty(6), angles=np.empty((N, 6)), offsets=np.empty(6), var_pose=np.empty(6),
+                 var_joints=np.empty((N, 6) if frame_mode else 6), costs=np.empty(3), steps=np.zeros(1, np.int32), frame_cost=np.empty(N))
+        if want_words:
+            o['words'] = np.empty((N, BNEQ_WORDS))
+        nbytes = self.refine_bundle_workspace(N)
+        if nbytes == 0:
+            raise ValueError(f"rope_refine_bundle takes no batch of {N} frames of {self.H} x {self.W} in one call")
+        fx, fy, cx, cy = (float(v) for v in intr)
+        dev = t.device
+        with torch.cuda.device(dev):
+            work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()            # the frames are ready, and `work` is no longer anyone else's
+            rc = self._lib.rope_refine_bundle(self._ctx, 0 if frame_mode else 1, _p(pose), _p(q), C.c_void_p(t.data_ptr()), int(N), fx, fy, cx, cy,
+                                              float(znear), float(zfar), jm, cm, _p(limits), float(clip), int(iterations), float(damping),
+                                              C.c_void_p(work.data_ptr()), _p(o['pose']), _p(o['angles']), _p(o['offsets']), _p(o['var_pose']),
+                                              _p(o['var_joints']), _p(o['costs']), _p(o['steps']), _p(o['frame_cost']), _p(o.get('words')))
+        if rc == -1:
+            raise ValueError(f"rope_refine_bundle refused its arguments: {self._lib.rope_last_error(self._ctx).decode()}")
+        self._check(rc, 'rope_refine_bundle')
+        costs = o.pop('costs')
+        o.update(cost_before=float(costs[0]), cost_after=float(costs[1]), inliers=float(costs[2]), steps=int(o['steps'][0]))
+        return o
 
     def debug_targets(self, want_tsweep: bool = False):
         """rope_debug_targets: the resident set back on the host -> (tq (N,H,W) uint64, t32 (N,H,W) float32, tsweep planes or None,

@@ -124,8 +124,8 @@ class _CameraStageMachine:
 
     def __init__(self, base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine=False):
         self.base_pose = np.array(base_pose, dtype=float)
-        if isinstance(refine, str) and refine not in ('bundle', 'bundle+silhouette'):
-            raise ValueError(f"refine: True, False, 'bundle' or 'bundle+silhouette', got {refine!r}")
+        if isinstance(refine, str) and refine not in ('bundle', 'bundle+silhouette', 'bundle+native'):
+            raise ValueError(f"refine: True, False, 'bundle', 'bundle+silhouette' or 'bundle+native', got {refine!r}")
         self.refine, self.last_refinement, self._refiner = refine if isinstance(refine, str) else bool(refine), None, None
         self._robot_masks = None
         self.ds_factor, self.preview = ds_factor, preview
@@ -330,7 +330,8 @@ class _CameraStageMachine:
         refine='bundle': refinement.BundleRefiner in 'frame' mode instead — S, L and U of every frame are unknowns beside the camera,
         so an encoder error is not absorbed into the pose; the caller's recorded angles are not changed.
         refine='bundle+silhouette': the same with the outline term at weight 1 (BundleRefiner(silhouette=1)) against the robot masks
-        of this run (`_robot_masks`: the run's own, one per frame)."""
+        of this run (`_robot_masks`: the run's own, one per frame).
+        refine='bundle+native': 'bundle' through rope_refine_bundle (BundleRefiner(native=True)): the solves on the device."""
         self.last_refinement = None
         if not self.refine:
             return pose
@@ -339,7 +340,8 @@ class _CameraStageMachine:
             if self.refine == 'bundle+silhouette':
                 self._refiner = BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame', silhouette=1.0)
             else:
-                self._refiner = (BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame') if self.refine == 'bundle'
+                self._refiner = (BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame',
+                                               native=self.refine == 'bundle+native') if self.refine in ('bundle', 'bundle+native')
                                  else CameraPoseRefiner(self.renderer, self.renderer.intrinsics))
         if self.refine == 'bundle+silhouette':
             self.last_refinement = self._refiner.refine(pose, self.robot_poses, np.asarray(self._tgt_depths, np.float32), self._robot_masks)
@@ -400,7 +402,8 @@ class ModellessCameraPredictor(_CameraStageMachine):
                  base_intrinsics='1280_720_color', *, device: int = 0, refine=False):
         """`refine`: True polishes the pose the stages end on with refinement.CameraPoseRefiner and keeps its CameraRefineResult (the
         pooled formal sigma of the six parameters, every frame's own cost) in `last_refinement`; 'bundle' polishes it together with
-        every frame's S, L and U (refinement.BundleRefiner, 'frame' mode) and keeps the BundleRefineResult; 'bundle+silhouette' adds
+        every frame's S, L and U (refinement.BundleRefiner, 'frame' mode) and keeps the BundleRefineResult ('bundle+native': the same
+        through rope_refine_bundle, the solves on the device); 'bundle+silhouette' adds
         the outline term.  This predictor has no segmentation: its robot mask is where the down-sampled depth frame holds a
         measurement, which is the robot only for frames whose background carries no depth (synthetic sets, background removed)."""
         super().__init__(base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine)

@@ -527,14 +527,23 @@ class BundleRefiner:
                         c_d + silhouette c_s is strictly smaller, and the system solved is the sum of the two terms' words, each
                         divided by its pixel count and truncation at the iterate held.  One-directional: the render's outline is
                         measured against the mask
-    radius              1 .. 16 pixels: the truncation of the mask's distance field"""
+    radius              1 .. 16 pixels: the truncation of the mask's distance field
+    native              False (the default): the loop below, on the host, numpy's LAPACK for the solves.  True: refine is one
+                        Engine.refine_bundle call per batch (rope_refine_bundle, csrc/rope_bundle_polish.hip) — the same loop with the
+                        joint axes, the pool, the Schur or twelve-column solves, accept / reject, damping and the variances on the
+                        device.  Same fields, same meanings; the numbers differ by the rounding of another elimination order and of
+                        the device's sine in the joint axes.  Depth term only: with silhouette > 0 it raises ValueError"""
 
     def __init__(self, renderer_or_engine, intrinsics, do_angles: str = 'SLU', do_params=(True,) * 6, joints: str = 'frame',
-                 clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3, silhouette: float = 0.0, radius: int = 8):
+                 clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3, silhouette: float = 0.0, radius: int = 8,
+                 native: bool = False):
         if not (np.isfinite(clip) and clip > 0):
             raise ValueError(f"clip must be finite and positive, got {clip}")
         if not (np.isfinite(silhouette) and silhouette >= 0):
             raise ValueError(f"silhouette: a finite weight, 0 or more, got {silhouette}")
+        if native and silhouette > 0:
+            raise ValueError("native=True polishes on the depth term alone: silhouette must be 0 (rope_refine_bundle has no outline term)")
+        self.native = bool(native)
         if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
             raise ValueError(f"radius: a whole number of pixels in 1 .. {SIL_MAX_RADIUS}, got {radius}")
         self.silhouette, self.radius = float(silhouette), int(radius)
@@ -603,6 +612,8 @@ class BundleRefiner:
         depth_t = depth.to(device=device, dtype=torch.float32).contiguous()
         if depth_t.dim() != 3 or depth_t.shape[0] != N:
             raise ValueError(f"depth: ({N}, H, W), got {tuple(depth_t.shape)}")
+        if self.native:
+            return self._refine_native(pose, q0, depth_t)
         q, off = q0.copy(), np.zeros(6)
         lam = self.damping
         words = self.equations(pose, q, depth_t)
@@ -632,6 +643,20 @@ class BundleRefiner:
         s = bundle_columns_sigma(pooled, slots)
         return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), s[6:], None, s[:6], cost_before, cost, steps,
                                   float(pooled[2]), frame_cost)
+
+    def _refine_native(self, pose: np.ndarray, q0: np.ndarray, depth_t) -> BundleRefineResult:
+        """refine through rope_refine_bundle: ONE call, because one system spans all frames — a batch whose scratch one call does
+        not take is refused (Engine.refine_bundle_workspace says what a batch needs)."""
+        from ..constants import ZFAR, ZNEAR
+        intr = self.intrinsics
+        jm, cm = sum(1 << j for j in self.active_j), sum(1 << k for k in self.active_c)
+        r = self.engine.refine_bundle(self.mode, pose, q0, depth_t, (intr.fx, intr.fy, intr.cx, intr.cy), ZNEAR, ZFAR, jm, cm, self.limits,
+                                      self.clip, self.iterations, self.damping)
+        if self.mode == 'frame':
+            return BundleRefineResult(r['pose'], r['angles'], np.full(6, np.nan), np.sqrt(r['var_pose']), np.sqrt(r['var_joints']), None,
+                                      r['cost_before'], r['cost_after'], r['steps'], r['inliers'], r['frame_cost'])
+        return BundleRefineResult(r['pose'], r['angles'], np.where(np.isin(np.arange(6), self.active_j), r['offsets'], 0.0), np.sqrt(r['var_pose']),
+                                  None, np.sqrt(r['var_joints']), r['cost_before'], r['cost_after'], r['steps'], r['inliers'], r['frame_cost'])
 
     # ------------------------------------------------------------------------------------------ depth and outline together
     def equations_both(self, pose, angles: np.ndarray, depth_t, sd2_t):
