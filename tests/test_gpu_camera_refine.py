@@ -113,6 +113,29 @@ def test_kernel_agrees_with_the_reference_on_the_hand_built_planes_and_tiny_fram
     assert np.concatenate(parts).tobytes() == got.tobytes()
 
 
+@pytest.mark.parametrize('Hh,Ww', [(23, 89), (32, 64), (3, 683)])
+def test_kernel_at_the_chunk_edges_and_cut_into_calls(Hh, Ww):
+    """2047, 2048 and 2049 pixels: the last pass one thread short, a full workgroup, a second workgroup for one pixel; frames
+    built as test_gpu_bundle's, links 0 .. 2 in stripes.  Three frames cut as [0:1], [1:3]: the gather kernel's last workgroup
+    holds one frame of its two."""
+    rng = np.random.default_rng(Hh)
+    n = np.array([0.2, -0.3, 1.0]) / np.linalg.norm([0.2, -0.3, 1.0])
+    intr = (150.0, 150.0, Ww / 2 - 0.25, Hh / 2)
+    R3 = np.stack([refine_ref.tilted_depth(Hh, Ww, intr, n, c) for c in (1.8, 2.0, 2.3)]).astype(np.float32)
+    I3 = (np.arange(Ww)[None, None, :] * 3 // Ww + np.zeros((3, Hh, 1))).astype(np.uint8)
+    I3[1, Hh - 1:] = 255
+    T3 = (R3 + rng.uniform(-0.04, 0.04, R3.shape)).astype(np.float32)
+    T3[0, Hh - 1, Ww - 5:] = 0.0
+    for n_cols in (3, 6):
+        tw = _twists(rng, 3, n_cols)
+        rc, got = _call(R3, I3, T3, tw, 3, intr)
+        assert rc == 0
+        want = _hold(got, R3, I3, T3, tw, 3, intr)
+        assert (want[:, 2] > 1000).all()
+    parts = [_call(R3[a:b], I3[a:b], T3[a:b], tw[a:b], 3, intr)[1] for a, b in ((0, 1), (1, 3))]
+    assert np.concatenate(parts).tobytes() == got.tobytes()
+
+
 def _robot_scene():
     """The engine at 160 x 120 with the robot and the three poses of the golden set."""
     gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'camera_160x120.npz'))

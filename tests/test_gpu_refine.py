@@ -4,8 +4,9 @@ what it refuses, PoseRefiner end to end against refine_ref's loop on the engine'
 
 The bound.  A sum of n float64 terms added in any order differs from the exact sum by at most (n - 1) eps sum|terms| to first
 order, eps = 2^-52 being twice the unit roundoff; two orders differ by at most twice that, and the terms themselves are the same
-bits on both sides (one IEEE operation per written operation).  4 n eps sum|terms| covers it with the second-order terms; n is
-the pixel count of the frame.  No measured number enters."""
+bits on both sides (one IEEE operation per written operation; tests/test_gpu_neq_terms.py holds the kernels to that on frames
+of one and two inliers, exactly).  4 n eps sum|terms| covers it with the second-order terms; n is the pixel count of the frame.
+No measured number enters."""
 import ctypes as C
 
 import numpy as np
@@ -89,6 +90,58 @@ def test_kernel_agrees_with_the_reference_on_the_hand_built_planes_and_tiny_fram
         assert rc == 0
         want = _hold(got, R1, I1, T1, joints[:2], HAND_LINKS, HAND_INTR)
         assert want[0, 0] == H * W and want[1, 0] == H * W - 1 and not want[:, 2].any() and want[0, 1] > 0
+
+
+def _axes(rng, N, n_joints):
+    """Generic joint axes and points about the planes' depth (test_gpu_bundle's `_columns`)."""
+    return np.concatenate([rng.uniform(-1, 1, (N, n_joints, 3)), rng.uniform(-.5, .5, (N, n_joints, 2)), rng.uniform(1.5, 2.5, (N, n_joints, 1))], axis=2)
+
+
+@pytest.mark.parametrize('n_links,n_joints', [(HAND_LINKS, 1), (HAND_LINKS, 3), (HAND_LINKS, 4), (2, 6), (3, 6)])
+def test_hand_planes_at_the_other_counts_of_joints_and_links(n_links, n_joints):
+    """`j < n_joints && j < id` and MOVING's `id <= n_joints` have an edge at every count; the other tests run 2 joints on 4 links
+    and 6 on 6.  Here: fewer joints than moving links (1, 3), as many joints as ids below n_links + 1 (4: link 3 moves too), and
+    joints beyond the drawn links (n_links 2 and 3 with 6 joints: the planes' links 2 .. 4 are not rendered)."""
+    R, ids, T, _ = hand_planes()
+    joints = _axes(np.random.default_rng(10 * n_links + n_joints), 3, n_joints)
+    rc, got = _call(R, ids, T, joints, n_links, HAND_INTR)
+    assert rc == 0
+    want = _hold(got, R, ids, T, joints, n_links, HAND_INTR)
+    top = min(n_joints, n_links - 1)                                 # the last link that is drawn and moves
+    assert (want[:2, 2] > 0).all() and (want[:2, 10] > 0).all()
+    live = [4 + j for j in range(min(top, 2))]                       # frame 0 has links 1 and 2
+    assert want[0, live].all() and not got[0, 4 + min(top, 2):10].any() and not got[:, 4 + top:10].any()
+    if n_links == HAND_LINKS and n_joints == 1:
+        more = refine_ref.normal_equations(R, ids, T, n_links, HAND_INTR, _axes(np.random.default_rng(1), 3, 2))[0]
+        assert more[0, 2] > want[0, 2]                               # a second joint moves frame 0's link 2 as well
+
+
+def _chunk_edge_frames(Hh, Ww, rng):
+    """Three frames a pixel below, at or above a workgroup's 2048, built as test_gpu_bundle's: links 0 .. 2 in stripes."""
+    n = np.array([0.2, -0.3, 1.0]) / np.linalg.norm([0.2, -0.3, 1.0])
+    intr = (150.0, 150.0, Ww / 2 - 0.25, Hh / 2)
+    R3 = np.stack([refine_ref.tilted_depth(Hh, Ww, intr, n, c) for c in (1.8, 2.0, 2.3)]).astype(np.float32)
+    I3 = (np.arange(Ww)[None, None, :] * 3 // Ww + np.zeros((3, Hh, 1))).astype(np.uint8)
+    I3[1, Hh - 1:] = 255
+    T3 = (R3 + rng.uniform(-0.04, 0.04, R3.shape)).astype(np.float32)
+    T3[0, Hh - 1, Ww - 5:] = 0.0
+    return R3, I3, T3, intr
+
+
+@pytest.mark.parametrize('Hh,Ww', [(23, 89), (32, 64), (3, 683)])
+def test_kernel_at_the_chunk_edges_and_cut_into_calls(Hh, Ww):
+    """2047, 2048 and 2049 pixels: the last pass one thread short, a full workgroup, a second workgroup for one pixel.  Three
+    frames cut as [0:1], [1:3]: the gather kernel's last workgroup holds one frame of its two."""
+    rng = np.random.default_rng(Hh)
+    R3, I3, T3, intr = _chunk_edge_frames(Hh, Ww, rng)
+    for n_joints in (2, 6):
+        joints = _axes(rng, 3, n_joints)
+        rc, got = _call(R3, I3, T3, joints, 3, intr)
+        assert rc == 0
+        want = _hold(got, R3, I3, T3, joints, 3, intr)
+        assert (want[:, 2] > 500).all()                              # two of three stripes move, about 0.78 of them within the clip
+    parts = [_call(R3[a:b], I3[a:b], T3[a:b], joints[a:b], 3, intr)[1] for a, b in ((0, 1), (1, 3))]
+    assert np.concatenate(parts).tobytes() == got.tobytes()
 
 
 def test_kernel_agrees_with_the_reference_on_renders_of_the_robot():

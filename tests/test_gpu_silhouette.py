@@ -101,6 +101,24 @@ def test_distance_field_on_single_rows_and_columns_and_many_planes():
         e.close()
 
 
+def test_distance_field_walks_the_planes_beyond_the_grids_height():
+    """32 768 + 5 planes of 3 x 5 at radius 2: the grid is 32 768 workgroups high and the workgroups 0 .. 4 walk on to a second
+    plane each.  Seven distinct masks, tiled: plane i is mask i % 7, so no two planes 32 768 apart are the same."""
+    planes = 32768 + 5
+    rng = np.random.default_rng(12)
+    seven = (rng.random((7, 3, 5)) < 0.45).astype(np.uint8)
+    seven[5], seven[6] = 0, 1                                                           # FAR everywhere, both signs
+    want7 = sref.mask_distance(seven, 2)
+    assert len({w.tobytes() for w in want7}) == 7 and 32768 % 7 != 0
+    which = np.arange(planes) % 7
+    rc, got = _distance(seven[which], 2)
+    assert rc == 0
+    for i in (0, 4, 5, 32767, 32768, 32769, planes - 1):
+        assert np.array_equal(got[i], want7[i % 7]), i
+    bad = np.flatnonzero((got != want7[which]).any(axis=(1, 2)))
+    assert len(bad) == 0, bad[:8]
+
+
 def test_distance_field_refuses_bad_arguments_and_writes_nothing():
     m = np.ones((2, 5, 6), np.uint8)
     for case in (dict(n=-1), dict(hw=(0, 6)), dict(hw=(5, 0)), dict(hw=(1 << 16, 1 << 15)), dict(radius=0), dict(radius=17), dict(radius=-3),
