@@ -22,6 +22,7 @@
 // a per-thread array indexed that way would live in scratch.  A frame's system is 6 x 13 doubles for the step (D | B | g) and
 // 6 x 18 for the variances (A | B | I): 39 936 and 55 296 bytes a workgroup of one wave.  The systems one thread solves (the
 // camera's 6 x 7 and 6 x 12, the pooled 12 x 13 and 12 x 24) lie in LDS as well, one word an element.  No kernel uses scratch.
+// THE ELIMINATION of all of them is one function, eliminate<MW, RW, TS> in rope_solve.h, which rope_polish.hip calls too.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -32,6 +33,7 @@
 #include <vector>
 
 #include "rope_ctx.h"
+#include "rope_solve.h"
 
 namespace {
 
@@ -49,7 +51,6 @@ constexpr int REC_X = 0, REC_P = 42, REC_OK = 84;                            // 
 constexpr int REC_Y = 0, REC_AINV = 36, REC_VP = 42, REC_VOK = 78, REC_NP = 79;   // variance: Y (r 6 + a), diag A^-1, P (a 6 + b), ok, p
 constexpr int STATE = 48;                                                    // the reduce kernel's words for the back kernel
 
-struct BundleLimits { double lo[6], hi[6]; };
 struct BundleTwists { double v[36]; };
 
 // word of A[i][j], i <= j, among the 96: the upper triangle over the twelve slots row by row from word 16
@@ -66,55 +67,6 @@ __device__ __forceinline__ int live_slots(const double *__restrict__ w, int mask
     return p;
 }
 __device__ __forceinline__ int slot_of(uint64_t packed, int r) { return (int)((packed >> (4 * r)) & 15); }
-
-// THE ELIMINATION (include/rope_s3d.h) of a p x p system with nr right-hand sides: element (r, c) of M at s_m[r RW + c][t], right-
-// hand side m at column MW + m.  Every row operation goes over all right-hand sides; x replaces them.  false: SINGULAR.
-template <int MW, int RW, int TS>
-__device__ __forceinline__ bool eliminate(double (*s_m)[TS], int t, int p, int nr)
-{
-#define EL(r, c) s_m[(r) * RW + (c)][t]
-    for (int k = 0; k < p; k++) {
-        int piv = k;
-        double best = fabs(EL(k, k));
-        for (int r = k + 1; r < p; r++) {                       // the FIRST row with the largest magnitude
-            const double a = fabs(EL(r, k));
-            if (a > best) { best = a; piv = r; }
-        }
-        const double pv = EL(piv, k);
-        if (pv == 0.0 || !isfinite(pv)) return false;
-        if (piv != k) {
-            for (int c = k; c < p; c++) { const double u = EL(k, c); EL(k, c) = EL(piv, c); EL(piv, c) = u; }
-            for (int m = 0; m < nr; m++) { const double u = EL(k, MW + m); EL(k, MW + m) = EL(piv, MW + m); EL(piv, MW + m) = u; }
-        }
-        for (int i = k + 1; i < p; i++) {
-            const double f = EL(i, k) / pv;
-            for (int c = k + 1; c < p; c++) EL(i, c) = EL(i, c) - f * EL(k, c);
-            for (int m = 0; m < nr; m++) EL(i, MW + m) = EL(i, MW + m) - f * EL(k, MW + m);
-        }
-    }
-    for (int m = 0; m < nr; m++)
-        for (int i = p - 1; i >= 0; i--) {
-            double s = EL(i, MW + m);
-            for (int c = i + 1; c < p; c++) s = s - EL(i, c) * EL(c, MW + m);
-            EL(i, MW + m) = s / EL(i, i);
-        }
-    return true;
-}
-
-template <int MW, int RW, int TS>
-__device__ __forceinline__ bool all_finite(double (*s_m)[TS], int t, int p, int nr)
-{
-    bool ok = true;
-    for (int r = 0; r < p; r++)
-        for (int m = 0; m < nr; m++) ok = ok && isfinite(EL(r, MW + m));
-    return ok;
-}
-
-__device__ __forceinline__ double clip_to(double v, double lo, double hi)
-{
-    v = v < lo ? lo : v;
-    return v > hi ? hi : v;
-}
 
 // ---------------------------------------------------------------------------------------------- the pool
 __global__ void __launch_bounds__(BP_THREADS)
@@ -212,7 +164,7 @@ schur_reduce_kernel(const double *__restrict__ rec, const double *__restrict__ p
 
 __global__ void __launch_bounds__(BP_THREADS)
 schur_back_kernel(const double *__restrict__ words, const double *__restrict__ pooled, const double *__restrict__ rec,
-                  const double *__restrict__ state, const double *__restrict__ q, int n_frames, int joint_mask, int camera_mask, BundleLimits lim,
+                  const double *__restrict__ state, const double *__restrict__ q, int n_frames, int joint_mask, int camera_mask, JointLimits lim,
                   double *__restrict__ trial)
 {
     const int f = blockIdx.x * BP_THREADS + threadIdx.x;
@@ -376,7 +328,7 @@ schur_var_back_kernel(const double *__restrict__ words, const double *__restrict
 // writes the trial pose and offsets
 __global__ void __launch_bounds__(BP_THREADS)
 columns_step_kernel(const double *__restrict__ pooled, const double *__restrict__ lam_dev, int slot_mask, const double *__restrict__ pose,
-                    const double *__restrict__ off, const double *__restrict__ q0, int n_frames, BundleLimits lim,
+                    const double *__restrict__ off, const double *__restrict__ q0, int n_frames, JointLimits lim,
                     double *__restrict__ trial_pose, double *__restrict__ trial_off, double *__restrict__ trial)
 {
     __shared__ double s_s[COL_ELEMS][1];
@@ -450,20 +402,17 @@ columns_variance_kernel(const double *__restrict__ pooled, int slot_mask, double
         var[c] = v;
     }
 }
-#undef EL
 
 // ---------------------------------------------------------------------------------------------- the loop's own kernels
 // head, in doubles: the scalars of rope_refine_bundle's state, brought down with the rest in one copy
 constexpr int HD_POSE = 0, HD_OFF = 6, HD_VPOSE = 12, HD_VOFF = 18, HD_COST0 = 24, HD_COST = 25, HD_INL = 26, HD_STEPS = 27, HD_LAM = 28,
               HD_ACCEPT = 29, HD_WORDS = 32;
 
-__device__ __forceinline__ double pooled_cost(const double *w) { return w[0] > 0.0 ? w[1] / w[0] : (double)INFINITY; }
-
 __global__ void bundle_init_kernel(const double *__restrict__ pooled, BundleTwists pose, double damping, double *__restrict__ head)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     for (int k = 0; k < 6; k++) { head[HD_POSE + k] = pose.v[k]; head[HD_OFF + k] = 0.0; }
-    const double c = pooled_cost(pooled);
+    const double c = mean_cost(pooled);
     head[HD_COST0] = head[HD_COST] = c;
     head[HD_STEPS] = 0.0;
     head[HD_LAM] = damping;
@@ -479,7 +428,7 @@ bundle_verdict_kernel(const double *__restrict__ pooled_t, const double *__restr
     __shared__ int s_take;
     const int t = threadIdx.x;
     if (t == 0) {
-        const double c = pooled_cost(pooled_t);
+        const double c = mean_cost(pooled_t);
         const bool take = c < head[HD_COST];
         s_take = take ? 1 : 0;
         head[HD_ACCEPT] = take ? 1.0 : 0.0;
@@ -518,7 +467,7 @@ bundle_finish_kernel(const double *__restrict__ words, const double *__restrict_
         else
             for (int k = 0; k < 6; k++) head[HD_VOFF + k] = (double)NAN;
     }
-    if (f < n_frames) frame_cost[f] = pooled_cost(words + (size_t)f * BW);
+    if (f < n_frames) frame_cost[f] = mean_cost(words + (size_t)f * BW);
 }
 
 __global__ void __launch_bounds__(BP_THREADS)
@@ -531,21 +480,6 @@ tile_twists_kernel(BundleTwists tw, int n_frames, double *__restrict__ out)
 }
 
 inline unsigned frame_grid(int n_frames) { return (unsigned)((n_frames + BP_THREADS - 1) / BP_THREADS); }
-inline bool misaligned8(const void *p) { return ((uintptr_t)p & 7) != 0; }
-inline bool bad6(int mask) { return mask < 0 || mask > 63; }
-bool bad_limits(const double *limits)
-{
-    if (!limits) return true;
-    for (int j = 0; j < 6; j++)
-        if (!std::isfinite(limits[2 * j]) || !std::isfinite(limits[2 * j + 1]) || limits[2 * j] > limits[2 * j + 1]) return true;
-    return false;
-}
-BundleLimits limits_of(const double *limits)
-{
-    BundleLimits lim;
-    for (int j = 0; j < 6; j++) { lim.lo[j] = limits[2 * j]; lim.hi[j] = limits[2 * j + 1]; }
-    return lim;
-}
 inline int launched() { return hipGetLastError() == hipSuccess ? ROPE_OK : ROPE_E_HIP; }
 
 // The pieces of rope_refine_bundle's work_dev, in bytes from its start; every piece 8-byte aligned.  `total` 0: a shape refused.
@@ -628,7 +562,7 @@ extern "C" int rope_bundle_schur_step(const double *words_dev, const double *poo
                                       double *trial_q_dev, double *trial_pose_dev, void *stream)
 {
     if (n_frames < 1 || !words_dev || !pooled_dev || !q_dev || !pose_dev || !lam_dev || !work_dev || !trial_q_dev || !trial_pose_dev) return ROPE_E_ARG;
-    if (bad6(joint_mask) || bad6(camera_mask) || bad_limits(limits)) return ROPE_E_ARG;
+    if (bad_mask6(joint_mask) || bad_mask6(camera_mask) || bad_limits(limits)) return ROPE_E_ARG;
     if (misaligned8(words_dev) || misaligned8(pooled_dev) || misaligned8(q_dev) || misaligned8(pose_dev) || misaligned8(lam_dev) ||
         misaligned8(work_dev) || misaligned8(trial_q_dev) || misaligned8(trial_pose_dev))
         return ROPE_E_ARG;
@@ -638,14 +572,14 @@ extern "C" int rope_bundle_schur_step(const double *words_dev, const double *poo
     hipLaunchKernelGGL(schur_frame_kernel, grid, block, 0, s, words_dev, pooled_dev, lam_dev, n_frames, joint_mask, camera_mask, rec);
     hipLaunchKernelGGL(schur_reduce_kernel, dim3(1), block, 0, s, rec, pooled_dev, lam_dev, n_frames, camera_mask, pose_dev, state, trial_pose_dev);
     hipLaunchKernelGGL(schur_back_kernel, grid, block, 0, s, words_dev, pooled_dev, rec, state, q_dev, n_frames, joint_mask, camera_mask,
-                       limits_of(limits), trial_q_dev);
+                       JointLimits(limits), trial_q_dev);
     return launched();
 }
 
 extern "C" int rope_bundle_schur_variance(const double *words_dev, const double *pooled_dev, int n_frames, int joint_mask, int camera_mask,
                                           void *work_dev, double *var_q_dev, double *var_pose_dev, void *stream)
 {
-    if (n_frames < 1 || !words_dev || !pooled_dev || !work_dev || !var_q_dev || !var_pose_dev || bad6(joint_mask) || bad6(camera_mask)) return ROPE_E_ARG;
+    if (n_frames < 1 || !words_dev || !pooled_dev || !work_dev || !var_q_dev || !var_pose_dev || bad_mask6(joint_mask) || bad_mask6(camera_mask)) return ROPE_E_ARG;
     if (misaligned8(words_dev) || misaligned8(pooled_dev) || misaligned8(work_dev) || misaligned8(var_q_dev) || misaligned8(var_pose_dev)) return ROPE_E_ARG;
     double *const rec = static_cast<double *>(work_dev), *const state = rec + (size_t)n_frames * REC;
     const dim3 grid(frame_grid(n_frames)), block(BP_THREADS);
@@ -666,7 +600,7 @@ extern "C" int rope_bundle_columns_step(const double *pooled_dev, const double *
         misaligned8(trial_pose_dev) || misaligned8(trial_off_dev) || misaligned8(trial_q_dev))
         return ROPE_E_ARG;
     hipLaunchKernelGGL(columns_step_kernel, dim3(frame_grid(n_frames)), dim3(BP_THREADS), 0, (hipStream_t)stream, pooled_dev, lam_dev, slot_mask,
-                       pose_dev, off_dev, q0_dev, n_frames, limits_of(limits), trial_pose_dev, trial_off_dev, trial_q_dev);
+                       pose_dev, off_dev, q0_dev, n_frames, JointLimits(limits), trial_pose_dev, trial_off_dev, trial_q_dev);
     return launched();
 }
 
@@ -698,7 +632,7 @@ extern "C" int rope_refine_bundle(rope_ctx *c, int mode, const double *camera_po
         !costs_out || !steps_out || !frame_cost_out)
         ARG_FAIL(c, "rope_refine_bundle: null pointer");
     if (((uintptr_t)frame_depth_dev & 3) || misaligned8(work_dev)) ARG_FAIL(c, "rope_refine_bundle: misaligned device pointer");
-    if (bad6(joint_mask) || bad6(camera_mask) || (joint_mask == 0 && camera_mask == 0))
+    if (bad_mask6(joint_mask) || bad_mask6(camera_mask) || (joint_mask == 0 && camera_mask == 0))
         ARG_FAIL(c, "rope_refine_bundle: joint_mask and camera_mask are 0 .. 63, not both 0");
     if (bad_limits(limits)) ARG_FAIL(c, "rope_refine_bundle: limits must be finite with lo <= hi");
     if (iterations < 0 || !std::isfinite(damping) || damping < 0.0) ARG_FAIL(c, "rope_refine_bundle: iterations and damping must not be negative");

@@ -19,7 +19,8 @@
 // LDS element-major, s_m[element][thread] — lane t reads word t of a row of 64 consecutive 8-byte words, whatever element its
 // own control flow has reached, so a wave's access is at unit stride.  21.5 KB (step) and 24.6 KB (variance) a workgroup of one
 // wave; a batch is a few hundred frames, so occupancy is not what these kernels wait for.  No thread reads another's words and
-// there is no barrier: a thread beyond the batch simply leaves.
+// there is no barrier: a thread beyond the batch simply leaves.  The elimination itself, the clip, the cost and the checks of masks
+// and limits are rope_bundle_polish.hip's as well and live in rope_solve.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -31,6 +32,7 @@
 
 #include "rope_ctx.h"
 #include "rope_fk.h"
+#include "rope_solve.h"
 
 namespace {
 
@@ -38,13 +40,10 @@ constexpr int POLISH_THREADS = 64;
 constexpr int POLISH_COLS = 7;                  // six columns of M and the right-hand side
 constexpr int POLISH_ELEMS = 6 * POLISH_COLS;
 
-struct PolishLimits { double lo[6], hi[6]; };
 struct PolishCamera { double R[9], t[3]; };     // X_c = R (X_w - t)
 
 // word of A[i][j], i <= j, among a frame's ROPE_NEQ_WORDS: the upper triangle row by row from word 10
 __device__ __forceinline__ int tri_word(int i, int j) { return 10 + 6 * i - (i * (i - 1)) / 2 + (j - i); }
-
-#define SM(r, c) s_m[(r) * POLISH_COLS + (c)][t]
 
 // The live joints of a frame: those of active_mask with a positive diagonal entry, ascending, three bits each -> p.
 __device__ __forceinline__ int live_joints(const double *__restrict__ w, int active_mask, uint32_t &packed)
@@ -65,45 +64,14 @@ __device__ __forceinline__ void load_block(double (*s_m)[POLISH_THREADS], int t,
         for (int c = 0; c < p; c++) {
             const int jc = (packed >> (3 * c)) & 7;
             const double a = w[jr <= jc ? tri_word(jr, jc) : tri_word(jc, jr)];
-            SM(r, c) = (damp && r == c) ? a + lam * a : a;
+            s_m[r * POLISH_COLS + c][t] = (damp && r == c) ? a + lam * a : a;
         }
     }
-}
-
-// Gaussian elimination with partial pivoting and back substitution on the thread's p x (p + 1) system; x ends in column 6.
-// false: a pivot that is 0 or not finite.
-__device__ __forceinline__ bool solve_block(double (*s_m)[POLISH_THREADS], int t, int p)
-{
-    for (int k = 0; k < p; k++) {
-        int piv = k;
-        double best = fabs(SM(k, k));
-        for (int r = k + 1; r < p; r++) {                       // the FIRST row with the largest magnitude
-            const double a = fabs(SM(r, k));
-            if (a > best) { best = a; piv = r; }
-        }
-        const double pv = SM(piv, k);
-        if (pv == 0.0 || !isfinite(pv)) return false;
-        if (piv != k) {
-            for (int c = k; c < p; c++) { const double u = SM(k, c); SM(k, c) = SM(piv, c); SM(piv, c) = u; }
-            const double u = SM(k, 6); SM(k, 6) = SM(piv, 6); SM(piv, 6) = u;
-        }
-        for (int i = k + 1; i < p; i++) {
-            const double f = SM(i, k) / pv;
-            for (int c = k + 1; c < p; c++) SM(i, c) = SM(i, c) - f * SM(k, c);
-            SM(i, 6) = SM(i, 6) - f * SM(k, 6);
-        }
-    }
-    for (int i = p - 1; i >= 0; i--) {
-        double s = SM(i, 6);
-        for (int c = i + 1; c < p; c++) s = s - SM(i, c) * SM(c, 6);
-        SM(i, 6) = s / SM(i, i);
-    }
-    return true;
 }
 
 __global__ void __launch_bounds__(POLISH_THREADS)
 levenberg_step_kernel(const double *__restrict__ words, const double *__restrict__ q, const double *__restrict__ lam_dev, int n_frames,
-                      int active_mask, PolishLimits lim, double *__restrict__ trial)
+                      int active_mask, JointLimits lim, double *__restrict__ trial)
 {
     __shared__ double s_m[POLISH_ELEMS][POLISH_THREADS];
     const int t = threadIdx.x;
@@ -115,20 +83,17 @@ levenberg_step_kernel(const double *__restrict__ words, const double *__restrict
     bool ok = p > 0;
     if (ok) {
         load_block(s_m, t, w, packed, p, true, lam_dev[f]);
-        for (int r = 0; r < p; r++) SM(r, 6) = -w[4 + ((packed >> (3 * r)) & 7)];
-        ok = solve_block(s_m, t, p);
-        for (int r = 0; ok && r < p; r++) ok = isfinite(SM(r, 6));
+        for (int r = 0; r < p; r++) s_m[r * POLISH_COLS + 6][t] = -w[4 + ((packed >> (3 * r)) & 7)];
+        ok = eliminate<6, POLISH_COLS, POLISH_THREADS>(s_m, t, p, 1);
+        for (int r = 0; ok && r < p; r++) ok = isfinite(s_m[r * POLISH_COLS + 6][t]);
     }
     int k = 0;
 #pragma unroll
     for (int j = 0; j < 6; j++) {
         const bool live = ((active_mask >> j) & 1) && w[tri_word(j, j)] > 0.0;
-        const double d = (ok && live) ? SM(k, 6) : 0.0;
+        const double d = (ok && live) ? s_m[k * POLISH_COLS + 6][t] : 0.0;
         k += live ? 1 : 0;
-        double v = q[(size_t)f * 6 + j] + d;
-        v = v < lim.lo[j] ? lim.lo[j] : v;
-        v = v > lim.hi[j] ? lim.hi[j] : v;
-        trial[(size_t)f * 6 + j] = v;
+        trial[(size_t)f * 6 + j] = clip_to(q[(size_t)f * 6 + j] + d, lim.lo[j], lim.hi[j]);
     }
 }
 
@@ -148,10 +113,10 @@ formal_variance_kernel(const double *__restrict__ words, int n_frames, int activ
         const double s2 = w[3] / (w[2] - (double)p);
         for (int k = 0; ok && k < p; k++) {                     // A x = e_k: the elimination of the block again, with another right-hand side
             load_block(s_m, t, w, packed, p, false, 0.0);
-            for (int r = 0; r < p; r++) SM(r, 6) = r == k ? 1.0 : 0.0;
-            ok = solve_block(s_m, t, p);
+            for (int r = 0; r < p; r++) s_m[r * POLISH_COLS + 6][t] = r == k ? 1.0 : 0.0;
+            ok = eliminate<6, POLISH_COLS, POLISH_THREADS>(s_m, t, p, 1);
             if (ok) {
-                const double v = s2 * SM(k, 6);
+                const double v = s2 * s_m[k * POLISH_COLS + 6][t];
                 s_v[k][t] = v;
                 ok = isfinite(v) && v >= 0.0;
             }
@@ -168,8 +133,6 @@ formal_variance_kernel(const double *__restrict__ words, int n_frames, int activ
         var[(size_t)f * 6 + j] = v;
     }
 }
-
-#undef SM
 
 __device__ __forceinline__ double dot3(double ux, double uy, double uz, double vx, double vy, double vz) { return (ux * vx + uy * vy) + uz * vz; }
 
@@ -199,9 +162,6 @@ joint_axes_kernel(const double *__restrict__ q, int n_frames, const double *__re
         }
     }
 }
-
-// the mean truncated cost of a frame's words: [1] / [0], inf without a pixel to compare
-__device__ __forceinline__ double mean_cost(const double *w) { return w[0] > 0.0 ? w[1] / w[0] : (double)INFINITY; }
 
 // The state of rope_refine_poses at the start: the cost of the systems at q, no step taken, the damping every frame starts with
 __global__ void __launch_bounds__(POLISH_THREADS)
@@ -244,15 +204,6 @@ polish_inliers_kernel(const double *__restrict__ words, int n_frames, double *__
 }
 
 inline unsigned polish_grid(int n_frames) { return (unsigned)((n_frames + POLISH_THREADS - 1) / POLISH_THREADS); }
-inline bool misaligned8(const void *p) { return ((uintptr_t)p & 7) != 0; }
-inline bool bad_mask(int active_mask) { return active_mask < 0 || active_mask > 63; }
-bool bad_limits(const double *limits)
-{
-    if (!limits) return true;
-    for (int j = 0; j < 6; j++)
-        if (!std::isfinite(limits[2 * j]) || !std::isfinite(limits[2 * j + 1]) || limits[2 * j] > limits[2 * j + 1]) return true;
-    return false;
-}
 
 // The pieces of rope_refine_poses' work_dev, in bytes from its start; every piece 8-byte aligned.  `total` 0: a shape refused.
 // What the caller gets back lies in one run, q .. steps and then the systems, so that it comes down in one copy.
@@ -307,18 +258,16 @@ extern "C" int rope_joint_axes(rope_ctx *c, const double *q_dev, int n_frames, c
 extern "C" int rope_levenberg_step(const double *words_dev, const double *q_dev, const double *lam_dev, int n_frames, int active_mask,
                                    const double *limits, double *trial_dev, void *stream)
 {
-    if (n_frames < 1 || !words_dev || !q_dev || !lam_dev || !trial_dev || bad_mask(active_mask) || bad_limits(limits)) return ROPE_E_ARG;
+    if (n_frames < 1 || !words_dev || !q_dev || !lam_dev || !trial_dev || bad_mask6(active_mask) || bad_limits(limits)) return ROPE_E_ARG;
     if (misaligned8(words_dev) || misaligned8(q_dev) || misaligned8(lam_dev) || misaligned8(trial_dev)) return ROPE_E_ARG;
-    PolishLimits lim;
-    for (int j = 0; j < 6; j++) { lim.lo[j] = limits[2 * j]; lim.hi[j] = limits[2 * j + 1]; }
     hipLaunchKernelGGL(levenberg_step_kernel, dim3(polish_grid(n_frames)), dim3(POLISH_THREADS), 0, (hipStream_t)stream, words_dev, q_dev, lam_dev,
-                       n_frames, active_mask, lim, trial_dev);
+                       n_frames, active_mask, JointLimits(limits), trial_dev);
     return hipGetLastError() == hipSuccess ? ROPE_OK : ROPE_E_HIP;
 }
 
 extern "C" int rope_formal_variance(const double *words_dev, int n_frames, int active_mask, double *var_dev, void *stream)
 {
-    if (n_frames < 1 || !words_dev || !var_dev || bad_mask(active_mask) || misaligned8(words_dev) || misaligned8(var_dev)) return ROPE_E_ARG;
+    if (n_frames < 1 || !words_dev || !var_dev || bad_mask6(active_mask) || misaligned8(words_dev) || misaligned8(var_dev)) return ROPE_E_ARG;
     hipLaunchKernelGGL(formal_variance_kernel, dim3(polish_grid(n_frames)), dim3(POLISH_THREADS), 0, (hipStream_t)stream, words_dev, n_frames,
                        active_mask, var_dev);
     return hipGetLastError() == hipSuccess ? ROPE_OK : ROPE_E_HIP;
@@ -342,7 +291,7 @@ extern "C" int rope_refine_poses(rope_ctx *c, const double *q, const float *fram
     if (!q || !frame_depth_dev || !camera_pose6 || !work_dev || !angles_out || !var_out || !cost_before || !cost_after || !steps_out || !inliers_out)
         ARG_FAIL(c, "rope_refine_poses: null pointer");
     if (((uintptr_t)frame_depth_dev & 3) || misaligned8(work_dev)) ARG_FAIL(c, "rope_refine_poses: misaligned device pointer");
-    if (bad_mask(active_mask)) ARG_FAIL(c, "rope_refine_poses: active_mask outside 0 .. 63");
+    if (bad_mask6(active_mask)) ARG_FAIL(c, "rope_refine_poses: active_mask outside 0 .. 63");
     if (bad_limits(limits)) ARG_FAIL(c, "rope_refine_poses: limits must be finite with lo <= hi");
     if (iterations < 0 || !std::isfinite(damping) || damping < 0.0) ARG_FAIL(c, "rope_refine_poses: iterations and damping must not be negative");
     if (!std::isfinite(clip_m) || !(clip_m > 0.0f)) ARG_FAIL(c, "rope_refine_poses: clip_m must be finite and positive");

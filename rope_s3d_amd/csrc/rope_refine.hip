@@ -9,7 +9,8 @@
 // pose's parameters instead of joint axes, every drawn link moves with every column (the base, link 0, too), and a surface point P
 // has the velocity w x P + v per unit of a column.  The two entry points share one kernel body, neq_partial_body<CAMERA>; what
 // differs is the MOVING rule and the column of J, nothing in the shape or in the order of the sums.  tests/camera_refine_ref.py
-// restates that contract.
+// restates that contract.  The depth surface of a pixel, the columns' velocities, the chunk rule, the gather and the host checks are
+// rope_bundle.hip's and rope_silhouette.hip's as well and live in rope_neq.h; this file keeps the 31 register accumulators.
 //
 // Shape.  A workgroup takes NEQ_CHUNK consecutive pixels of one frame — pixel p = chunk NEQ_CHUNK + k NEQ_THREADS + t for thread t,
 // k = 0 .. 7, so a wave's loads are consecutive — and a thread reads its pixel's R, id and T and the R and id of its four
@@ -23,34 +24,13 @@
 // order.  The same planes give the same bytes from run to run, and in one call or in several.
 // Lane exchange: every accumulator is defined (zero) in all 256 threads before the loop, no thread leaves early, and pixels beyond
 // the frame add nothing instead of branching around the butterfly: no lane reads what an inactive lane made.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/rope_s3d.h"
+#include "rope_neq.h"
 
 namespace {
 
-constexpr int NEQ_THREADS = 256;
-constexpr int NEQ_WAVES = NEQ_THREADS / 64;
-constexpr int NEQ_PER_THREAD = 8;
-constexpr int NEQ_CHUNK = NEQ_THREADS * NEQ_PER_THREAD;      // pixels of a workgroup
-constexpr int NEQ_JOINTS = 6;
 constexpr int NEQ_USED = 4 + NEQ_JOINTS + NEQ_JOINTS * (NEQ_JOINTS + 1) / 2;       // 31 of the 32 words
-constexpr int NEQ_GATHER_THREADS = 64;                       // two frames a workgroup
 
 static_assert(NEQ_USED <= ROPE_NEQ_WORDS && ROPE_NEQ_WORDS == 32, "the words of a frame");
-
-struct Camera { double fx, fy, cx, cy; };
-
-struct Vec3 { double x, y, z; };
-
-__device__ __forceinline__ Vec3 sub(const Vec3 &a, const Vec3 &b) { return Vec3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ Vec3 cross(const Vec3 &a, const Vec3 &b)
-{
-    return Vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ double dot(const Vec3 &a, const Vec3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
 // Workgroup blockIdx.x = frame * chunks + chunk.  CAMERA = false: `joints` holds (axis, point) per joint and link l moves with the
 // joints j < l; CAMERA = true: `joints` holds (w, v) per column and every drawn link moves with every column.
@@ -93,41 +73,18 @@ neq_partial_kernel(const float *__restrict__ render, const uint8_t *__restrict__
         }
 
         const int y = p / W, x = p - y * W;
-        const double kx = ((double)x - cam.cx) / cam.fx, ky = ((double)y - cam.cy) / cam.fy;
-        const Vec3 P = {kx * z, ky * z, z};
-        Vec3 dX = {0.0, 0.0, 0.0}, dY = {0.0, 0.0, 0.0};
-        if (x + 1 < W && i0[p + 1] == id) {
-            const double zn = (double)r0[p + 1], kn = ((double)(x + 1) - cam.cx) / cam.fx;
-            dX = sub(Vec3{kn * zn, ky * zn, zn}, P);
-        } else if (x > 0 && i0[p - 1] == id) {
-            const double zn = (double)r0[p - 1], kn = ((double)(x - 1) - cam.cx) / cam.fx;
-            dX = sub(P, Vec3{kn * zn, ky * zn, zn});
-        }
-        if (y + 1 < H && i0[p + W] == id) {
-            const double zn = (double)r0[p + W], kn = ((double)(y + 1) - cam.cy) / cam.fy;
-            dY = sub(Vec3{kx * zn, kn * zn, zn}, P);
-        } else if (y > 0 && i0[p - W] == id) {
-            const double zn = (double)r0[p - W], kn = ((double)(y - 1) - cam.cy) / cam.fy;
-            dY = sub(P, Vec3{kx * zn, kn * zn, zn});
-        }
-        const Vec3 n = cross(dX, dY);
-        if (!(isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) || (n.x == 0.0 && n.y == 0.0 && n.z == 0.0)) continue;      // no normal
-        const double nn = dot(n, n), nP = dot(n, P), PP = dot(P, P);
-        if (!(nP * nP >= 0.01 * (nn * PP)) || nP == 0.0) continue;                      // grazing
+        Vec3 P, n;
+        double nP;
+        if (!depth_surface(r0, i0, p, x, y, H, W, id, z, cam, P, n, nP)) continue;      // no normal, or grazing
 
         double J[NEQ_JOINTS];
 #pragma unroll
         for (int j = 0; j < NEQ_JOINTS; j++) {
             J[j] = 0.0;
             if (CAMERA) {
-                if (j < n_joints) {                                                     // every column moves every drawn link
-                    const Vec3 w = {jf[6 * j], jf[6 * j + 1], jf[6 * j + 2]}, v = {jf[6 * j + 3], jf[6 * j + 4], jf[6 * j + 5]};
-                    const Vec3 c = cross(w, P);
-                    J[j] = (z * dot(n, Vec3{c.x + v.x, c.y + v.y, c.z + v.z})) / nP;  // the point moves by w x P + v
-                }
+                if (j < n_joints) J[j] = depth_column(z, n, nP, twist_velocity(jf, j, P));      // every column moves every drawn link
             } else if (j < n_joints && j < id) {                                        // joint j moves the links behind it
-                const Vec3 a = {jf[6 * j], jf[6 * j + 1], jf[6 * j + 2]}, o = {jf[6 * j + 3], jf[6 * j + 4], jf[6 * j + 5]};
-                J[j] = (z * dot(n, cross(a, sub(P, o)))) / nP;
+                J[j] = depth_column(z, n, nP, joint_velocity(jf, j, P));
             }
         }
         acc[2] += 1.0;
@@ -161,28 +118,11 @@ neq_partial_kernel(const float *__restrict__ render, const uint8_t *__restrict__
     }
 }
 
-// Thread t of workgroup b: word t & 31 of frame 2 b + (t >> 5), the partials of the frame added in index order.
-__global__ void __launch_bounds__(NEQ_GATHER_THREADS)
+// a frame's partials added in index order, two frames a workgroup (rope_neq.h)
+__global__ void __launch_bounds__(NEQ_GATHER_FRAMES * ROPE_NEQ_WORDS)
 neq_gather_kernel(const double *__restrict__ work, int n_frames, int chunks, double *__restrict__ out)
 {
-    const int frame = blockIdx.x * (NEQ_GATHER_THREADS / ROPE_NEQ_WORDS) + (int)(threadIdx.x / ROPE_NEQ_WORDS);
-    const int word = threadIdx.x % ROPE_NEQ_WORDS;
-    if (frame >= n_frames) return;
-    const double *const w = work + (size_t)frame * chunks * ROPE_NEQ_WORDS + word;
-    double s = w[0];
-    for (int c = 1; c < chunks; c++) s += w[(size_t)c * ROPE_NEQ_WORDS];
-    out[(size_t)frame * ROPE_NEQ_WORDS + word] = s;
-}
-
-// chunks of a frame, or 0 when the shape is refused
-long long neq_chunks(int n_frames, int H, int W)
-{
-    if (n_frames < 1 || H < 1 || W < 1) return 0;
-    const long long hw = (long long)H * (long long)W;
-    if (hw > (1ll << 24)) return 0;
-    const long long chunks = (hw + NEQ_CHUNK - 1) / NEQ_CHUNK;
-    if ((long long)n_frames * chunks >= (1ll << 24)) return 0;                          // a grid holds fewer than 2^32 threads: 2^24 workgroups of 256
-    return chunks;
+    neq_gather<ROPE_NEQ_WORDS>(work, n_frames, chunks, out);
 }
 
 // the checks and the two launches both entry points share; `columns_dev, n_columns`: joints or twists
@@ -191,12 +131,9 @@ int neq_launch(const float *render_depth_dev, const uint8_t *render_ids_dev, con
                float fx, float fy, float cx, float cy, const double *columns_dev, int n_columns, float clip_m, double *out_dev, double *work_dev,
                void *stream)
 {
-    if (n_links < 1 || n_links > ROPE_MAX_LINKS || n_columns < 1 || n_columns > NEQ_JOINTS) return ROPE_E_ARG;
+    if (neq_bad_args(n_links, fx, fy, cx, cy, render_depth_dev, render_ids_dev, frame_depth_dev, out_dev, work_dev)) return ROPE_E_ARG;
+    if (n_columns < 1 || n_columns > NEQ_JOINTS || !columns_dev || ((uintptr_t)columns_dev & 7)) return ROPE_E_ARG;
     if (!isfinite(clip_m) || !(clip_m > 0.0f)) return ROPE_E_ARG;
-    if (!isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy) || fx == 0.0f || fy == 0.0f) return ROPE_E_ARG;
-    if (!render_depth_dev || !render_ids_dev || !frame_depth_dev || !columns_dev || !out_dev || !work_dev) return ROPE_E_ARG;
-    if (((uintptr_t)render_depth_dev & 3) || ((uintptr_t)frame_depth_dev & 3)) return ROPE_E_ARG;
-    if (((uintptr_t)columns_dev & 7) || ((uintptr_t)out_dev & 7) || ((uintptr_t)work_dev & 7)) return ROPE_E_ARG;
     const long long chunks = neq_chunks(n_frames, H, W);
     if (chunks == 0) return ROPE_E_ARG;
 
@@ -206,8 +143,7 @@ int neq_launch(const float *render_depth_dev, const uint8_t *render_ids_dev, con
                        0, st, render_depth_dev, render_ids_dev, frame_depth_dev, H, W, (int)chunks, n_links, cam, columns_dev, n_columns,
                        (double)clip_m, work_dev);
     if (hipGetLastError() != hipSuccess) return ROPE_E_HIP;
-    const int per = NEQ_GATHER_THREADS / ROPE_NEQ_WORDS;
-    hipLaunchKernelGGL(neq_gather_kernel, dim3((unsigned)((n_frames + per - 1) / per)), dim3(NEQ_GATHER_THREADS), 0, st, work_dev, n_frames,
+    hipLaunchKernelGGL(neq_gather_kernel, dim3(neq_gather_grid(n_frames)), dim3(NEQ_GATHER_FRAMES * ROPE_NEQ_WORDS), 0, st, work_dev, n_frames,
                        (int)chunks, out_dev);
     return hipGetLastError() == hipSuccess ? ROPE_OK : ROPE_E_HIP;
 }
@@ -216,7 +152,7 @@ int neq_launch(const float *render_depth_dev, const uint8_t *render_ids_dev, con
 
 extern "C" size_t rope_pose_normal_workspace(int n_frames, int H, int W)
 {
-    return (size_t)n_frames * (size_t)neq_chunks(n_frames, H, W) * ROPE_NEQ_WORDS * sizeof(double);
+    return neq_workspace(n_frames, H, W, ROPE_NEQ_WORDS);
 }
 
 extern "C" int rope_pose_normal_equations(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames,

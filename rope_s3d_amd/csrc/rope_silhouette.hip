@@ -3,7 +3,8 @@
 //   rope_silhouette_normal_equations   per frame J^T J, J^T e and the residual sums of the render's CONTOUR pixels against that field,
 //                                      over rope_bundle_normal_equations' twelve column slots and in its 96-word layout.
 // Everything floating is float64 with one IEEE operation per written operation (-ffp-contract=off); tests/silhouette_ref.py restates
-// both contracts in numpy.  The geometry helpers are copies of rope_bundle.hip's: that file is untouched.
+// both contracts in numpy.  The normal-equation half holds what is particular to the outline term, sneq_pixel; the vector helpers,
+// the columns' velocities and the body of the kernel are rope_bundle.hip's as well and live in rope_neq.h.
 //
 // Distance.  A workgroup takes a tile of 32 x 32 pixels of one plane.  With R <= 16 the tile and its halo are 64 columns wide: a row
 // of it is ONE 64-bit word.  Each wave reads rows of 64 mask bytes, a lane a byte, and two ballots turn the row into the word of its
@@ -12,8 +13,8 @@
 // column are one count of leading and one of trailing zeros, so a row costs a handful of integer operations whatever R is, and
 // m = min over the rows of dy^2 + dx^2.  All lanes of a half wave read the same word of LDS (a broadcast).  No floating point at all.
 //
-// Normal equations.  The shape is bneq_partial_kernel's: a workgroup takes SNEQ_CHUNK consecutive pixels of a frame in 8 passes of
-// 256; a thread classifies its pixel (contour pixels are a perimeter, a few in a hundred), adds words 0 .. 2 to accumulators of its
+// Normal equations.  The shape is bneq_partial_kernel's (bneq_pack_and_own_words, rope_neq.h): a workgroup takes NEQ_CHUNK
+// consecutive pixels of a frame in 8 passes of 256; a thread classifies its pixel (contour pixels are a perimeter, a few in a hundred), adds words 0 .. 2 to accumulators of its
 // own and, for an inlier, works out v = (J_0 .. J_11, e); the inliers of a pass are packed into LDS in pixel order (a ballot and a
 // prefix count per wave, the waves' counts through LDS); then the threads own WORDS, v_a v_b for a <= b over the 13 entries, the two
 // halves of the workgroup half of the rows each.  Background and interior pixels cost the classification alone.
@@ -21,11 +22,7 @@
 // Determinism.  No floating-point atomics.  A workgroup's pixels depend on H W alone; rows are packed in pixel order; the halves are
 // added first + second; words 0 .. 2 go through a butterfly and the waves in the order 0 .. 3; the workgroup writes ONE partial of
 // ROPE_BNEQ_WORDS doubles and sneq_gather_kernel adds a frame's partials in index order.  No thread leaves before the last barrier.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/rope_s3d.h"
+#include "rope_neq.h"
 
 namespace {
 
@@ -90,31 +87,6 @@ mask_distance_kernel(const uint8_t *__restrict__ mask, int n_planes, int H, int 
 }
 
 // ---------------------------------------------------------------------------------------------- the normal equations
-constexpr int SNEQ_THREADS = 256;
-constexpr int SNEQ_WAVES = SNEQ_THREADS / 64;
-constexpr int SNEQ_PER_THREAD = 8;
-constexpr int SNEQ_CHUNK = SNEQ_THREADS * SNEQ_PER_THREAD;  // pixels of a workgroup: rope_bundle.hip's
-constexpr int SNEQ_HALF = 6;                                 // joint slots; as many camera slots
-constexpr int SNEQ_SLOTS = 2 * SNEQ_HALF;
-constexpr int SNEQ_VEC = SNEQ_SLOTS + 1;                     // J_0 .. J_11 and e
-constexpr int SNEQ_PAIRS = SNEQ_VEC * (SNEQ_VEC + 1) / 2;    // 91
-constexpr int SNEQ_HEAD = 3;                                 // words 0 .. 2: per-pixel sums that are no product of two entries of v
-constexpr int SNEQ_SEG_THREADS = SNEQ_THREADS / 2;           // threads of a half
-constexpr int SNEQ_GATHER_FRAMES = 2;                        // frames a gather workgroup
-
-static_assert(ROPE_BNEQ_WORDS == 96 && SNEQ_HEAD + SNEQ_PAIRS + 2 == ROPE_BNEQ_WORDS, "the words of a frame");
-static_assert(SNEQ_PAIRS <= SNEQ_SEG_THREADS, "a thread a word in each half");
-
-struct Camera { double fx, fy, cx, cy; };
-
-struct Vec3 { double x, y, z; };
-
-__device__ __forceinline__ Vec3 sub(const Vec3 &a, const Vec3 &b) { return Vec3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ Vec3 cross(const Vec3 &a, const Vec3 &b)
-{
-    return Vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-
 // phi of step 1: the signed distance to the boundary in pixels, from the field's integer; beyond the truncation it is that of FAR
 __device__ __forceinline__ double sil_phi(int32_t sd, int far2)
 {
@@ -127,7 +99,7 @@ __device__ __forceinline__ double sil_phi(int32_t sd, int far2)
 // Pixel p of a frame: adds its share of words 0 .. 2 to head and, for an inlier, fills v and returns true.
 __device__ __forceinline__ bool sneq_pixel(const float *__restrict__ r0, const uint8_t *__restrict__ i0, const int32_t *__restrict__ d0, int p, int H,
                                            int W, int n_links, const Camera &cam, const double *__restrict__ jf, int n_joints,
-                                           const double *__restrict__ tf, int n_cols, int near2, double (&head)[SNEQ_HEAD], double (&v)[SNEQ_VEC])
+                                           const double *__restrict__ tf, int n_cols, int near2, double (&head)[BNEQ_HEAD], double (&v)[BNEQ_VEC])
 {
     const int id = i0[p];
     if (id >= n_links) return false;                                                    // not rendered
@@ -156,39 +128,23 @@ __device__ __forceinline__ bool sneq_pixel(const float *__restrict__ r0, const u
     const double kx = ((double)x - cam.cx) / cam.fx, ky = ((double)y - cam.cy) / cam.fy;
     const Vec3 P = {kx * z, ky * z, z};
 #pragma unroll
-    for (int j = 0; j < SNEQ_HALF; j++) {
+    for (int j = 0; j < NEQ_JOINTS; j++) {
         v[j] = 0.0;
-        if (j < n_joints && j < id) {                                                   // joint j moves the links behind it; the base none
-            const Vec3 a = {jf[6 * j], jf[6 * j + 1], jf[6 * j + 2]}, o = {jf[6 * j + 3], jf[6 * j + 4], jf[6 * j + 5]};
-            const Vec3 u = cross(a, sub(P, o));
-            const double vx = (cam.fx * (u.x - kx * u.z)) / z, vy = (cam.fy * (u.y - ky * u.z)) / z;
-            v[j] = gx * vx + gy * vy;
-        }
-        v[SNEQ_HALF + j] = 0.0;
-        if (j < n_cols) {                                                               // every column moves every drawn link
-            const Vec3 w = {tf[6 * j], tf[6 * j + 1], tf[6 * j + 2]}, l = {tf[6 * j + 3], tf[6 * j + 4], tf[6 * j + 5]};
-            const Vec3 c = cross(w, P);
-            const Vec3 u = {c.x + l.x, c.y + l.y, c.z + l.z};
-            const double vx = (cam.fx * (u.x - kx * u.z)) / z, vy = (cam.fy * (u.y - ky * u.z)) / z;
-            v[SNEQ_HALF + j] = gx * vx + gy * vy;
-        }
+        if (j < n_joints && j < id) v[j] = silhouette_column(gx, gy, cam, kx, ky, z, joint_velocity(jf, j, P));    // joint j moves the links behind it
+        v[NEQ_JOINTS + j] = 0.0;
+        if (j < n_cols) v[NEQ_JOINTS + j] = silhouette_column(gx, gy, cam, kx, ky, z, twist_velocity(tf, j, P));   // every column moves every drawn link
     }
-    v[SNEQ_SLOTS] = e;
+    v[BNEQ_SLOTS] = e;
     head[2] += 1.0;
     return true;
 }
 
 // Workgroup blockIdx.x = frame * chunks + chunk.
-__global__ void __launch_bounds__(SNEQ_THREADS)
+__global__ void __launch_bounds__(NEQ_THREADS)
 sneq_partial_kernel(const float *__restrict__ render, const uint8_t *__restrict__ ids, const int32_t *__restrict__ sd2, int H, int W, int chunks,
                     int n_links, Camera cam, const double *__restrict__ joints, int n_joints, const double *__restrict__ twists, int n_cols,
                     int near2, double *__restrict__ work)
 {
-    __shared__ double s_v[SNEQ_THREADS * SNEQ_VEC];             // the packed inliers of a pass, a row each
-    __shared__ double s_head[SNEQ_WAVES][SNEQ_HEAD];
-    __shared__ double s_second[SNEQ_PAIRS];                     // the second half's sums
-    __shared__ int s_count[SNEQ_WAVES];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int frame = blockIdx.x / chunks, chunk = blockIdx.x - frame * chunks;
     const int hw = H * W;                                                               // at most 2^24
     const float *const r0 = render + (size_t)frame * hw;
@@ -196,91 +152,16 @@ sneq_partial_kernel(const float *__restrict__ render, const uint8_t *__restrict_
     const uint8_t *const i0 = ids + (size_t)frame * hw;
     const double *const jf = joints + (size_t)frame * n_joints * 6;                     // never read when its count is 0
     const double *const tf = twists + (size_t)frame * n_cols * 6;
-
-    // the word of this thread in the accumulation: entries a <= b of v, row by row over the 13, and the word of the frame they belong to
-    const int half = t / SNEQ_SEG_THREADS, pair = t - half * SNEQ_SEG_THREADS;
-    int a = 0, b = 0;
-    if (pair < SNEQ_PAIRS) {
-        int w = pair;
-        while (w >= SNEQ_VEC - a) { w -= SNEQ_VEC - a; a++; }
-        b = a + w;
-    }
-    const int word = b < SNEQ_SLOTS ? 4 + SNEQ_SLOTS + (a * SNEQ_SLOTS - a * (a - 1) / 2) + (b - a) : (a < SNEQ_SLOTS ? 4 + a : 3);
-
-    double head[SNEQ_HEAD] = {0.0, 0.0, 0.0};
-    double acc = 0.0;
-    for (int k = 0; k < SNEQ_PER_THREAD; k++) {
-        const int p = chunk * SNEQ_CHUNK + k * SNEQ_THREADS + t;
-        double v[SNEQ_VEC];
-        const bool in = p < hw && sneq_pixel(r0, i0, d0, p, H, W, n_links, cam, jf, n_joints, tf, n_cols, near2, head, v);
-        const unsigned long long m = __ballot(in);
-        if (lane == 0) s_count[wave] = __popcll(m);
-        __syncthreads();
-        int row = __popcll(m & ((1ull << lane) - 1ull)), rows = 0;
-#pragma unroll
-        for (int w = 0; w < SNEQ_WAVES; w++) {
-            const int c = s_count[w];
-            if (w < wave) row += c;
-            rows += c;
-        }
-        if (in) {                                                                       // row < rows <= 256
-#pragma unroll
-            for (int c = 0; c < SNEQ_VEC; c++) s_v[row * SNEQ_VEC + c] = v[c];
-        }
-        __syncthreads();
-        if (pair < SNEQ_PAIRS) {
-            const int mid = (rows + 1) >> 1;
-            const int first = half ? mid : 0, last = half ? rows : mid;
-            for (int i = first; i < last; i++) acc += s_v[i * SNEQ_VEC + a] * s_v[i * SNEQ_VEC + b];
-        }
-        __syncthreads();                                                                // the next pass writes s_count and s_v again
-    }
-
-    // every thread of the workgroup is here with its accumulators defined
-#pragma unroll
-    for (int j = 0; j < SNEQ_HEAD; j++) {
-        double s = head[j];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-        if (lane == 0) s_head[wave][j] = s;
-    }
-    if (half == 1 && pair < SNEQ_PAIRS) s_second[pair] = acc;
-    __syncthreads();
-    double *const out = work + (size_t)blockIdx.x * ROPE_BNEQ_WORDS;
-    if (half == 0) {
-        if (pair < SNEQ_PAIRS) out[word] = acc + s_second[pair];                        // words 3 .. 93, each once
-    } else if (pair < SNEQ_HEAD) {
-        double s = s_head[0][pair];
-#pragma unroll
-        for (int w = 1; w < SNEQ_WAVES; w++) s += s_head[w][pair];
-        out[pair] = s;
-    } else if (pair < SNEQ_HEAD + 2) {
-        out[ROPE_BNEQ_WORDS - 2 + (pair - SNEQ_HEAD)] = 0.0;
-    }
+    bneq_pack_and_own_words(hw, chunk, [&](int p, double (&head)[BNEQ_HEAD], double (&v)[BNEQ_VEC]) {
+        return sneq_pixel(r0, i0, d0, p, H, W, n_links, cam, jf, n_joints, tf, n_cols, near2, head, v);
+    }, work + (size_t)blockIdx.x * ROPE_BNEQ_WORDS);
 }
 
-// Thread t of workgroup b: word t % 96 of frame 2 b + t / 96, the partials of the frame added in index order.
-__global__ void __launch_bounds__(SNEQ_GATHER_FRAMES * ROPE_BNEQ_WORDS)
+// a frame's partials added in index order, two frames a workgroup (rope_neq.h)
+__global__ void __launch_bounds__(NEQ_GATHER_FRAMES * ROPE_BNEQ_WORDS)
 sneq_gather_kernel(const double *__restrict__ work, int n_frames, int chunks, double *__restrict__ out)
 {
-    const int frame = blockIdx.x * SNEQ_GATHER_FRAMES + (int)(threadIdx.x / ROPE_BNEQ_WORDS);
-    const int word = threadIdx.x % ROPE_BNEQ_WORDS;
-    if (frame >= n_frames) return;
-    const double *const w = work + (size_t)frame * chunks * ROPE_BNEQ_WORDS + word;
-    double s = w[0];
-    for (int c = 1; c < chunks; c++) s += w[(size_t)c * ROPE_BNEQ_WORDS];
-    out[(size_t)frame * ROPE_BNEQ_WORDS + word] = s;
-}
-
-// chunks of a frame, or 0 when the shape is refused: rope_bundle.hip's rule
-long long sneq_chunks(int n_frames, int H, int W)
-{
-    if (n_frames < 1 || H < 1 || W < 1) return 0;
-    const long long hw = (long long)H * (long long)W;
-    if (hw > (1ll << 24)) return 0;
-    const long long chunks = (hw + SNEQ_CHUNK - 1) / SNEQ_CHUNK;
-    if ((long long)n_frames * chunks >= (1ll << 24)) return 0;                          // a grid holds fewer than 2^32 threads
-    return chunks;
+    neq_gather<ROPE_BNEQ_WORDS>(work, n_frames, chunks, out);
 }
 
 }  // namespace
@@ -299,7 +180,7 @@ extern "C" int rope_mask_distance(const uint8_t *mask_dev, int N, int H, int W, 
 
 extern "C" size_t rope_silhouette_normal_workspace(int n_frames, int H, int W)
 {
-    return (size_t)n_frames * (size_t)sneq_chunks(n_frames, H, W) * ROPE_BNEQ_WORDS * sizeof(double);
+    return neq_workspace(n_frames, H, W, ROPE_BNEQ_WORDS);
 }
 
 extern "C" int rope_silhouette_normal_equations(const float *render_depth_dev, const uint8_t *render_ids_dev, const int32_t *sd2_dev, int n_frames,
@@ -307,25 +188,19 @@ extern "C" int rope_silhouette_normal_equations(const float *render_depth_dev, c
                                                 int n_joints, const double *twists_dev, int n_cols, int radius, double *out_dev, double *work_dev,
                                                 void *stream)
 {
-    if (n_links < 1 || n_links > ROPE_MAX_LINKS) return ROPE_E_ARG;
-    if (n_joints < 0 || n_joints > SNEQ_HALF || n_cols < 0 || n_cols > SNEQ_HALF || n_joints + n_cols < 1) return ROPE_E_ARG;
+    if (neq_bad_args(n_links, fx, fy, cx, cy, render_depth_dev, render_ids_dev, sd2_dev, out_dev, work_dev)) return ROPE_E_ARG;
+    if (neq_bad_columns12(joints_dev, n_joints, twists_dev, n_cols)) return ROPE_E_ARG;
     if (radius < 1 || radius > ROPE_SIL_MAX_RADIUS) return ROPE_E_ARG;
-    if (!isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy) || fx == 0.0f || fy == 0.0f) return ROPE_E_ARG;
-    if (!render_depth_dev || !render_ids_dev || !sd2_dev || !out_dev || !work_dev) return ROPE_E_ARG;
-    if ((n_joints > 0 && !joints_dev) || (n_cols > 0 && !twists_dev)) return ROPE_E_ARG;
-    if (((uintptr_t)render_depth_dev & 3) || ((uintptr_t)sd2_dev & 3)) return ROPE_E_ARG;
-    if ((n_joints > 0 && ((uintptr_t)joints_dev & 7)) || (n_cols > 0 && ((uintptr_t)twists_dev & 7))) return ROPE_E_ARG;
-    if (((uintptr_t)out_dev & 7) || ((uintptr_t)work_dev & 7)) return ROPE_E_ARG;
-    const long long chunks = sneq_chunks(n_frames, H, W);
+    const long long chunks = neq_chunks(n_frames, H, W);
     if (chunks == 0) return ROPE_E_ARG;
 
     hipStream_t st = (hipStream_t)stream;
     const Camera cam = {(double)fx, (double)fy, (double)cx, (double)cy};
-    hipLaunchKernelGGL(sneq_partial_kernel, dim3((unsigned)((long long)n_frames * chunks)), dim3(SNEQ_THREADS), 0, st, render_depth_dev,
+    hipLaunchKernelGGL(sneq_partial_kernel, dim3((unsigned)((long long)n_frames * chunks)), dim3(NEQ_THREADS), 0, st, render_depth_dev,
                        render_ids_dev, sd2_dev, H, W, (int)chunks, n_links, cam, n_joints > 0 ? joints_dev : nullptr, n_joints,
                        n_cols > 0 ? twists_dev : nullptr, n_cols, radius * radius, work_dev);
     if (hipGetLastError() != hipSuccess) return ROPE_E_HIP;
-    hipLaunchKernelGGL(sneq_gather_kernel, dim3((unsigned)((n_frames + SNEQ_GATHER_FRAMES - 1) / SNEQ_GATHER_FRAMES)),
-                       dim3(SNEQ_GATHER_FRAMES * ROPE_BNEQ_WORDS), 0, st, work_dev, n_frames, (int)chunks, out_dev);
+    hipLaunchKernelGGL(sneq_gather_kernel, dim3(neq_gather_grid(n_frames)), dim3(NEQ_GATHER_FRAMES * ROPE_BNEQ_WORDS), 0, st, work_dev, n_frames,
+                       (int)chunks, out_dev);
     return hipGetLastError() == hipSuccess ? ROPE_OK : ROPE_E_HIP;
 }

@@ -153,3 +153,26 @@ def test_silhouette_kernel_two_pixel_frames_are_a_plus_b(nj, nc):
         return out
 
     _two(run, nt.sil_frames_with, pairs, f"silhouette, {nj} joints, {nc} columns, two inliers")
+
+
+# ---------------------------------------------------------------------------------------------- the shared gather and pack bodies
+@pytest.mark.parametrize('kernel', ['bundle', 'silhouette'])
+def test_twelve_slot_kernels_on_three_frames_of_two_workgroups(kernel):
+    """Three frames of 47 x 45: two workgroups a frame, and the gather kernel's last workgroup holds one frame of its two (the pose
+    and camera kernels meet both in tests/test_gpu_refine.py and tests/test_gpu_camera_refine.py).  The two-inlier frames of the
+    tests above, the first, the middle and the last pair; bit for bit against the reference."""
+    pairs = nt.depth_pairs() if kernel == 'bundle' else nt.sil_pairs()
+    pairs = [pairs[0], pairs[len(pairs) // 2], pairs[-1]]
+    joints, twists = nt.columns(np.random.default_rng(700), 3, 6, 6)
+    if kernel == 'bundle':
+        R, ids, T = nt.frames_with(nt.surface2(), pairs)
+        want = bref.normal_equations(R, ids, T, 4, nt.INTR2, joints, twists, CLIP)[0]
+        rc, got = bundle_call(R, ids, T, joints, twists, 4, nt.INTR2)
+    else:
+        R, ids, _ = nt.sil_frames_with(pairs)
+        sd2 = np.ascontiguousarray(np.broadcast_to(sref.mask_distance(nt.disc_mask(nt.H2, nt.W2, nt.SIL2_DISC)[None], nt.SIL2_RADIUS)[0], R.shape))
+        want = sref.normal_equations(R, ids, sd2, 6, nt.INTR2, joints, twists, nt.SIL2_RADIUS)[0]
+        rc, got = sil_call(R, ids, sd2, joints, twists, 6, nt.INTR2, nt.SIL2_RADIUS)
+    assert rc == 0 and len(R) == 3 and R.shape[1] * R.shape[2] > 2048
+    assert (want[:, 2] == 2).all()
+    _same(got, want, f"{kernel}, three frames of two workgroups")
