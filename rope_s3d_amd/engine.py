@@ -231,6 +231,11 @@ def load_library(path: str = None):
     return lib
 
 
+def _dp(t):
+    """A torch tensor's storage as a void pointer."""
+    return C.c_void_p(t.data_ptr())
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -573,6 +578,23 @@ class Engine:
             raise EngineError(f"rope_depth_holes failed ({rc}): N <= 65535 planes, dilations and connection_factor at most 32")
         return depth_t
 
+    def _planes(self, named):
+        """named: (name, tensor, torch dtype by name, or a tuple of names) per plane stack.  Every one a contiguous (N, H, W) tensor of
+        its dtype on this engine's device and of the first one's shape, or ValueError -> (N, H, W)."""
+        import torch
+        shape = None
+        for name, t, dt in named:
+            dts, text = (dt, ' or '.join(dt)) if isinstance(dt, tuple) else ((dt,), f"torch.{dt}")
+            if not isinstance(t, torch.Tensor) or t.dtype not in [getattr(torch, d) for d in dts] or t.dim() != 3 or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous (N, H, W) {text} tensor")
+            if t.device.type != 'cuda' or t.device.index != self.device:
+                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
+            if shape is None:
+                shape = tuple(t.shape)
+            elif tuple(t.shape) != shape:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {shape}")
+        return shape
+
     def shade_frames(self, depth_t, ids_t, params, intr, n_links: int, backgrounds=None, frame0: int = 0, seed: int = 0, depth_out=True,
                      out=None):
         """rope_shade_frames: the N renders depth_t (N, H, W) float32 / ids_t (N, H, W) uint8 (render_batch_device's, on this engine's
@@ -584,13 +606,8 @@ class Engine:
         -> (bgr (N, H, W, 3) uint8, depth with bg_depth behind the robot (N, H, W) float32 or None).
         The arithmetic is the contract of include/rope_s3d.h; tests/shade_ref.py restates it in numpy."""
         import torch
+        N, H, W = self._planes((('depth', depth_t, 'float32'), ('ids', ids_t, 'uint8')))
         dev = depth_t.device
-        for name, t, dt in (('depth', depth_t, torch.float32), ('ids', ids_t, torch.uint8)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous() or t.shape != depth_t.shape:
-                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
-            if t.device.type != 'cuda' or t.device.index != self.device:
-                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
-        N, H, W = depth_t.shape
         params = np.ascontiguousarray(params, SHADE_DTYPE).reshape(-1)
         if len(params) != N:
             raise ValueError(f"{len(params)} parameter records for {N} frames")
@@ -631,15 +648,7 @@ class Engine:
         render_ids (N, H, W) uint8 are torch tensors on this engine's device (render_batch_device's); the kernel runs on torch's
         current stream and the sums are waited for here."""
         import torch
-        for name, t, dt in (('render_depth', render_depth, torch.float32), ('render_ids', render_ids, torch.uint8),
-                            ('frame_depth', frame_depth, torch.float32)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous():
-                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
-            if t.device.type != 'cuda' or t.device.index != self.device:
-                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
-            if t.shape != render_depth.shape:
-                raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {tuple(render_depth.shape)}")
-        N, H, W = render_depth.shape
+        N, H, W = self._planes((('render_depth', render_depth, 'float32'), ('render_ids', render_ids, 'uint8'), ('frame_depth', frame_depth, 'float32')))
         if N == 0:
             return np.zeros((0, AGREE_WORDS), np.uint64)
         dev = render_depth.device
@@ -664,8 +673,9 @@ class Engine:
         (render_batch_device's); joints (N, n_joints, 6) float64, a numpy array or a tensor: unit axis and a point on the axis per
         joint, in camera axes (x right, y down, z forward); intr: (fx, fy, cx, cy).  The kernels run on torch's current stream and
         the sums are waited for here.  The same planes give the same bytes from run to run and however a batch is cut."""
-        return self._normal_equations('rope_pose_normal_equations', render_depth, render_ids, frame_depth, joints, 'joints',
-                                      'axis and a point on it per joint', n_links, clip, intr)
+        return self._normal_equations('rope_pose_normal_equations', self._lib.rope_pose_normal_workspace, NEQ_WORDS, render_depth, render_ids,
+                                      ('frame_depth', frame_depth, 'float32'), [('joints', joints, 'axis and a point on it per joint')],
+                                      n_links, float(clip), f"clip {clip} (finite, positive)", intr)
 
     def camera_normal_equations(self, render_depth, render_ids, frame_depth, twists, n_links: int, clip: float, intr) -> np.ndarray:
         """rope_camera_normal_equations: pose_normal_equations with respect to the camera pose -> (N, 32) float64 with the same
@@ -673,8 +683,9 @@ class Engine:
         camera axes; a surface point P moves by w x P + v per unit of the column, and EVERY drawn link moves with every column,
         link 0 too (prediction/refinement.py: camera_twists).  Columns from n_cols on are exactly zero in [4..30].  Everything
         else — the planes, intr, the stream, determinism, the empty batch — is pose_normal_equations'."""
-        return self._normal_equations('rope_camera_normal_equations', render_depth, render_ids, frame_depth, twists, 'twists',
-                                      'angular and linear part per column', n_links, clip, intr)
+        return self._normal_equations('rope_camera_normal_equations', self._lib.rope_pose_normal_workspace, NEQ_WORDS, render_depth, render_ids,
+                                      ('frame_depth', frame_depth, 'float32'), [('twists', twists, 'angular and linear part per column')],
+                                      n_links, float(clip), f"clip {clip} (finite, positive)", intr)
 
     def bundle_normal_equations(self, render_depth, render_ids, frame_depth, joint_axes, twists, n_links: int, clip: float, intr) -> np.ndarray:
         """rope_bundle_normal_equations: the joints' and the camera's columns in ONE system of twelve slots -> (N, 96) float64, per
@@ -683,46 +694,9 @@ class Engine:
         (camera_normal_equations'), and every drawn link is an inlier, the base too (include/rope_s3d.h).  joint_axes
         (N, n_joints, 6) and twists (N, n_cols, 6) float64 as those two calls take them; either may be None (no such columns), not
         both.  Everything else — the planes, intr, the stream, determinism, the empty batch — is pose_normal_equations'."""
-        import torch
-        for name, t, dt in (('render_depth', render_depth, torch.float32), ('render_ids', render_ids, torch.uint8),
-                            ('frame_depth', frame_depth, torch.float32)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous():
-                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
-            if t.device.type != 'cuda' or t.device.index != self.device:
-                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
-            if t.shape != render_depth.shape:
-                raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {tuple(render_depth.shape)}")
-        N, H, W = render_depth.shape
-        dev = render_depth.device
-        if joint_axes is None and twists is None:
-            raise ValueError("joint_axes and twists: at least one of them")
-        cols = []
-        for name, c, what in (('joint_axes', joint_axes, 'axis and a point on it per joint'), ('twists', twists, 'angular and linear part per column')):
-            if c is not None and not isinstance(c, torch.Tensor):
-                c = torch.from_numpy(np.ascontiguousarray(c, np.float64))
-            if c is not None and (c.dtype != torch.float64 or c.dim() != 3 or c.shape[0] != N or c.shape[2] != 6):
-                raise ValueError(f"{name}: ({N}, n, 6) float64 — {what}, got {tuple(c.shape)} {c.dtype}")
-            cols.append(c)
-        counts = [0 if c is None else int(c.shape[1]) for c in cols]
-        if N == 0:
-            return np.zeros((0, BNEQ_WORDS), np.float64)
-        fx, fy, cx, cy = (float(v) for v in intr)
-        with torch.cuda.device(dev):
-            cols = [None if c is None or n == 0 else c.to(dev).contiguous() for c, n in zip(cols, counts)]
-            ptrs = [None if c is None else C.c_void_p(c.data_ptr()) for c in cols]
-            out = torch.empty((N, BNEQ_WORDS), dtype=torch.float64, device=dev)
-            work = torch.empty(max(1, self._lib.rope_bundle_normal_workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
-            rc = self._lib.rope_bundle_normal_equations(C.c_void_p(render_depth.data_ptr()), C.c_void_p(render_ids.data_ptr()),
-                                                        C.c_void_p(frame_depth.data_ptr()), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
-                                                        ptrs[0], counts[0], ptrs[1], counts[1], float(clip), C.c_void_p(out.data_ptr()),
-                                                        C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc == -1:
-                raise ValueError(f"rope_bundle_normal_equations refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), n_links "
-                                 f"{n_links} (1 .. 6), {counts[0]} joints and {counts[1]} twists (0 .. 6 each, not both 0), clip {clip} (finite, "
-                                 f"positive), intrinsics {(fx, fy, cx, cy)}")
-            if rc:
-                raise EngineError(f"rope_bundle_normal_equations failed ({rc})")
-            return out.cpu().numpy()
+        return self._normal_equations('rope_bundle_normal_equations', self._lib.rope_bundle_normal_workspace, BNEQ_WORDS, render_depth, render_ids,
+                                      ('frame_depth', frame_depth, 'float32'), self._two_blocks(joint_axes, twists), n_links, float(clip),
+                                      f"clip {clip} (finite, positive)", intr)
 
     def mask_distance(self, mask_t, radius: int):
         """rope_mask_distance: N masks -> (N, H, W) int32 on the device, the truncated signed squared distance of every pixel to
@@ -731,20 +705,14 @@ class Engine:
         contiguous torch tensor on this engine's device, non-zero = robot; radius 1 .. 16.  The kernel runs on torch's current
         stream and nothing is waited for."""
         import torch
-        if not isinstance(mask_t, torch.Tensor) or mask_t.dtype not in (torch.uint8, torch.bool) or mask_t.dim() != 3 or not mask_t.is_contiguous():
-            raise ValueError("mask: a contiguous (N, H, W) uint8 or bool tensor")
-        if mask_t.device.type != 'cuda' or mask_t.device.index != self.device:
-            raise ValueError(f"mask must be on cuda:{self.device}, got {mask_t.device}")
-        if int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
-            raise ValueError(f"radius: a whole number in 1 .. {SIL_MAX_RADIUS}, got {radius}")
-        N, H, W = mask_t.shape
+        N, H, W = self._planes([('mask', mask_t, ('uint8', 'bool'))])
+        radius = self._radius(radius)
         dev = mask_t.device
         with torch.cuda.device(dev):
             sd2 = torch.empty((N, H, W), dtype=torch.int32, device=dev)
             if N == 0:
                 return sd2
-            rc = self._lib.rope_mask_distance(C.c_void_p(mask_t.data_ptr()), int(N), int(H), int(W), int(radius), C.c_void_p(sd2.data_ptr()),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = self._lib.rope_mask_distance(_dp(mask_t), int(N), int(H), int(W), radius, _dp(sd2), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         if rc == -1:
             raise ValueError(f"rope_mask_distance refused its arguments: {N} planes of {H} x {W} (fewer than 2^31 pixels), radius {radius}")
         if rc:
@@ -759,81 +727,54 @@ class Engine:
         [95] 0 (include/rope_s3d.h).  sd2 (N, H, W) int32: mask_distance's of the same radius.  One-directional: the render's
         outline is measured against the mask.  Everything else — the renders, joint_axes, twists, intr, the stream, determinism,
         the empty batch — is bundle_normal_equations'."""
+        return self._normal_equations('rope_silhouette_normal_equations', self._lib.rope_silhouette_normal_workspace, BNEQ_WORDS, render_depth,
+                                      render_ids, ('sd2', sd2, 'int32'), self._two_blocks(joint_axes, twists), n_links, self._radius(radius),
+                                      f"radius {radius}", intr)
+
+    @staticmethod
+    def _radius(radius) -> int:
+        if int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
+            raise ValueError(f"radius: a whole number in 1 .. {SIL_MAX_RADIUS}, got {radius}")
+        return int(radius)
+
+    @staticmethod
+    def _two_blocks(joint_axes, twists):
+        return [('joint_axes', joint_axes, 'axis and a point on it per joint'), ('twists', twists, 'angular and linear part per column')]
+
+    def _normal_equations(self, entry: str, workspace, width: int, render_depth, render_ids, third, blocks, n_links: int, scalar, scalar_text: str,
+                          intr) -> np.ndarray:
+        """The checks, the buffers and the call behind the four normal-equation entries.  workspace: the entry's scratch query;
+        width: the words a frame gets (32 or 96); third: (name, tensor, dtype) of the planes the renders are held against; blocks:
+        one or two (name, columns, what they are), columns (N, n, 6) float64 or None — not all None; scalar: what the entry takes
+        after the columns (clip or radius), checked and converted by the caller, and scalar_text its part of the refusal."""
         import torch
-        for name, t, dt in (('render_depth', render_depth, torch.float32), ('render_ids', render_ids, torch.uint8), ('sd2', sd2, torch.int32)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous():
-                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
-            if t.device.type != 'cuda' or t.device.index != self.device:
-                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
-            if t.shape != render_depth.shape:
-                raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {tuple(render_depth.shape)}")
-        N, H, W = render_depth.shape
+        N, H, W = self._planes((('render_depth', render_depth, 'float32'), ('render_ids', render_ids, 'uint8'), third))
         dev = render_depth.device
-        if joint_axes is None and twists is None:
-            raise ValueError("joint_axes and twists: at least one of them")
+        if all(c is None for _, c, _ in blocks):
+            raise ValueError(f"{' and '.join(name for name, _, _ in blocks)}: at least one of them" if len(blocks) > 1 else f"{blocks[0][0]}: not None")
         cols = []
-        for name, c, what in (('joint_axes', joint_axes, 'axis and a point on it per joint'), ('twists', twists, 'angular and linear part per column')):
+        for name, c, what in blocks:
             if c is not None and not isinstance(c, torch.Tensor):
                 c = torch.from_numpy(np.ascontiguousarray(c, np.float64))
             if c is not None and (c.dtype != torch.float64 or c.dim() != 3 or c.shape[0] != N or c.shape[2] != 6):
                 raise ValueError(f"{name}: ({N}, n, 6) float64 — {what}, got {tuple(c.shape)} {c.dtype}")
             cols.append(c)
         counts = [0 if c is None else int(c.shape[1]) for c in cols]
-        if int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
-            raise ValueError(f"radius: a whole number in 1 .. {SIL_MAX_RADIUS}, got {radius}")
         if N == 0:
-            return np.zeros((0, BNEQ_WORDS), np.float64)
+            return np.zeros((0, width), np.float64)
         fx, fy, cx, cy = (float(v) for v in intr)
         with torch.cuda.device(dev):
             cols = [None if c is None or n == 0 else c.to(dev).contiguous() for c, n in zip(cols, counts)]
-            ptrs = [None if c is None else C.c_void_p(c.data_ptr()) for c in cols]
-            out = torch.empty((N, BNEQ_WORDS), dtype=torch.float64, device=dev)
-            work = torch.empty(max(1, self._lib.rope_silhouette_normal_workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
-            rc = self._lib.rope_silhouette_normal_equations(C.c_void_p(render_depth.data_ptr()), C.c_void_p(render_ids.data_ptr()),
-                                                            C.c_void_p(sd2.data_ptr()), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
-                                                            ptrs[0], counts[0], ptrs[1], counts[1], int(radius), C.c_void_p(out.data_ptr()),
-                                                            C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            out = torch.empty((N, width), dtype=torch.float64, device=dev)
+            work = torch.empty(max(1, workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
+            rc = getattr(self._lib, entry)(_dp(render_depth), _dp(render_ids), _dp(third[1]), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
+                                           *(a for c, n in zip(cols, counts) for a in (None if c is None else _dp(c), n)), scalar, _dp(out), _dp(work),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
             if rc == -1:
-                raise ValueError(f"rope_silhouette_normal_equations refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), "
-                                 f"n_links {n_links} (1 .. 6), {counts[0]} joints and {counts[1]} twists (0 .. 6 each, not both 0), radius "
-                                 f"{radius}, intrinsics {(fx, fy, cx, cy)}")
-            if rc:
-                raise EngineError(f"rope_silhouette_normal_equations failed ({rc})")
-            return out.cpu().numpy()
-
-    def _normal_equations(self, entry: str, render_depth, render_ids, frame_depth, columns, col_name: str, col_what: str, n_links: int,
-                          clip: float, intr) -> np.ndarray:
-        """The checks, the buffers and the call that rope_pose_normal_equations and rope_camera_normal_equations share."""
-        import torch
-        for name, t, dt in (('render_depth', render_depth, torch.float32), ('render_ids', render_ids, torch.uint8),
-                            ('frame_depth', frame_depth, torch.float32)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 3 or not t.is_contiguous():
-                raise ValueError(f"{name}: a contiguous (N, H, W) {dt} tensor")
-            if t.device.type != 'cuda' or t.device.index != self.device:
-                raise ValueError(f"{name} must be on cuda:{self.device}, got {t.device}")
-            if t.shape != render_depth.shape:
-                raise ValueError(f"{name}: shape {tuple(t.shape)}, the renders are {tuple(render_depth.shape)}")
-        N, H, W = render_depth.shape
-        dev = render_depth.device
-        if not isinstance(columns, torch.Tensor):
-            columns = torch.from_numpy(np.ascontiguousarray(columns, np.float64))
-        if columns.dtype != torch.float64 or columns.dim() != 3 or columns.shape[0] != N or columns.shape[2] != 6:
-            raise ValueError(f"{col_name}: ({N}, n, 6) float64 — {col_what}, got {tuple(columns.shape)} {columns.dtype}")
-        n_columns = int(columns.shape[1])
-        if N == 0:
-            return np.zeros((0, NEQ_WORDS), np.float64)
-        fx, fy, cx, cy = (float(v) for v in intr)
-        with torch.cuda.device(dev):
-            columns = columns.to(dev).contiguous()
-            out = torch.empty((N, NEQ_WORDS), dtype=torch.float64, device=dev)
-            work = torch.empty(max(1, self._lib.rope_pose_normal_workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
-            rc = getattr(self._lib, entry)(C.c_void_p(render_depth.data_ptr()), C.c_void_p(render_ids.data_ptr()),
-                                           C.c_void_p(frame_depth.data_ptr()), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
-                                           C.c_void_p(columns.data_ptr()), n_columns, float(clip), C.c_void_p(out.data_ptr()),
-                                           C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc == -1:
-                raise ValueError(f"{entry} refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), n_links {n_links} "
-                                 f"(1 .. 6), {n_columns} {col_name} (1 .. 6), clip {clip} (finite, positive), intrinsics {(fx, fy, cx, cy)}")
+                columns = f"{counts[0]} {blocks[0][0]} (1 .. 6)" if len(blocks) == 1 else \
+                    f"{counts[0]} joints and {counts[1]} twists (0 .. 6 each, not both 0)"
+                raise ValueError(f"{entry} refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), n_links {n_links} (1 .. 6), "
+                                 f"{columns}, {scalar_text}, intrinsics {(fx, fy, cx, cy)}")
             if rc:
                 raise EngineError(f"{entry} failed ({rc})")
             return out.cpu().numpy()
@@ -940,41 +881,51 @@ class Engine:
         -> dict(angles (N, 6), var (N, 6) — formal_sigma squared —, cost_before, cost_after, inliers (N,) float64, steps (N,) int32
         [, words (N, 32) the final systems]).  Runs on the context's stream, after torch's current stream has finished with the
         frames, and is complete on return.  Like render_batch_device it takes the per-candidate buffers."""
+        mask, limits = self._active_mask(active_mask), self._limits(limits)
+        fx, fy, cx, cy = (float(v) for v in intr)
+
+        def outputs(N):
+            out = dict(angles=np.empty((N, 6)), var=np.empty((N, 6)), cost_before=np.empty(N), cost_after=np.empty(N), inliers=np.empty(N),
+                       steps=np.empty(N, np.int32))
+            if want_words:
+                out['words'] = np.empty((N, NEQ_WORDS))
+            return out
+
+        return self._native_refine('rope_refine_poses', self.refine_workspace, q, frame_depth, camera_pose, iterations, damping, 0, outputs,
+                                   lambda q, pose, depth, N, work, o: self._lib.rope_refine_poses(
+                                       self._ctx, q, depth, N, pose, fx, fy, cx, cy, mask, _p(limits), float(clip), int(iterations), float(damping), work,
+                                       _p(o['angles']), _p(o['var']), _p(o['cost_before']), _p(o['cost_after']), _p(o['steps']), _p(o['inliers']),
+                                       _p(o.get('words'))))
+
+    def _native_refine(self, entry: str, workspace, q, frame_depth, camera_pose, iterations, damping, min_frames: int, outputs, call):
+        """What refine_poses and refine_bundle share: the checks of the poses, the frames and the loop's arguments, outputs(N) ->
+        the dict of host arrays the entry fills, the scratch, and call(q, pose, frames, N, scratch, outputs) -> the entry's code
+        once torch's current stream has finished with the frames.  Fewer than min_frames frames are refused; an empty batch
+        that is not returns its empty outputs without a call."""
         import torch
         q = np.ascontiguousarray(q, np.float64).reshape(-1, 6)
         N = len(q)
-        t = frame_depth
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
-            raise ValueError("frame_depth: a contiguous (N, H, W) torch.float32 tensor")
-        if t.device.type != 'cuda' or t.device.index != self.device:
-            raise ValueError(f"frame_depth must be on cuda:{self.device}, got {t.device}")
-        if tuple(t.shape) != (N, self.H, self.W):
-            raise ValueError(f"frame_depth: ({N}, {self.H}, {self.W}) as the poses and the camera, got {tuple(t.shape)}")
-        mask, limits = self._active_mask(active_mask), self._limits(limits)
+        self._planes([('frame_depth', frame_depth, 'float32')])
+        if N < min_frames or tuple(frame_depth.shape) != (N, self.H, self.W):
+            raise ValueError(f"frame_depth: ({N}, {self.H}, {self.W}) as the poses and the camera{f', N >= {min_frames}' if min_frames else ''}, "
+                             f"got {tuple(frame_depth.shape)}")
         pose = np.ascontiguousarray(camera_pose, np.float64).reshape(6)
         if int(iterations) != iterations or iterations < 0 or not (np.isfinite(damping) and damping >= 0):
             raise ValueError("iterations and damping must not be negative")
-        out = dict(angles=np.empty((N, 6)), var=np.empty((N, 6)), cost_before=np.empty(N), cost_after=np.empty(N), inliers=np.empty(N),
-                   steps=np.empty(N, np.int32))
-        if want_words:
-            out['words'] = np.empty((N, NEQ_WORDS))
+        out = outputs(N)
         if N == 0:
             return out
-        nbytes = self.refine_workspace(N)
+        nbytes = workspace(N)
         if nbytes == 0:
-            raise ValueError(f"rope_refine_poses takes no batch of {N} frames of {self.H} x {self.W} in one call")
-        fx, fy, cx, cy = (float(v) for v in intr)
-        dev = t.device
+            raise ValueError(f"{entry} takes no batch of {N} frames of {self.H} x {self.W} in one call")
+        dev = frame_depth.device
         with torch.cuda.device(dev):
             work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
             torch.cuda.current_stream(dev).synchronize()            # the frames are ready, and `work` is no longer anyone else's
-            rc = self._lib.rope_refine_poses(self._ctx, _p(q), C.c_void_p(t.data_ptr()), int(N), _p(pose), fx, fy, cx, cy, mask, _p(limits),
-                                             float(clip), int(iterations), float(damping), C.c_void_p(work.data_ptr()), _p(out['angles']),
-                                             _p(out['var']), _p(out['cost_before']), _p(out['cost_after']), _p(out['steps']), _p(out['inliers']),
-                                             _p(out.get('words')))
+            rc = call(_p(q), _p(pose), _dp(frame_depth), int(N), _dp(work), out)
         if rc == -1:
-            raise ValueError(f"rope_refine_poses refused its arguments: {self._lib.rope_last_error(self._ctx).decode()}")
-        self._check(rc, 'rope_refine_poses')
+            raise ValueError(f"{entry} refused its arguments: {self._lib.rope_last_error(self._ctx).decode()}")
+        self._check(rc, entry)
         return out
 
     # -- the native camera and bundle polish (csrc/rope_bundle_polish.hip) ----------------------------
@@ -986,7 +937,7 @@ class Engine:
             tensors = [torch.empty(shape, dtype=torch.float64, device=dev) for shape in outs]
             if N > 0:
                 work = torch.empty(max(1, self._lib.rope_bundle_schur_workspace(int(N)) // 8), dtype=torch.float64, device=dev)
-                rc = call(C.c_void_p(work.data_ptr()), [C.c_void_p(t.data_ptr()) for t in tensors],
+                rc = call(_dp(work), [_dp(t) for t in tensors],
                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
                 if rc:
                     raise EngineError(f"{name} failed ({rc})")
@@ -1000,7 +951,7 @@ class Engine:
         if w.shape[0] == 0:
             return torch.zeros(BNEQ_WORDS, dtype=torch.float64, device=w.device)
         return self._bundle_call('rope_bundle_pool', w.shape[0], [(BNEQ_WORDS,)],
-                                 lambda work, o, s: self._lib.rope_bundle_pool(C.c_void_p(w.data_ptr()), int(w.shape[0]), o[0], s))[0]
+                                 lambda work, o, s: self._lib.rope_bundle_pool(_dp(w), int(w.shape[0]), o[0], s))[0]
 
     def bundle_schur_step(self, words, pooled, q, pose, lam: float, joint_mask: int, camera_mask: int, limits):
         """rope_bundle_schur_step: refinement.schur_step on the device, then pose + dc and clip(q + dq) -> (trial_q (N, 6),
@@ -1012,9 +963,8 @@ class Engine:
         p_t, q_t, pose_t = self._polish_tensor('pooled', pooled, None, BNEQ_WORDS), self._polish_tensor('q', q, 6, N), self._polish_tensor('pose', pose, None, 6)
         lam_t = torch.tensor([float(lam)], dtype=torch.float64, device=w.device)
         jm, cm, limits = self._active_mask(joint_mask), self._active_mask(camera_mask), self._limits(limits)
-        vp = lambda t: C.c_void_p(t.data_ptr())
         out = self._bundle_call('rope_bundle_schur_step', N, [(N, 6), (6,)], lambda work, o, s: self._lib.rope_bundle_schur_step(
-            vp(w), vp(p_t), vp(q_t), vp(pose_t), vp(lam_t), int(N), jm, cm, _p(limits), work, o[0], o[1], s))
+            _dp(w), _dp(p_t), _dp(q_t), _dp(pose_t), _dp(lam_t), int(N), jm, cm, _p(limits), work, o[0], o[1], s))
         return out[0], out[1]
 
     def bundle_schur_variance(self, words, pooled, joint_mask: int, camera_mask: int):
@@ -1024,9 +974,8 @@ class Engine:
         N = w.shape[0]
         p_t = self._polish_tensor('pooled', pooled, None, BNEQ_WORDS)
         jm, cm = self._active_mask(joint_mask), self._active_mask(camera_mask)
-        vp = lambda t: C.c_void_p(t.data_ptr())
         out = self._bundle_call('rope_bundle_schur_variance', N, [(N, 6), (6,)], lambda work, o, s: self._lib.rope_bundle_schur_variance(
-            vp(w), vp(p_t), int(N), jm, cm, work, o[0], o[1], s))
+            _dp(w), _dp(p_t), int(N), jm, cm, work, o[0], o[1], s))
         return out[0], out[1]
 
     @staticmethod
@@ -1045,9 +994,8 @@ class Engine:
         pose_t, off_t = self._polish_tensor('pose', pose, None, 6), self._polish_tensor('off', off, None, 6)
         lam_t = torch.tensor([float(lam)], dtype=torch.float64, device=p_t.device)
         sm, limits = self._slot_mask(slot_mask), self._limits(limits)
-        vp = lambda t: C.c_void_p(t.data_ptr())
         out = self._bundle_call('rope_bundle_columns_step', N, [(6,), (6,), (N, 6)], lambda work, o, s: self._lib.rope_bundle_columns_step(
-            vp(p_t), vp(lam_t), sm, vp(pose_t), vp(off_t), vp(q_t), int(N), _p(limits), o[0], o[1], o[2], s))
+            _dp(p_t), _dp(lam_t), sm, _dp(pose_t), _dp(off_t), _dp(q_t), int(N), _p(limits), o[0], o[1], o[2], s))
         return out[0], out[1], out[2]
 
     def bundle_columns_variance(self, pooled, slot_mask: int):
@@ -1055,7 +1003,7 @@ class Engine:
         p_t = self._polish_tensor('pooled', pooled, None, BNEQ_WORDS)
         sm = self._slot_mask(slot_mask)
         return self._bundle_call('rope_bundle_columns_variance', 1, [(12,)], lambda work, o, s: self._lib.rope_bundle_columns_variance(
-            C.c_void_p(p_t.data_ptr()), sm, o[0], s))[0]
+            _dp(p_t), sm, o[0], s))[0]
 
     def refine_bundle_workspace(self, n_frames: int) -> int:
         """rope_refine_bundle_workspace: the bytes of device scratch refine_bundle needs for n_frames frames; 0 for a batch one
@@ -1071,44 +1019,26 @@ class Engine:
         (fx, fy, cx, cy); znear, zfar those of set_camera.
         -> dict(pose (6,), angles (N, 6), offsets (6,) — nan in 'frame' mode —, var_pose (6,), var_joints ((N, 6) 'frame', (6,)
         'offset'), cost_before, cost_after, inliers (float), steps (int), frame_cost (N,) [, words (N, 96)]).  Complete on return."""
-        import torch
         if mode not in ('frame', 'offset'):
             raise ValueError(f"mode: 'frame' or 'offset', got {mode!r}")
-        q = np.ascontiguousarray(q, np.float64).reshape(-1, 6)
-        N = len(q)
-        t = frame_depth
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
-            raise ValueError("frame_depth: a contiguous (N, H, W) torch.float32 tensor")
-        if t.device.type != 'cuda' or t.device.index != self.device:
-            raise ValueError(f"frame_depth must be on cuda:{self.device}, got {t.device}")
-        if N < 1 or tuple(t.shape) != (N, self.H, self.W):
-            raise ValueError(f"frame_depth: ({N}, {self.H}, {self.W}) as the poses and the camera, N >= 1, got {tuple(t.shape)}")
         jm, cm, limits = self._active_mask(joint_mask), self._active_mask(camera_mask), self._limits(limits)
         if jm == 0 and cm == 0:
             raise ValueError("joint_mask and camera_mask: not both 0")
-        pose = np.ascontiguousarray(camera_pose, np.float64).reshape(6)
-        if int(iterations) != iterations or iterations < 0 or not (np.isfinite(damping) and damping >= 0):
-            raise ValueError("iterations and damping must not be negative")
         frame_mode = mode == 'frame'
-        o = dict(pose=np.empty(6), angles=np.empty((N, 6)), offsets=np.empty(6), var_pose=np.empty(6),
-                 var_joints=np.empty((N, 6) if frame_mode else 6), costs=np.empty(3), steps=np.zeros(1, np.int32), frame_cost=np.empty(N))
-        if want_words:
-            o['words'] = np.empty((N, BNEQ_WORDS))
-        nbytes = self.refine_bundle_workspace(N)
-        if nbytes == 0:
-            raise ValueError(f"rope_refine_bundle takes no batch of {N} frames of {self.H} x {self.W} in one call")
         fx, fy, cx, cy = (float(v) for v in intr)
-        dev = t.device
-        with torch.cuda.device(dev):
-            work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()            # the frames are ready, and `work` is no longer anyone else's
-            rc = self._lib.rope_refine_bundle(self._ctx, 0 if frame_mode else 1, _p(pose), _p(q), C.c_void_p(t.data_ptr()), int(N), fx, fy, cx, cy,
-                                              float(znear), float(zfar), jm, cm, _p(limits), float(clip), int(iterations), float(damping),
-                                              C.c_void_p(work.data_ptr()), _p(o['pose']), _p(o['angles']), _p(o['offsets']), _p(o['var_pose']),
-                                              _p(o['var_joints']), _p(o['costs']), _p(o['steps']), _p(o['frame_cost']), _p(o.get('words')))
-        if rc == -1:
-            raise ValueError(f"rope_refine_bundle refused its arguments: {self._lib.rope_last_error(self._ctx).decode()}")
-        self._check(rc, 'rope_refine_bundle')
+
+        def outputs(N):
+            o = dict(pose=np.empty(6), angles=np.empty((N, 6)), offsets=np.empty(6), var_pose=np.empty(6),
+                     var_joints=np.empty((N, 6) if frame_mode else 6), costs=np.empty(3), steps=np.zeros(1, np.int32), frame_cost=np.empty(N))
+            if want_words:
+                o['words'] = np.empty((N, BNEQ_WORDS))
+            return o
+
+        o = self._native_refine('rope_refine_bundle', self.refine_bundle_workspace, q, frame_depth, camera_pose, iterations, damping, 1, outputs,
+                                lambda q, pose, depth, N, work, o: self._lib.rope_refine_bundle(
+                                    self._ctx, 0 if frame_mode else 1, pose, q, depth, N, fx, fy, cx, cy, float(znear), float(zfar), jm, cm, _p(limits),
+                                    float(clip), int(iterations), float(damping), work, _p(o['pose']), _p(o['angles']), _p(o['offsets']),
+                                    _p(o['var_pose']), _p(o['var_joints']), _p(o['costs']), _p(o['steps']), _p(o['frame_cost']), _p(o.get('words'))))
         costs = o.pop('costs')
         o.update(cost_before=float(costs[0]), cost_after=float(costs[1]), inliers=float(costs[2]), steps=int(o['steps'][0]))
         return o

@@ -41,29 +41,130 @@ class RefineResult:
                               ('angles', 'sigma', 'cost_before', 'cost_after', 'steps_taken', 'inliers')))
 
 
+def _intr4(intr):
+    return intr.fx, intr.fy, intr.cx, intr.cy
+
+
+def _check_loop_args(clip, iterations, damping):
+    if not (np.isfinite(clip) and clip > 0):
+        raise ValueError(f"clip must be finite and positive, got {clip}")
+    if iterations < 0 or not (np.isfinite(damping) and damping >= 0):
+        raise ValueError("iterations and damping must not be negative")
+
+
+def _active_params(do_params):
+    do_params = np.asarray(do_params, bool).reshape(-1)
+    if len(do_params) != 6:
+        raise ValueError("do_params: six flags, one per pose parameter")
+    return [int(k) for k in np.flatnonzero(do_params)]
+
+
+def _stage_depth(engine, depth, N):
+    """depth (N, H, W), a numpy array or a torch tensor on the host or the device -> a contiguous float32 tensor on the engine's device."""
+    import torch
+    if not isinstance(depth, torch.Tensor):
+        depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32))
+    depth_t = depth.to(device=torch.device('cuda', engine.device), dtype=torch.float32).contiguous()
+    if depth_t.dim() != 3 or depth_t.shape[0] != N:
+        raise ValueError(f"depth: ({N}, H, W), got {tuple(depth_t.shape)}")
+    return depth_t
+
+
+def _camera_axes(pose):
+    """[x, y, z, a3, a4, a5] -> (Rwc, tc) of the kernel's camera axes X_c = Rwc (X_w - tc): x right, y down, z forward."""
+    M = camera_pose_matrix(np.asarray(pose, np.float64).reshape(6))    # camera to world; the GL camera looks along -z with y up
+    return np.diag([1.0, -1.0, -1.0]) @ M[:3, :3].T, M[:3, 3].copy()
+
+
+class _DrawsEveryLink:
+    @property
+    def n_links(self) -> int:
+        """Links the refiner draws: all that are ever drawn, whatever limit the renderer stands at (setMaxParts)."""
+        return min(int(self.engine.n_links), NUM_RENDER_LINKS)
+
+
+def _levenberg_loop(evaluate, propose, state, iterations: int, damping: float):
+    """The Levenberg loop with ONE damping and ONE cost: evaluate(state) -> (payload, cost) and propose(state, payload, lam) ->
+    the trial state.  A trial is kept only when its cost is strictly smaller; refused, it multiplies lam by 10.
+    -> (the state held at the end, its payload, the start's payload, accepted steps)."""
+    lam = damping
+    payload, cost = evaluate(state)
+    first, steps = payload, 0
+    for _ in range(iterations):
+        trial = propose(state, payload, lam)
+        p_t, c_t = evaluate(trial)
+        if c_t < cost:                                                  # strictly smaller, or everything is put back
+            state, payload, cost, steps = trial, p_t, c_t, steps + 1
+        else:
+            lam *= 10.0
+    return state, payload, first, steps
+
+
+def _unpack(words: np.ndarray, slots: int):
+    """[4 ..] of a system of `slots` unknowns -> (A (slots, slots) = J^T J from its upper triangle, g (slots,) = J^T r)."""
+    A = np.zeros((slots, slots))
+    A[np.triu_indices(slots)] = words[4 + slots:4 + slots + slots * (slots + 1) // 2]
+    return A + np.triu(A, 1).T, np.array(words[4:4 + slots], np.float64)
+
+
+def _pool(words: np.ndarray, width: int) -> np.ndarray:
+    """(N, width) -> (width,): the frames' words added in frame order, one float64 addition after the other (no pairwise summation:
+    the order is part of what tests/camera_refine_ref.py and tests/bundle_ref.py restate)."""
+    pooled = np.zeros(width)
+    for w in np.asarray(words, np.float64).reshape(-1, width):
+        pooled = pooled + w
+    return pooled
+
+
+def _solve_finite(M, rhs):
+    """np.linalg.solve; None for a singular matrix or a solution that is not finite."""
+    try:
+        x = np.linalg.solve(M, rhs)
+    except np.linalg.LinAlgError:
+        return None
+    return x if np.isfinite(x).all() else None
+
+
+def _step(A, g, active, lam: float) -> np.ndarray:
+    """(A + lam diag A) d = -g on the active unknowns whose diagonal entry is positive -> d; zero for every other unknown, and zero
+    altogether when the system is singular or its solution not finite."""
+    idx = [j for j in active if A[j, j] > 0]
+    d = np.zeros(len(g))
+    if idx:
+        S = A[np.ix_(idx, idx)]
+        sol = _solve_finite(S + lam * np.diag(np.diag(S)), -g[idx])
+        if sol is not None:
+            d[idx] = sol
+    return d
+
+
+def _sigma(A, inliers: float, r2: float, active) -> np.ndarray:
+    """sqrt(s^2 diag(A^-1)) with s^2 = r2 / (inliers - p), p the active unknowns with a positive diagonal.  inf for an active unknown
+    with a zero diagonal, for fewer inliers than p + 1 and for a singular A; nan for what is not active."""
+    out = np.full(len(A), np.nan)
+    out[list(active)] = np.inf
+    idx = [j for j in active if A[j, j] > 0]
+    p = len(idx)
+    if p == 0 or inliers < p + 1:
+        return out
+    cov = _solve_finite(A[np.ix_(idx, idx)], np.eye(p))                 # LAPACK's gesv on the identity, as np.linalg.inv
+    if cov is None:
+        return out
+    var = (r2 / (inliers - p)) * np.diag(cov)
+    if np.isfinite(var).all() and (var >= 0).all():
+        out[idx] = np.sqrt(var)
+    return out
+
+
 def unpack_normal_equations(words: np.ndarray):
     """One frame's 32 words -> (A (6, 6) = J^T J, g (6,) = J^T r)."""
-    A = np.zeros((6, 6))
-    A[np.triu_indices(6)] = words[10:31]
-    return A + np.triu(A, 1).T, np.array(words[4:10], np.float64)
+    return _unpack(words, 6)
 
 
 def levenberg_step(words: np.ndarray, active, lam: float) -> np.ndarray:
     """(A + lam diag A) d = -g on the active joints whose diagonal entry is positive -> d (6,); zero for every other joint, and
     zero altogether when the system is singular."""
-    A, g = unpack_normal_equations(words)
-    idx = [j for j in active if A[j, j] > 0]
-    d = np.zeros(6)
-    if not idx:
-        return d
-    S = A[np.ix_(idx, idx)]
-    try:
-        sol = np.linalg.solve(S + lam * np.diag(np.diag(S)), -g[idx])
-    except np.linalg.LinAlgError:
-        return d
-    if np.isfinite(sol).all():
-        d[idx] = sol
-    return d
+    return _step(*unpack_normal_equations(words), active, lam)
 
 
 def formal_sigma(words: np.ndarray, active) -> np.ndarray:
@@ -72,21 +173,7 @@ def formal_sigma(words: np.ndarray, active) -> np.ndarray:
     that are not active.  This is a FORMAL sigma: it treats the pixels as independent measurements, and neighbouring pixels of a
     depth frame are not, so it is optimistic — good for telling an observable joint from a hidden one and for ranking, not an
     error bar to be taken at its face value."""
-    A, _ = unpack_normal_equations(words)
-    out = np.full(6, np.nan)
-    out[list(active)] = np.inf
-    idx = [j for j in active if A[j, j] > 0]
-    p = len(idx)
-    if p == 0 or words[2] < p + 1:
-        return out
-    try:
-        cov = np.linalg.inv(A[np.ix_(idx, idx)])
-    except np.linalg.LinAlgError:
-        return out
-    var = (words[3] / (words[2] - p)) * np.diag(cov)
-    if np.isfinite(var).all() and (var >= 0).all():
-        out[idx] = np.sqrt(var)
-    return out
+    return _sigma(unpack_normal_equations(words)[0], words[2], words[3], active)
 
 
 def mean_cost(words: np.ndarray) -> np.ndarray:
@@ -116,7 +203,7 @@ def joint_axes_camera(fk, Rwc, tc, angles: np.ndarray) -> np.ndarray:
     return out
 
 
-class PoseRefiner:
+class PoseRefiner(_DrawsEveryLink):
     """renderer_or_engine  a simulation.render.Renderer (its camera is moved to camera_pose here unless it stands there) — or an
                         Engine on which robot and camera are set already, all links rendered
     camera_pose         [x, y, z, a3, a4, a5] as the Predictor takes it
@@ -134,10 +221,7 @@ class PoseRefiner:
 
     def __init__(self, renderer_or_engine, camera_pose, intrinsics, do_angles: str = 'SLU', clip: float = 2 ** -5, iterations: int = 5,
                  damping: float = 1e-3, native: bool = False):
-        if not (np.isfinite(clip) and clip > 0):
-            raise ValueError(f"clip must be finite and positive, got {clip}")
-        if iterations < 0 or not (np.isfinite(damping) and damping >= 0):
-            raise ValueError("iterations and damping must not be negative")
+        _check_loop_args(clip, iterations, damping)
         self.renderer = renderer_or_engine if hasattr(renderer_or_engine, 'render_ids_batch_device') else None
         self.engine = self.renderer.engine if self.renderer is not None else renderer_or_engine
         self.intrinsics = intrinsics
@@ -154,14 +238,7 @@ class PoseRefiner:
         # (the Predictor's lookup table)
         if self.renderer is not None and not np.array_equal(getattr(self.renderer, '_camera_pose6', None), self.camera_pose):
             self.renderer.setCameraPose(self.camera_pose)
-        M = camera_pose_matrix(self.camera_pose)                       # camera to world; the GL camera looks along -z with y up
-        flip = np.diag([1.0, -1.0, -1.0])                              # to the kernel's axes: x right, y down, z forward
-        self._Rwc, self._tc = flip @ M[:3, :3].T, M[:3, 3].copy()
-
-    @property
-    def n_links(self) -> int:
-        """Links the refiner draws: all that are ever drawn, whatever limit the renderer stands at (setMaxParts)."""
-        return min(int(self.engine.n_links), NUM_RENDER_LINKS)
+        self._Rwc, self._tc = _camera_axes(self.camera_pose)
 
     def joint_axes(self, angles: np.ndarray) -> np.ndarray:
         """(N, 6) angles -> (N, 6, 6): per joint its unit axis and a point on it, in camera axes, at those angles."""
@@ -173,28 +250,21 @@ class PoseRefiner:
     def equations(self, angles: np.ndarray, depth_t) -> np.ndarray:
         """One render and one kernel call: the normal equations of the poses `angles` against the frames depth_t (a float32 tensor
         on the engine's device) -> (N, 32)."""
-        intr = self.intrinsics
         rd, ri = self._render(angles)
-        return self.engine.pose_normal_equations(rd, ri, depth_t, self.joint_axes(angles), self.n_links, self.clip,
-                                                 (intr.fx, intr.fy, intr.cx, intr.cy))
+        return self.engine.pose_normal_equations(rd, ri, depth_t, self.joint_axes(angles), self.n_links, self.clip, _intr4(self.intrinsics))
 
     def refine(self, angles, depth) -> RefineResult:
         """angles (N, 6); depth (N, H, W) metres at the refiner's resolution, a numpy array or a torch tensor on the host or the
         device, 0 / NaN where nothing was measured -> RefineResult."""
-        import torch
         q = np.array(angles, np.float64).reshape(-1, 6)
         N = len(q)
         if N == 0:
             e = np.zeros(0)
             return RefineResult(q, np.zeros((0, 6)), e, e.copy(), np.zeros(0, np.int64), e.copy())
-        device = torch.device('cuda', self.engine.device)
-        if not isinstance(depth, torch.Tensor):
-            depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32))
-        depth_t = depth.to(device=device, dtype=torch.float32).contiguous()
-        if depth_t.dim() != 3 or depth_t.shape[0] != N:
-            raise ValueError(f"depth: ({N}, H, W), got {tuple(depth_t.shape)}")
+        depth_t = _stage_depth(self.engine, depth, N)
         if self.native:
             return self._refine_native(q, depth_t)
+        # _levenberg_loop's rule with a damping, a cost and a verdict PER FRAME, and all frames in one render: vectors, so its own loop
         lam = np.full(N, self.damping)
         words = self.equations(q, depth_t)
         cost = mean_cost(words)
@@ -210,15 +280,14 @@ class PoseRefiner:
             lam[~ok] *= 10.0
         return RefineResult(q, np.stack([formal_sigma(w, self.active) for w in words]), cost_before, cost, steps, words[:, 2].copy())
 
-
     def _refine_native(self, q: np.ndarray, depth_t) -> RefineResult:
         """refine through rope_refine_poses: one call per chunk of frames whose scratch fits NATIVE_WORK_BYTES."""
-        intr, N = self.intrinsics, len(q)
+        N = len(q)
         mask = sum(1 << j for j in self.active)
         chunk = max(1, min(N, self.NATIVE_WORK_BYTES // max(1, self.engine.refine_workspace(1))))
         parts = []
         for lo in range(0, N, chunk):
-            r = self.engine.refine_poses(q[lo:lo + chunk], depth_t[lo:lo + chunk], self.camera_pose, (intr.fx, intr.fy, intr.cx, intr.cy), mask,
+            r = self.engine.refine_poses(q[lo:lo + chunk], depth_t[lo:lo + chunk], self.camera_pose, _intr4(self.intrinsics), mask,
                                          self.limits, self.clip, self.iterations, self.damping)
             parts.append(RefineResult(r['angles'], np.sqrt(r['var']), r['cost_before'], r['cost_after'], r['steps'].astype(np.int64), r['inliers']))
         return parts[0] if len(parts) == 1 else RefineResult.concatenate(parts)
@@ -248,7 +317,7 @@ def camera_twists(pose6) -> np.ndarray:
       dX_c = -diag(1, -1, -1) R^T (a x (X_w - t)) = -(Rwc a) x X_c (diag(1, -1, -1) is a rotation, it goes through the cross
       product): w = -Rwc a, v = 0."""
     p = np.asarray(pose6, np.float64).reshape(6)
-    Rwc = np.diag([1.0, -1.0, -1.0]) @ camera_pose_matrix(p)[:3, :3].T
+    Rwc, _ = _camera_axes(p)
     yaw, pitch = p[5], p[3]
     cy, sy, cp, sp = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch)
     axis = {5: np.array([0.0, 0.0, 1.0]), 3: np.array([-sy, cy, 0.0]), 4: np.array([cy * cp, sy * cp, -sp])}      # z; Rz y; Rz Ry x
@@ -261,15 +330,17 @@ def camera_twists(pose6) -> np.ndarray:
 
 
 def pool_frames(words: np.ndarray) -> np.ndarray:
-    """(N, 32) -> (32,): the frames' words added in frame order, one float64 addition after the other (no pairwise summation: the
-    order is part of what tests/camera_refine_ref.py restates)."""
-    pooled = np.zeros(NEQ_WORDS)
-    for w in np.asarray(words, np.float64).reshape(-1, NEQ_WORDS):
-        pooled = pooled + w
-    return pooled
+    """(N, 32) -> (32,): the frames' words added in frame order (_pool)."""
+    return _pool(words, NEQ_WORDS)
 
 
-class CameraPoseRefiner:
+def _render_under(engine, intr, pose, angles, n_links):
+    """One render of the N frames' angles under the camera `pose`, which brings its own P V -> (depth, ids) on the device."""
+    from ..projection import camera_matrix
+    return engine.render_batch_device(angles, n_links, np.tile(camera_matrix(pose, intr)[None], (len(angles), 1, 1)))
+
+
+class CameraPoseRefiner(_DrawsEveryLink):
     """A continuous last step for a CAMERA pose seen in N frames at known joint angles, and how sure it is: PoseRefiner's loop
     with the six pose parameters as columns (camera_twists, rope_camera_normal_equations) and ONE system pooled over the frames.
 
@@ -281,31 +352,17 @@ class CameraPoseRefiner:
     clip, iterations, damping   as PoseRefiner's; damping is multiplied by 10 whenever a step is refused"""
 
     def __init__(self, renderer_or_engine, intrinsics, do_params=(True,) * 6, clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3):
-        if not (np.isfinite(clip) and clip > 0):
-            raise ValueError(f"clip must be finite and positive, got {clip}")
-        if iterations < 0 or not (np.isfinite(damping) and damping >= 0):
-            raise ValueError("iterations and damping must not be negative")
-        do_params = np.asarray(do_params, bool).reshape(-1)
-        if len(do_params) != 6:
-            raise ValueError("do_params: six flags, one per pose parameter")
+        _check_loop_args(clip, iterations, damping)
+        self.active = _active_params(do_params)
         self.engine = renderer_or_engine.engine if hasattr(renderer_or_engine, 'render_ids_batch_device') else renderer_or_engine
         self.intrinsics = intrinsics
-        self.active = [int(k) for k in np.flatnonzero(do_params)]
         self.clip, self.iterations, self.damping = float(clip), int(iterations), float(damping)
-
-    @property
-    def n_links(self) -> int:
-        return min(int(self.engine.n_links), NUM_RENDER_LINKS)
 
     def equations(self, pose, angles: np.ndarray, depth_t) -> np.ndarray:
         """One render of the N frames' angles under the camera `pose` and one kernel call -> (N, 32), per frame."""
-        from ..projection import camera_matrix
-        intr = self.intrinsics
-        N = len(angles)
-        PV = np.tile(camera_matrix(pose, intr)[None], (N, 1, 1))
-        rd, ri = self.engine.render_batch_device(angles, self.n_links, PV)
-        twists = np.tile(camera_twists(pose)[None], (N, 1, 1))
-        return self.engine.camera_normal_equations(rd, ri, depth_t, twists, self.n_links, self.clip, (intr.fx, intr.fy, intr.cx, intr.cy))
+        rd, ri = _render_under(self.engine, self.intrinsics, pose, angles, self.n_links)
+        twists = np.tile(camera_twists(pose)[None], (len(angles), 1, 1))
+        return self.engine.camera_normal_equations(rd, ri, depth_t, twists, self.n_links, self.clip, _intr4(self.intrinsics))
 
     def refine(self, camera_pose, angles, depth) -> CameraRefineResult:
         """camera_pose (6,); angles (N, 6) the robot's joint angles in the frames; depth (N, H, W) metres at the refiner's
@@ -314,7 +371,6 @@ class CameraPoseRefiner:
         sigma is formal_sigma's of the pooled system: it treats the pixels as independent measurements, and neighbouring pixels
         of a depth frame are not, so it is FORMAL and optimistic — good for telling a parameter the views pin down from one they
         do not (a camera seen head-on barely fixes its distance) and for ranking, not an error bar to be taken at face value."""
-        import torch
         pose = np.array(camera_pose, np.float64).reshape(6)
         q = np.ascontiguousarray(np.asarray(angles, np.float64).reshape(-1, 6))
         N = len(q)
@@ -322,27 +378,16 @@ class CameraPoseRefiner:
             sig = np.full(6, np.nan)
             sig[self.active] = np.inf
             return CameraRefineResult(pose, sig, np.inf, np.inf, 0, 0.0, np.zeros(0))
-        device = torch.device('cuda', self.engine.device)
-        if not isinstance(depth, torch.Tensor):
-            depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32))
-        depth_t = depth.to(device=device, dtype=torch.float32).contiguous()
-        if depth_t.dim() != 3 or depth_t.shape[0] != N:
-            raise ValueError(f"depth: ({N}, H, W), got {tuple(depth_t.shape)}")
-        lam = self.damping
-        words = self.equations(pose, q, depth_t)
-        pooled = pool_frames(words)
-        cost = float(mean_cost(pooled[None])[0])
-        cost_before, steps = cost, 0
-        for _ in range(self.iterations):
-            trial = pose + levenberg_step(pooled, self.active, lam)
-            w_t = self.equations(trial, q, depth_t)
-            p_t = pool_frames(w_t)
-            c_t = float(mean_cost(p_t[None])[0])
-            if c_t < cost:                                              # strictly smaller, or the pose is put back
-                pose, words, pooled, cost = trial, w_t, p_t, c_t
-                steps += 1
-            else:
-                lam *= 10.0
+        depth_t = _stage_depth(self.engine, depth, N)
+
+        def evaluate(pose):
+            words = self.equations(pose, q, depth_t)
+            pooled = pool_frames(words)
+            cost = float(mean_cost(pooled[None])[0])
+            return (words, pooled, cost), cost
+
+        pose, (words, pooled, cost), (_, _, cost_before), steps = _levenberg_loop(
+            evaluate, lambda pose, held, lam: pose + levenberg_step(held[1], self.active, lam), pose, self.iterations, self.damping)
         return CameraRefineResult(pose, formal_sigma(pooled, self.active), cost_before, cost, steps, float(pooled[2]), mean_cost(words))
 
 
@@ -374,26 +419,12 @@ class BundleRefineResult:
 
 def unpack_bundle(words: np.ndarray):
     """One frame's (or the pooled) 96 words -> (A (12, 12) = J^T J, g (12,) = J^T r); slots 0 .. 5 the joints, 6 .. 11 the camera."""
-    A = np.zeros((BNEQ_SLOTS, BNEQ_SLOTS))
-    A[np.triu_indices(BNEQ_SLOTS)] = words[16:94]
-    return A + np.triu(A, 1).T, np.array(words[4:16], np.float64)
+    return _unpack(words, BNEQ_SLOTS)
 
 
 def pool_bundle(words: np.ndarray) -> np.ndarray:
     """(N, 96) -> (96,): pool_frames for the bundle's words, added in frame order."""
-    pooled = np.zeros(BNEQ_WORDS)
-    for w in np.asarray(words, np.float64).reshape(-1, BNEQ_WORDS):
-        pooled = pooled + w
-    return pooled
-
-
-def _solve_finite(M, rhs):
-    """np.linalg.solve; None for a singular matrix or a solution that is not finite."""
-    try:
-        x = np.linalg.solve(M, rhs)
-    except np.linalg.LinAlgError:
-        return None
-    return x if np.isfinite(x).all() else None
+    return _pool(words, BNEQ_WORDS)
 
 
 def _arrow_blocks(words, active_j, active_c):
@@ -477,36 +508,15 @@ def schur_sigma(words: np.ndarray, active_j, active_c):
 
 def bundle_columns_step(pooled: np.ndarray, active, lam: float) -> np.ndarray:
     """levenberg_step's rule over the twelve slots of a pooled system -> (12,)."""
-    A, g = unpack_bundle(pooled)
-    idx = [c for c in active if A[c, c] > 0]
-    d = np.zeros(BNEQ_SLOTS)
-    if idx:
-        S = A[np.ix_(idx, idx)]
-        sol = _solve_finite(S + lam * np.diag(np.diag(S)), -g[idx])
-        if sol is not None:
-            d[idx] = sol
-    return d
+    return _step(*unpack_bundle(pooled), active, lam)
 
 
 def bundle_columns_sigma(pooled: np.ndarray, active) -> np.ndarray:
     """formal_sigma's rule over the twelve slots of a pooled system -> (12,)."""
-    A, _ = unpack_bundle(pooled)
-    out = np.full(BNEQ_SLOTS, np.nan)
-    out[list(active)] = np.inf
-    idx = [c for c in active if A[c, c] > 0]
-    p = len(idx)
-    if p == 0 or pooled[2] < p + 1:
-        return out
-    cov = _solve_finite(A[np.ix_(idx, idx)], np.eye(p))
-    if cov is None:
-        return out
-    var = (pooled[3] / (pooled[2] - p)) * np.diag(cov)
-    if np.isfinite(var).all() and (var >= 0).all():
-        out[idx] = np.sqrt(var)
-    return out
+    return _sigma(unpack_bundle(pooled)[0], pooled[2], pooled[3], active)
 
 
-class BundleRefiner:
+class BundleRefiner(_DrawsEveryLink):
     """Joint angles AND camera pose of N frames of one fixed camera polished in ONE Gauss-Newton / Levenberg system
     (rope_bundle_normal_equations, csrc/rope_bundle.hip): PoseRefiner takes the camera as exact and CameraPoseRefiner the angles,
     and each absorbs the other's error; here neither half is assumed, and the formal sigmas say what the views pin down then.
@@ -537,8 +547,7 @@ class BundleRefiner:
     def __init__(self, renderer_or_engine, intrinsics, do_angles: str = 'SLU', do_params=(True,) * 6, joints: str = 'frame',
                  clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3, silhouette: float = 0.0, radius: int = 8,
                  native: bool = False):
-        if not (np.isfinite(clip) and clip > 0):
-            raise ValueError(f"clip must be finite and positive, got {clip}")
+        _check_loop_args(clip, iterations, damping)
         if not (np.isfinite(silhouette) and silhouette >= 0):
             raise ValueError(f"silhouette: a finite weight, 0 or more, got {silhouette}")
         if native and silhouette > 0:
@@ -547,17 +556,12 @@ class BundleRefiner:
         if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
             raise ValueError(f"radius: a whole number of pixels in 1 .. {SIL_MAX_RADIUS}, got {radius}")
         self.silhouette, self.radius = float(silhouette), int(radius)
-        if iterations < 0 or not (np.isfinite(damping) and damping >= 0):
-            raise ValueError("iterations and damping must not be negative")
         if joints not in ('frame', 'offset'):
             raise ValueError(f"joints: 'frame' or 'offset', got {joints!r}")
-        do_params = np.asarray(do_params, bool).reshape(-1)
-        if len(do_params) != 6:
-            raise ValueError("do_params: six flags, one per pose parameter")
+        self.active_c = _active_params(do_params)
         self.engine = renderer_or_engine.engine if hasattr(renderer_or_engine, 'render_ids_batch_device') else renderer_or_engine
         self.intrinsics = intrinsics
         self.active_j = [int(j) for j in np.flatnonzero(str_to_arr(do_angles.upper()))]
-        self.active_c = [int(k) for k in np.flatnonzero(do_params)]
         if not self.active_j and not self.active_c:
             raise ValueError("nothing to refine: do_angles and do_params are both empty")
         self.mode = joints
@@ -565,27 +569,51 @@ class BundleRefiner:
         self.fk = ForwardKinematics()
         self.limits = np.asarray(self.fk.reader.joint_limits, np.float64)
 
-    @property
-    def n_links(self) -> int:
-        return min(int(self.engine.n_links), NUM_RENDER_LINKS)
-
     def joint_axes(self, pose, angles: np.ndarray) -> np.ndarray:
         """PoseRefiner.joint_axes under the camera `pose` -> (N, 6, 6)."""
-        M = camera_pose_matrix(np.asarray(pose, np.float64))
-        return joint_axes_camera(self.fk, np.diag([1.0, -1.0, -1.0]) @ M[:3, :3].T, M[:3, 3].copy(), angles)
+        return joint_axes_camera(self.fk, *_camera_axes(pose), angles)
+
+    def _equations(self, pose, angles: np.ndarray, depth_t, sd2_t):
+        """One render of the N frames' angles under the camera `pose`, the joint axes and the twists there, and one kernel call per
+        term that is given -> (depth words (N, 96) or None without depth_t, outline words (N, 96) or None without sd2_t)."""
+        angles = np.ascontiguousarray(angles, np.float64)
+        rd, ri = _render_under(self.engine, self.intrinsics, pose, angles, self.n_links)
+        axes = self.joint_axes(pose, angles) if self.active_j else None
+        twists = np.tile(camera_twists(pose)[None], (len(angles), 1, 1)) if self.active_c else None
+        intr4 = _intr4(self.intrinsics)
+        w_d = None if depth_t is None else self.engine.bundle_normal_equations(rd, ri, depth_t, axes, twists, self.n_links, self.clip, intr4)
+        w_s = None if sd2_t is None else self.engine.silhouette_normal_equations(rd, ri, sd2_t, axes, twists, self.n_links, self.radius, intr4)
+        return w_d, w_s
 
     def equations(self, pose, angles: np.ndarray, depth_t) -> np.ndarray:
         """One render of the N frames' angles under the camera `pose`, the joint axes and the twists there and one kernel call ->
         (N, 96), per frame."""
-        from ..projection import camera_matrix
-        intr = self.intrinsics
-        angles = np.ascontiguousarray(angles, np.float64)
-        N = len(angles)
-        PV = np.tile(camera_matrix(pose, intr)[None], (N, 1, 1))
-        rd, ri = self.engine.render_batch_device(angles, self.n_links, PV)
-        axes = self.joint_axes(pose, angles) if self.active_j else None
-        twists = np.tile(camera_twists(pose)[None], (N, 1, 1)) if self.active_c else None
-        return self.engine.bundle_normal_equations(rd, ri, depth_t, axes, twists, self.n_links, self.clip, (intr.fx, intr.fy, intr.cx, intr.cy))
+        return self._equations(pose, angles, depth_t, None)[0]
+
+    def equations_both(self, pose, angles: np.ndarray, depth_t, sd2_t):
+        """equations' render, axes and twists, handed to both kernels -> (depth words (N, 96) or None without depth_t, outline
+        words (N, 96))."""
+        return self._equations(pose, angles, depth_t, sd2_t)
+
+    def _result(self, pose, q, off, sigma_pose, sigma_joints, *fields) -> BundleRefineResult:
+        """The result in the refiner's mode: sigma_joints is sigma_angles (N, 6) in 'frame' mode and sigma_offsets (6,) in 'offset'
+        mode; fields are cost_before and what follows it."""
+        if self.mode == 'frame':
+            return BundleRefineResult(pose, q, np.full(6, np.nan), sigma_pose, sigma_joints, None, *fields)
+        return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), sigma_pose, None, sigma_joints, *fields)
+
+    def _stage_masks(self, mask, depth, N):
+        """refine's masks and, where given, depth of the same shape -> (depth_t or None, mask_distance's field of the masks)."""
+        import torch
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(mask))
+        if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 3 or mask.shape[0] != N:
+            raise ValueError(f"mask: ({N}, H, W) bool or uint8, got {tuple(mask.shape)} {mask.dtype}")
+        mask_t = mask.to(device=torch.device('cuda', self.engine.device)).ne(0).to(torch.uint8).contiguous()
+        depth_t = None if depth is None else _stage_depth(self.engine, depth, N)
+        if depth_t is not None and depth_t.shape != mask_t.shape:
+            raise ValueError(f"depth: {tuple(mask_t.shape)} as the masks, got {tuple(depth_t.shape)}")
+        return depth_t, self.engine.mask_distance(mask_t, self.radius)                  # once: the masks do not move
 
     def refine(self, camera_pose, angles, depth, mask=None) -> BundleRefineResult:
         """camera_pose (6,); angles (N, 6); depth (N, H, W) metres at the refiner's resolution, a numpy array or a torch tensor on
@@ -593,183 +621,90 @@ class BundleRefiner:
         only with silhouette > 0, and required then; depth may then be None (the outline alone, for colour-only frames).  The
         sigmas are FORMAL (schur_sigma, formal_sigma): good for telling what the views pin down and for ranking, not error bars to
         be taken at face value."""
-        import torch
-        if self.silhouette > 0:
-            return self._refine_with_silhouette(camera_pose, angles, depth, mask)
-        pose = np.array(camera_pose, np.float64).reshape(6)
-        q0 = np.ascontiguousarray(np.array(angles, np.float64).reshape(-1, 6))
-        N = len(q0)
-        frame_mode = self.mode == 'frame'
-        slots = self.active_j + [6 + k for k in self.active_c]
-        if N == 0:
-            sp, so = np.full(6, np.nan), np.full(6, np.nan)
-            sp[self.active_c], so[self.active_j] = np.inf, np.inf
-            return BundleRefineResult(pose, q0, np.full(6, np.nan) if frame_mode else np.zeros(6), sp, np.zeros((0, 6)) if frame_mode else None,
-                                      None if frame_mode else so, np.inf, np.inf, 0, 0.0, np.zeros(0))
-        device = torch.device('cuda', self.engine.device)
-        if not isinstance(depth, torch.Tensor):
-            depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32))
-        depth_t = depth.to(device=device, dtype=torch.float32).contiguous()
-        if depth_t.dim() != 3 or depth_t.shape[0] != N:
-            raise ValueError(f"depth: ({N}, H, W), got {tuple(depth_t.shape)}")
-        if self.native:
-            return self._refine_native(pose, q0, depth_t)
-        q, off = q0.copy(), np.zeros(6)
-        lam = self.damping
-        words = self.equations(pose, q, depth_t)
-        pooled = pool_bundle(words)
-        cost = float(mean_cost(pooled[None, :NEQ_WORDS])[0])
-        cost_before, steps = cost, 0
-        for _ in range(self.iterations):
-            if frame_mode:
-                dq, dc = schur_step(words, self.active_j, self.active_c, lam)
-                t_pose, t_off, t_q = pose + dc, off, np.clip(q + dq, self.limits[:, 0], self.limits[:, 1])
-            else:
-                d = bundle_columns_step(pooled, slots, lam)
-                t_pose, t_off = pose + d[6:], off + d[:6]
-                t_q = np.clip(q0 + t_off, self.limits[:, 0], self.limits[:, 1])
-            w_t = self.equations(t_pose, t_q, depth_t)
-            p_t = pool_bundle(w_t)
-            c_t = float(mean_cost(p_t[None, :NEQ_WORDS])[0])
-            if c_t < cost:                                              # strictly smaller, or everything is put back
-                pose, off, q, words, pooled, cost = t_pose, t_off, t_q, w_t, p_t, c_t
-                steps += 1
-            else:
-                lam *= 10.0
-        frame_cost = mean_cost(words[:, :NEQ_WORDS])
-        if frame_mode:
-            sq, sc = schur_sigma(words, self.active_j, self.active_c)
-            return BundleRefineResult(pose, q, np.full(6, np.nan), sc, sq, None, cost_before, cost, steps, float(pooled[2]), frame_cost)
-        s = bundle_columns_sigma(pooled, slots)
-        return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), s[6:], None, s[:6], cost_before, cost, steps,
-                                  float(pooled[2]), frame_cost)
-
-    def _refine_native(self, pose: np.ndarray, q0: np.ndarray, depth_t) -> BundleRefineResult:
-        """refine through rope_refine_bundle: ONE call, because one system spans all frames — a batch whose scratch one call does
-        not take is refused (Engine.refine_bundle_workspace says what a batch needs)."""
-        from ..constants import ZFAR, ZNEAR
-        intr = self.intrinsics
-        jm, cm = sum(1 << j for j in self.active_j), sum(1 << k for k in self.active_c)
-        r = self.engine.refine_bundle(self.mode, pose, q0, depth_t, (intr.fx, intr.fy, intr.cx, intr.cy), ZNEAR, ZFAR, jm, cm, self.limits,
-                                      self.clip, self.iterations, self.damping)
-        if self.mode == 'frame':
-            return BundleRefineResult(r['pose'], r['angles'], np.full(6, np.nan), np.sqrt(r['var_pose']), np.sqrt(r['var_joints']), None,
-                                      r['cost_before'], r['cost_after'], r['steps'], r['inliers'], r['frame_cost'])
-        return BundleRefineResult(r['pose'], r['angles'], np.where(np.isin(np.arange(6), self.active_j), r['offsets'], 0.0), np.sqrt(r['var_pose']),
-                                  None, np.sqrt(r['var_joints']), r['cost_before'], r['cost_after'], r['steps'], r['inliers'], r['frame_cost'])
-
-    # ------------------------------------------------------------------------------------------ depth and outline together
-    def equations_both(self, pose, angles: np.ndarray, depth_t, sd2_t):
-        """equations' render, axes and twists, handed to both kernels -> (depth words (N, 96) or None without depth_t, outline
-        words (N, 96))."""
-        from ..projection import camera_matrix
-        intr = self.intrinsics
-        angles = np.ascontiguousarray(angles, np.float64)
-        N = len(angles)
-        PV = np.tile(camera_matrix(pose, intr)[None], (N, 1, 1))
-        rd, ri = self.engine.render_batch_device(angles, self.n_links, PV)
-        axes = self.joint_axes(pose, angles) if self.active_j else None
-        twists = np.tile(camera_twists(pose)[None], (N, 1, 1)) if self.active_c else None
-        intr4 = (intr.fx, intr.fy, intr.cx, intr.cy)
-        w_d = None if depth_t is None else self.engine.bundle_normal_equations(rd, ri, depth_t, axes, twists, self.n_links, self.clip, intr4)
-        return w_d, self.engine.silhouette_normal_equations(rd, ri, sd2_t, axes, twists, self.n_links, self.radius, intr4)
-
-    def _refine_with_silhouette(self, camera_pose, angles, depth, mask) -> BundleRefineResult:
-        import torch
-        if mask is None:
+        outline = self.silhouette > 0
+        if outline and mask is None:
             raise ValueError("silhouette > 0: refine needs the frames' robot masks (mask=)")
         pose = np.array(camera_pose, np.float64).reshape(6)
         q0 = np.ascontiguousarray(np.array(angles, np.float64).reshape(-1, 6))
         N = len(q0)
         frame_mode = self.mode == 'frame'
         slots = self.active_j + [6 + k for k in self.active_c]
+        lo, hi = self.limits[:, 0], self.limits[:, 1]
         nan = float('nan')
         if N == 0:
             sp, so = np.full(6, np.nan), np.full(6, np.nan)
             sp[self.active_c], so[self.active_j] = np.inf, np.inf
-            return BundleRefineResult(pose, q0, np.full(6, np.nan) if frame_mode else np.zeros(6), sp, np.zeros((0, 6)) if frame_mode else None,
-                                      None if frame_mode else so, np.inf if depth is not None else nan, np.inf if depth is not None else nan, 0, 0.0,
-                                      np.zeros(0), np.inf, np.inf, 0.0)
-        device = torch.device('cuda', self.engine.device)
-        if not isinstance(mask, torch.Tensor):
-            mask = torch.from_numpy(np.ascontiguousarray(mask))
-        if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 3 or mask.shape[0] != N:
-            raise ValueError(f"mask: ({N}, H, W) bool or uint8, got {tuple(mask.shape)} {mask.dtype}")
-        mask_t = mask.to(device=device).ne(0).to(torch.uint8).contiguous()
-        depth_t = None
-        if depth is not None:
-            if not isinstance(depth, torch.Tensor):
-                depth = torch.from_numpy(np.ascontiguousarray(depth, np.float32))
-            depth_t = depth.to(device=device, dtype=torch.float32).contiguous()
-            if depth_t.dim() != 3 or depth_t.shape != mask_t.shape:
-                raise ValueError(f"depth: {tuple(mask_t.shape)} as the masks, got {tuple(depth_t.shape)}")
-        sd2_t = self.engine.mask_distance(mask_t, self.radius)                          # once: the masks do not move
+            c_d = np.inf if depth is not None or not outline else nan
+            return self._result(pose, q0, np.zeros(6), sp, np.zeros((0, 6)) if frame_mode else so, c_d, c_d, 0, 0.0, np.zeros(0),
+                                *((np.inf, np.inf, 0.0) if outline else ()))
+        depth_t, sd2_t = self._stage_masks(mask, depth, N) if outline else (_stage_depth(self.engine, depth, N), None)
+        if self.native:
+            return self._refine_native(pose, q0, depth_t)
         far = np.sqrt(self.radius * self.radius + 1.0) - 0.5                            # R'
         norm_d, norm_s = self.clip * self.clip, far * far
 
-        def costs(p_d, p_s):
-            """pooled words -> (mean depth cost or nan, mean outline cost, the cost a step is judged by)"""
-            c_s = p_s[1] / p_s[0] if p_s[0] > 0 else np.inf
-            if p_d is None:
-                return nan, float(c_s), float(self.silhouette * (c_s / norm_s))
-            c_d = p_d[1] / p_d[0] if p_d[0] > 0 else np.inf
-            return float(c_d), float(c_s), float(c_d / norm_d + self.silhouette * (c_s / norm_s))
+        def evaluate(state):
+            """-> ((the terms' words, their pools, their mean costs), the cost a step is judged by): depth alone its mean cost,
+            with the outline c_d / clip^2 + silhouette c_s / R'^2"""
+            w_d, w_s = self._equations(state[0], state[2], depth_t, sd2_t)
+            p_d, p_s = (None if w is None else pool_bundle(w) for w in (w_d, w_s))
+            c_d, c_s = (nan if p is None else float(p[1] / p[0]) if p[0] > 0 else np.inf for p in (p_d, p_s))
+            if not outline:
+                cost = c_d
+            else:
+                cost = float(self.silhouette * (c_s / norm_s)) if p_d is None else float(c_d / norm_d + self.silhouette * (c_s / norm_s))
+            return (w_d, p_d, c_d, w_s, p_s, c_s), cost
 
-        def weighted(w_d, a_d, w_s, a_s):
-            """a_d w_d + a_s w_s on the words of the system, [4 .. 93]; the rest 0"""
+        def system(w_d, p_d, w_s, p_s):
+            """a_d w_d + a_s w_s on the words of the system, [4 .. 93], each term divided by its pixel count and truncation; the rest 0"""
+            a_d = 1.0 / (p_d[0] * norm_d) if p_d is not None and p_d[0] > 0 else 0.0
+            a_s = self.silhouette / (p_s[0] * norm_s) if p_s[0] > 0 else 0.0
             out = np.zeros_like(w_s)
             out[..., 4:94] = a_s * w_s[..., 4:94] if w_d is None else a_d * w_d[..., 4:94] + a_s * w_s[..., 4:94]
             return out
 
-        def system(w_d, p_d, w_s, p_s):
-            a_d = 1.0 / (p_d[0] * norm_d) if p_d is not None and p_d[0] > 0 else 0.0
-            a_s = self.silhouette / (p_s[0] * norm_s) if p_s[0] > 0 else 0.0
-            return weighted(w_d, a_d, w_s, a_s)
-
-        q, off = q0.copy(), np.zeros(6)
-        lam = self.damping
-        w_d, w_s = self.equations_both(pose, q, depth_t, sd2_t)
-        p_d, p_s = None if w_d is None else pool_bundle(w_d), pool_bundle(w_s)
-        cd, cs, cost = costs(p_d, p_s)
-        cd_before, cs_before, steps = cd, cs, 0
-        for _ in range(self.iterations):
-            words = system(w_d, p_d, w_s, p_s)
+        def propose(state, held, lam):
+            pose, off, q = state
+            w_d, p_d, _, w_s, p_s, _ = held
+            words = system(w_d, p_d, w_s, p_s) if outline else w_d      # depth alone: the kernel's words as they came
             if frame_mode:
                 dq, dc = schur_step(words, self.active_j, self.active_c, lam)
-                t_pose, t_off, t_q = pose + dc, off, np.clip(q + dq, self.limits[:, 0], self.limits[:, 1])
-            else:
-                d = bundle_columns_step(pool_bundle(words), slots, lam)
-                t_pose, t_off = pose + d[6:], off + d[:6]
-                t_q = np.clip(q0 + t_off, self.limits[:, 0], self.limits[:, 1])
-            wt_d, wt_s = self.equations_both(t_pose, t_q, depth_t, sd2_t)
-            pt_d, pt_s = None if wt_d is None else pool_bundle(wt_d), pool_bundle(wt_s)
-            ct_d, ct_s, c_t = costs(pt_d, pt_s)
-            if c_t < cost:                                              # strictly smaller, or everything is put back
-                pose, off, q, w_d, w_s, p_d, p_s, cd, cs, cost = t_pose, t_off, t_q, wt_d, wt_s, pt_d, pt_s, ct_d, ct_s, c_t
-                steps += 1
-            else:
-                lam *= 10.0
+                return pose + dc, off, np.clip(q + dq, lo, hi)
+            d = bundle_columns_step(pool_bundle(words) if outline else p_d, slots, lam)
+            t_off = off + d[:6]
+            return pose + d[6:], t_off, np.clip(q0 + t_off, lo, hi)
 
-        # the sigmas: the information of the two terms added, each over its own s^2 = [3] / ([2] - p).  The sum goes through
-        # schur_sigma / bundle_columns_sigma with [2] = p + 1 and [3] = 1, which makes their own factor s^2 exactly 1.
-        terms = [(w, pl) for w, pl in ((w_d, p_d), (w_s, p_s)) if w is not None]
-        if frame_mode:
-            frames, kc, _, _ = _arrow_blocks(sum(w for w, _ in terms), self.active_j, self.active_c)
-            p = len(kc) + sum(len(fr[0]) for fr in frames)
-        else:
-            A, _ = unpack_bundle(sum(pl for _, pl in terms))
-            p = sum(1 for c in slots if A[c, c] > 0)
-        info = np.zeros_like(w_s)
-        for w, pl in terms:
-            if p > 0 and pl[2] >= p + 1 and pl[3] > 0:
-                info[:, 4:94] += w[:, 4:94] / (pl[3] / (pl[2] - p))
-        if info.any():
-            info[0, 2], info[0, 3] = p + 1.0, 1.0
-        inl_d = 0.0 if p_d is None else float(p_d[2])
-        frame_cost = np.full(N, np.nan) if w_d is None else mean_cost(w_d[:, :NEQ_WORDS])
-        if frame_mode:
-            sq, sc = schur_sigma(info, self.active_j, self.active_c)
-            return BundleRefineResult(pose, q, np.full(6, np.nan), sc, sq, None, cd_before, cd, steps, inl_d, frame_cost, cs_before, cs, float(p_s[2]))
-        s = bundle_columns_sigma(pool_bundle(info), slots)
-        return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), s[6:], None, s[:6], cd_before, cd, steps,
-                                  inl_d, frame_cost, cs_before, cs, float(p_s[2]))
+        (pose, off, q), (w_d, p_d, c_d, w_s, p_s, c_s), first, steps = _levenberg_loop(evaluate, propose, (pose, np.zeros(6), q0.copy()),
+                                                                                     self.iterations, self.damping)
+        words, pooled = w_d, p_d
+        if outline:
+            # the sigmas: the information of the two terms added, each over its own s^2 = [3] / ([2] - p).  The sum goes through
+            # schur_sigma / bundle_columns_sigma with [2] = p + 1 and [3] = 1, which makes their own factor s^2 exactly 1.
+            terms = [(w, pl) for w, pl in ((w_d, p_d), (w_s, p_s)) if w is not None]
+            if frame_mode:
+                frames, kc, _, _ = _arrow_blocks(sum(w for w, _ in terms), self.active_j, self.active_c)
+                p = len(kc) + sum(len(fr[0]) for fr in frames)
+            else:
+                A, _ = unpack_bundle(sum(pl for _, pl in terms))
+                p = sum(1 for c in slots if A[c, c] > 0)
+            words = np.zeros_like(w_s)
+            for w, pl in terms:
+                if p > 0 and pl[2] >= p + 1 and pl[3] > 0:
+                    words[:, 4:94] += w[:, 4:94] / (pl[3] / (pl[2] - p))
+            if words.any():
+                words[0, 2], words[0, 3] = p + 1.0, 1.0
+            pooled = None if frame_mode else pool_bundle(words)
+        sj, sp = schur_sigma(words, self.active_j, self.active_c) if frame_mode else np.split(bundle_columns_sigma(pooled, slots), 2)
+        return self._result(pose, q, off, sp, sj, first[2], c_d, steps, 0.0 if p_d is None else float(p_d[2]),
+                            np.full(N, np.nan) if w_d is None else mean_cost(w_d[:, :NEQ_WORDS]),
+                            *((first[5], c_s, float(p_s[2])) if outline else ()))
+
+    def _refine_native(self, pose: np.ndarray, q0: np.ndarray, depth_t) -> BundleRefineResult:
+        """refine through rope_refine_bundle: ONE call, because one system spans all frames — a batch whose scratch one call does
+        not take is refused (Engine.refine_bundle_workspace says what a batch needs)."""
+        from ..constants import ZFAR, ZNEAR
+        jm, cm = sum(1 << j for j in self.active_j), sum(1 << k for k in self.active_c)
+        r = self.engine.refine_bundle(self.mode, pose, q0, depth_t, _intr4(self.intrinsics), ZNEAR, ZFAR, jm, cm, self.limits,
+                                      self.clip, self.iterations, self.damping)
+        return self._result(r['pose'], r['angles'], r['offsets'], np.sqrt(r['var_pose']), np.sqrt(r['var_joints']), r['cost_before'], r['cost_after'],
+                            r['steps'], r['inliers'], r['frame_cost'])

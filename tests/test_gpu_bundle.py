@@ -1,7 +1,8 @@
 """GPU: rope_bundle_normal_equations (csrc/rope_bundle.hip; Engine.bundle_normal_equations) against the numpy restatement of its
 contract (tests/bundle_ref.py) and against the two shipped 6-column kernels on the same planes — counts equal, every float sum
 within the worst case of a reordered float64 summation — its determinism, what it refuses, BundleRefiner end to end in both modes
-against bundle_ref's loops on the engine's own renders, the 'bundle' switch of the two camera predictors, and calibrate.py.
+against bundle_ref's loops on the engine's own renders, the 'bundle' switch of the two camera predictors, calibrate.py, and the
+host loop the refiners share against the restated loops on the words of the same engine calls, byte for byte.
 
 The bound is tests/test_gpu_refine.py's: a sum of n float64 terms added in any order differs from the exact sum by at most
 (n - 1) eps sum|terms| to first order, eps = 2^-52; two orders differ by at most twice that, and the terms themselves are the
@@ -398,3 +399,147 @@ def test_calibrate_runs_on_a_synthetic_set(tmp_path, joints):
         assert len(rep['offsets']) == 6 and len(rep['sigma_offsets']) == 6
     if joints == 'frame':
         assert len(rep['angle_change_max']) == 6 and len(rep['angle_change_rms']) == 6 and len(rep['sigma_angles']) == 8
+
+
+# ---------------------------------------------------------------------------------------------- the shared host loop, byte for byte
+def _silhouette_loop(pose, angles, equations, limits, mode, active_j, active_c, weight, clip, radius, iterations=5, damping=1e-3):
+    """BundleRefiner(silhouette=weight)'s loop restated on bundle_ref's solves.  equations(pose, angles) -> (depth words (N, 96) or
+    None, outline words (N, 96)).  A step is judged by c_d / clip^2 + weight c_s / R'^2 and solved on the sum of the two terms' words,
+    each divided by its pixel count and truncation; the sigmas add the terms' information, each over its own s^2."""
+    p, q0 = np.array(pose, np.float64).reshape(6), np.array(angles, np.float64).reshape(-1, 6)
+    active_j, active_c = list(active_j), list(active_c)
+    slots = active_j + [6 + k for k in active_c]
+    far = np.sqrt(radius * radius + 1.0) - 0.5
+    norm_d, norm_s = clip * clip, far * far
+    nan = float('nan')
+
+    def look(p, q):
+        w_d, w_s = equations(p, q)
+        p_d, p_s = None if w_d is None else bref.pool(w_d), bref.pool(w_s)
+        c_s = p_s[1] / p_s[0] if p_s[0] > 0 else np.inf
+        if p_d is None:
+            return w_d, w_s, p_d, p_s, nan, float(c_s), float(weight * (c_s / norm_s))
+        c_d = p_d[1] / p_d[0] if p_d[0] > 0 else np.inf
+        return w_d, w_s, p_d, p_s, float(c_d), float(c_s), float(c_d / norm_d + weight * (c_s / norm_s))
+
+    q, off, lam, steps = q0.copy(), np.zeros(6), float(damping), 0
+    w_d, w_s, p_d, p_s, cd, cs, cost = look(p, q)
+    cd0, cs0 = cd, cs
+    for _ in range(iterations):
+        a_d = 1.0 / (p_d[0] * norm_d) if p_d is not None and p_d[0] > 0 else 0.0
+        a_s = weight / (p_s[0] * norm_s) if p_s[0] > 0 else 0.0
+        words = np.zeros_like(w_s)
+        words[:, 4:94] = a_s * w_s[:, 4:94] if w_d is None else a_d * w_d[:, 4:94] + a_s * w_s[:, 4:94]
+        if mode == 'frame':
+            dq, dc = bref.schur_step(words, active_j, active_c, lam)
+            t_p, t_off, t_q = p + dc, off, np.clip(q + dq, limits[:, 0], limits[:, 1])
+        else:
+            d = bref.columns_step(bref.pool(words), slots, lam)
+            t_p, t_off = p + d[6:], off + d[:6]
+            t_q = np.clip(q0 + t_off, limits[:, 0], limits[:, 1])
+        trial = look(t_p, t_q)
+        if trial[6] < cost:
+            p, off, q = t_p, t_off, t_q
+            w_d, w_s, p_d, p_s, cd, cs, cost = trial
+            steps += 1
+        else:
+            lam *= 10.0
+    terms = [(w, pl) for w, pl in ((w_d, p_d), (w_s, p_s)) if w is not None]
+    if mode == 'frame':
+        frames, kc, _, _ = bref.arrow_blocks(sum(w for w, _ in terms), active_j, active_c)
+        n_live = len(kc) + sum(len(fr[0]) for fr in frames)
+    else:
+        A, _ = bref.unpack(sum(pl for _, pl in terms))
+        n_live = sum(1 for c in slots if A[c, c] > 0)
+    info = np.zeros_like(w_s)
+    for w, pl in terms:
+        if n_live > 0 and pl[2] >= n_live + 1 and pl[3] > 0:
+            info[:, 4:94] += w[:, 4:94] / (pl[3] / (pl[2] - n_live))
+    if info.any():
+        info[0, 2], info[0, 3] = n_live + 1.0, 1.0
+    out = dict(pose=p, angles=q, cost_before=cd0, cost_after=cd, steps_taken=steps, inliers=0.0 if p_d is None else float(p_d[2]),
+               frame_cost=np.full(len(q), np.nan) if w_d is None else np.array([bref.mean_cost(w) for w in w_d]),
+               cost_silhouette_before=cs0, cost_silhouette_after=cs, inliers_silhouette=float(p_s[2]))
+    if mode == 'frame':
+        sq, sc = bref.schur_sigma(info, active_j, active_c)
+        out.update(offsets=np.full(6, np.nan), sigma_pose=sc, sigma_angles=sq, sigma_offsets=None)
+    else:
+        s = bref.columns_sigma(bref.pool(info), slots)
+        out.update(offsets=np.where(np.isin(np.arange(6), active_j), off, 0.0), sigma_pose=s[6:], sigma_angles=None, sigma_offsets=s[:6])
+    return out
+
+
+def _same_fields(got, want, fields):
+    for k in fields:
+        g, w = getattr(got, k), want[k]
+        if w is None:
+            assert g is None, k
+            continue
+        g, w = np.asarray(g, np.float64), np.asarray(w, np.float64)
+        assert g.shape == w.shape and g.tobytes() == w.tobytes(), (k, g, w)
+
+
+@pytest.fixture(scope='module')
+def small_scene():
+    """Three frames of 47 x 45 = 2115 pixels — two passes of a workgroup's 256 x 8 and a ragged last row, the shape of
+    tests/test_gpu_neq_terms.py's three-frame case — of the robot under a camera 5 mm / 4 mrad from the start."""
+    from rope_s3d_amd.constants import DEFAULT_CAMERA_POSE, ZFAR, ZNEAR
+    from rope_s3d_amd.projection import Intrinsics, camera_matrix
+    intr = Intrinsics('640_480_color')
+    intr.resolution, intr.f, intr.pp = [47, 45], [v * 47 / 640 for v in intr.f], [23.25, 22.75]
+    e = eng.Engine(0)
+    e.set_robot(helpers.robot())
+    e.set_camera(camera_matrix(DEFAULT_CAMERA_POSE, intr, ZNEAR, ZFAR), intr.width, intr.height, ZNEAR, ZFAR)
+    rng = np.random.default_rng(31)
+    lim, slu = np.asarray(helpers.robot().joint_limits, np.float64), np.array([1, 1, 1, 0, 0, 0])
+    truth = rng.uniform(lim[:, 0] * .5, lim[:, 1] * .5, (3, 6)) * slu
+    true_pose = np.array(DEFAULT_CAMERA_POSE, float) + TRUE_POSE_OFFSET
+    start_pose = true_pose + rng.uniform(-1, 1, 6) * np.array([.005, .005, .005, .004, .004, .004])
+    start = truth + rng.uniform(-DESCENT_STEP, DESCENT_STEP, (3, 6)) * slu
+    T, ti = e.render_batch_device(truth, 6, np.tile(camera_matrix(true_pose, intr)[None], (3, 1, 1)))
+    yield e, intr, lim, truth, start, start_pose, T.clone(), (ti < 6).clone()
+    e.close()
+
+
+@pytest.mark.parametrize('case', ['camera', 'frame', 'offset', 'silhouette', 'silhouette alone'])
+def test_the_refiners_walk_the_restated_loops_byte_for_byte_on_the_same_engine(small_scene, case):
+    """CameraPoseRefiner and BundleRefiner against camera_refine_ref.refine, bundle_ref.refine and _silhouette_loop, every side
+    with the words of the SAME engine calls: the host loops add nothing of their own, so no tolerance enters."""
+    from rope_s3d_amd.prediction import refinement as rf
+    from rope_s3d_amd.projection import camera_matrix, camera_pose_matrix
+    e, intr, lim, truth, start, start_pose, T, mask = small_scene
+    assert tuple(T.shape) == (3, 45, 47)
+    intr4 = (intr.fx, intr.fy, intr.cx, intr.cy)
+    sd2 = e.mask_distance(mask.to(torch.uint8).contiguous(), 8)
+
+    def words(p, q, depth=True, outline=False):
+        q = np.ascontiguousarray(q, np.float64)
+        rd, ri = e.render_batch_device(q, 6, np.tile(camera_matrix(p, intr)[None], (3, 1, 1)))
+        axes = rf.joint_axes_camera(rf.ForwardKinematics(), *cref.Rwc_t(p, camera_pose_matrix), q)
+        tw = np.tile(rf.camera_twists(p)[None], (3, 1, 1))
+        if case == 'camera':
+            return e.camera_normal_equations(rd, ri, T, tw, 6, CLIP, intr4)
+        w_d = e.bundle_normal_equations(rd, ri, T, axes[:, :3], tw, 6, CLIP, intr4) if depth else None
+        return (w_d, e.silhouette_normal_equations(rd, ri, sd2, axes[:, :3], tw, 6, 8, intr4)) if outline else w_d
+
+    plain = ('pose', 'cost_before', 'cost_after', 'steps_taken', 'inliers', 'frame_cost')
+    if case == 'camera':
+        want = cref.refine(start_pose, lambda p: words(p, truth))
+        got = rf.CameraPoseRefiner(e, intr).refine(start_pose, truth, T)
+        _same_fields(got, want, plain + ('sigma',))
+    elif case in ('frame', 'offset'):
+        want = bref.refine(start_pose, start, words, lim, case)
+        want.setdefault('sigma_angles'), want.setdefault('sigma_offsets')
+        got = rf.BundleRefiner(e, intr, joints=case).refine(start_pose, start, T)
+        _same_fields(got, want, plain + ('angles', 'offsets', 'sigma_pose', 'sigma_angles', 'sigma_offsets'))
+        assert np.isnan(got.cost_silhouette_before) and np.isnan(got.cost_silhouette_after) and got.inliers_silhouette == 0
+    else:
+        depth = case == 'silhouette'
+        for mode in ('frame', 'offset'):
+            want = _silhouette_loop(start_pose, start, lambda p, q: words(p, q, depth, True), lim, mode, (0, 1, 2), range(6), 1.0, CLIP, 8)
+            got = rf.BundleRefiner(e, intr, joints=mode, silhouette=1.0).refine(start_pose, start, T if depth else None, mask)
+            _same_fields(got, want, plain + ('angles', 'offsets', 'sigma_pose', 'sigma_angles', 'sigma_offsets', 'cost_silhouette_before',
+                                             'cost_silhouette_after', 'inliers_silhouette'))
+            assert want['inliers_silhouette'] > 0 and (want['inliers'] > 0) == depth
+    print(case, 'steps', got.steps_taken, 'cost', got.cost_before, '->', got.cost_after)
+    assert want['inliers'] > 0 or case == 'silhouette alone'
