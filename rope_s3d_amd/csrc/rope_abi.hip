@@ -64,13 +64,14 @@ extern "C" int rope_create(rope_ctx **out, int device)
     rope_ctx *c = new (std::nothrow) rope_ctx();
     if (!c) return ROPE_E_NOMEM;
     c->device = device;
-    if (const char *e = std::getenv("ROPE_SPLIT_TARGET")) c->split_target = std::max(1, std::atoi(e));     // tuning aid
+    PassTunables &t = c->tune;
+    if (const char *e = std::getenv("ROPE_SPLIT_TARGET")) t.split_target = std::max(1, std::atoi(e));     // tuning aid
     if (const char *e = std::getenv("ROPE_STRATEGY")) c->strategy = std::atoi(e) & 255;                     // tuning aid: rope_set_strategy's bits
-    if (const char *e = std::getenv("ROPE_SPLIT_CAP")) c->split_cap = std::max(1, std::min(64, std::atoi(e)));
-    if (const char *e = std::getenv("ROPE_SPLIT_MIN")) c->split_min = std::max(1, std::min(64, std::atoi(e)));
-    if (const char *e = std::getenv("ROPE_GEO_ROWS")) c->geo_rows = std::max(0, std::min(256, std::atoi(e)));     // d_touched holds 256 rows
-    if (const char *e = std::getenv("ROPE_LAYER_MIN_WG")) c->layer_min_wg = std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("ROPE_SPLIT_MIN_MANY")) c->split_min_many = std::max(1, std::min(64, std::atoi(e)));
+    if (const char *e = std::getenv("ROPE_SPLIT_CAP")) t.split_cap = std::max(1, std::min(64, std::atoi(e)));
+    if (const char *e = std::getenv("ROPE_SPLIT_MIN")) t.split_min = std::max(1, std::min(64, std::atoi(e)));
+    if (const char *e = std::getenv("ROPE_GEO_ROWS")) t.geo_rows = std::max(0, std::min(OWN_GEOMETRY_MAX_ROWS, std::atoi(e)));     // d_touched holds that many rows
+    if (const char *e = std::getenv("ROPE_LAYER_MIN_WG")) t.layer_min_wg = std::max(0, std::atoi(e));
+    if (const char *e = std::getenv("ROPE_SPLIT_MIN_MANY")) t.split_min_many = std::max(1, std::min(64, std::atoi(e)));
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         g_create_err = "hipSetDevice/hipStreamCreate failed";
         delete c;
@@ -464,12 +465,12 @@ int upload_candidates(rope_ctx *c, const double *cand, int C, bool group, const 
         }
         c->n_layers = (int)layer_rep.size();
         c->n_parents = (int)parent_rep.size();
-        if (c->n_layers * 4 <= C) {                // same rule as want_layers(): only then are the arrays read
+        if (layers_wanted(c->n_layers, C)) {        // only then are the arrays read
             rc = sync_grow(c, c->d_layer_rep, (size_t)c->n_layers);
             if (rc) return rc;
             HIP_TRY(c, hipMemcpyAsync(c->d_layer_of, layer_of.data(), (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
             HIP_TRY(c, hipMemcpyAsync(c->d_layer_rep, layer_rep.data(), layer_rep.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            if (c->n_parents * 4 <= c->n_layers) {     // same rule one level up (want_parents())
+            if (parents_wanted(c->n_parents, c->n_layers)) {
                 rc = sync_grow(c, c->d_parent_of, (size_t)c->n_layers, c->d_parent_rep, (size_t)c->n_layers);
                 if (rc) return rc;
                 HIP_TRY(c, hipMemcpyAsync(c->d_parent_of, parent_of.data(), parent_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
@@ -523,16 +524,17 @@ int ensure_totals(rope_ctx *c, const TargetSet &s, EmptyCache &cache, int loss, 
     return ROPE_OK;
 }
 
-// Layers pay off when many candidates share one upstream pose (lookup grids, sweeps of U).
-static bool want_layers(const rope_ctx *c) { return c->n_layers * 4 <= c->C; }
-
-// A small batch whose candidates share one or two upstream poses (a sweep of the third joint) would draw links 0-2 in a layer
-// launch of a handful of workgroups — 59 000 triangles each, the rest of the chip idle (100 us at 160x90) — before the scoring
-// launch: the split path draws all six links per candidate over many workgroups instead and is more than twice as fast there.
-static bool layers_pay(const rope_ctx *c)
+// What the rules of rope_passplan.h read, taken from the context once per pass.  `clip`: use_clip() for the pass's cameras.  The
+// render, coverage, table and debug entries, which only take the geometry part of a plan, say EVAL_SINGLE.
+static PassInputs pass_inputs(const rope_ctx *c, int n_render, int loss, const FrameParams &fp, EvalKind kind, bool frame_index, bool clip)
 {
-    const int busy_tiles = std::max(std::min(2, c->n_tiles), c->n_tiles / 3);
-    return c->C > 256 || c->n_layers * busy_tiles >= c->layer_min_wg;
+    PassInputs in;
+    in.C = c->C; in.n_tiles = c->n_tiles; in.n_layers = c->n_layers; in.n_parents = c->n_parents;
+    in.n_render = n_render; in.loss = loss; in.kind = kind; in.frame_index = frame_index;
+    in.strategy = c->strategy; in.n_cu = c->n_cu; in.q_weighted = c->q_weighted;
+    in.clip = clip; in.skip = ROPE_SKIP(fp, ~0);
+    in.t = c->tune;
+    return in;
 }
 
 static int ensure_layers(rope_ctx *c)
@@ -542,42 +544,29 @@ static int ensure_layers(rope_ctx *c)
     return sync_grow(c, c->d_layers, need, c->d_layer_sums, (size_t)c->n_layers * c->n_tiles * ROPE_SUM_WORDS);
 }
 
-static bool want_parents(const rope_ctx *c) { return c->n_parents * 4 <= c->n_layers; }
-static uint32_t *queue_weights(const rope_ctx *c);
-// Second level of sharing (links 0-1 once per distinct q0): pays when the layers are a launch of one workgroup per (layer, tile)
-// pair — not when they go through the weighted queue, which draws links 0-2 per layer faster than the extra launch of a
-// hundred busy workgroups plus the merge of every layer tile with its parent's (0.264 against 0.283 ms on the bench workload).
-static bool use_parents(const rope_ctx *c, int n_shared)
-{
-    if (n_shared != 3 || !want_parents(c) || (c->strategy & STRATEGY_NO_PARENTS)) return false;
-    return !(queue_weights(c) && !(c->strategy & STRATEGY_NO_QUEUE));
-}
-
 // The shared links of every layer into c->d_layers (+ their loss sums when `la` carries targets and layer_sums).
 // Two levels when many layers share their first joint angle: links 0-1 once per distinct q0, then link 2 per layer
 // merged with its parent's tile.
-static int enqueue_layers(rope_ctx *c, RasterArgs la, int loss, int n_shared, const FrameParams &fp)
+static int enqueue_layers(rope_ctx *c, const PassPlan &plan, RasterArgs la, int loss, const FrameParams &fp)
 {
     c->drop_kept();                               // every writer of the layer tiles comes through here
     la.cand_of_row = c->d_layer_rep; la.layers = c->d_layers;
-    if (use_parents(c, n_shared)) {
+    if (plan.parents) {
         const size_t need = (size_t)c->n_parents * c->n_tiles * (TILE_W * TILE_H);
         if (int rc = sync_grow(c, c->d_parents, need)) return rc;
         RasterArgs pa = la;
         pa.l_begin = 0; pa.l_end = 2; pa.cand_of_row = c->d_parent_rep; pa.layers = c->d_parents; pa.layer_sums = nullptr;
-        HIP_TRY(c, launch_raster(MODE_LAYER, loss, c->n_parents, c->stream, fp, c->rp, pa, use_clip(c)));
+        HIP_TRY(c, launch_raster(MODE_LAYER, loss, c->n_parents, c->stream, fp, c->rp, pa, plan.clip));
         la.l_begin = 2; la.l_end = 3; la.base_layers = c->d_parents; la.base_of_row = c->d_parent_of; la.base_rep = c->d_parent_rep;
     } else {
-        la.l_begin = 0; la.l_end = n_shared;
+        la.l_begin = 0; la.l_end = plan.n_shared;
     }
-    if (queue_weights(c) && !(c->strategy & STRATEGY_NO_QUEUE)) {
-        // the (layer, tile) pairs that have anything to draw, heaviest first, to a grid that just fills the chip: of the one-
-        // workgroup-per-pair launch's 266 us the last 100 ran with a third of the chip (a 140 us pair that started at 150 us)
-        HIP_TRY(c, launch_layer_queue(loss, c->n_layers, 2 * c->n_cu, c->stream, fp, c->rp, la, c->d_qitems + QUEUE_CLASSES * c->q_segment,
-                                      c->q_segment, c->d_qctr + QUEUE_COUNTERS, c->d_tile_tris_lo, use_clip(c)));
+    if (plan.layer_queue) {
+        HIP_TRY(c, launch_layer_queue(loss, c->n_layers, QUEUE_WG_PER_CU * c->n_cu, c->stream, fp, c->rp, la, c->d_qitems + QUEUE_CLASSES * c->q_segment,
+                                      c->q_segment, c->d_qctr + QUEUE_COUNTERS, c->d_tile_tris_lo, plan.clip));
         return ROPE_OK;
     }
-    HIP_TRY(c, launch_raster(MODE_LAYER, loss, c->n_layers, c->stream, fp, c->rp, la, use_clip(c)));
+    HIP_TRY(c, launch_raster(MODE_LAYER, loss, c->n_layers, c->stream, fp, c->rp, la, plan.clip));
     return ROPE_OK;
 }
 
@@ -590,59 +579,51 @@ static RasterArgs base_args(rope_ctx *c, int n_render)
     return a;
 }
 
-// The raster queue hands out the heaviest (candidate, tile) pairs first when a workgroup gets few enough pairs for the last ones
-// to matter: with 40 pairs per workgroup (4096 candidates at 640x480) a 20 000-triangle pair that starts late kept its workgroup
-// busy 180 us after the others had left, 7 % of the launch; with hundreds per workgroup (32 768 candidates at 1280x720) the tail is
-// nothing and candidate order, which keeps a candidate's boxes in L2 for its tiles, is 1.5 % faster.
-static uint32_t *queue_weights(const rope_ctx *c)
-{
-    const size_t busy_tiles = (size_t)std::max(std::min(2, c->n_tiles), c->n_tiles / 3);
-    return (c->q_weighted && c->C > 256 && (size_t)c->C * busy_tiles <= (size_t)256 * 2 * c->n_cu) ? c->d_tile_tris : nullptr;     // C <= 256: fk_bounds_kernel, no weights
-}
+// the queues' per-(candidate, tile) weights, when the plan uses them
+static uint32_t *queue_weights(const rope_ctx *c, const PassPlan &plan) { return plan.weighted ? c->d_tile_tris.get() : nullptr; }
 
 // What the buffers a large layered pass leaves behind depend on (GeometryKey): candidates, camera and robot by their epochs, the
 // pass's frame and n_render, and everything that decides which launches write them — the second sharing level, the queues and
-// their weights (functions of strategy, C, tiles and n_cu, recorded as taken), the clipping kernels — plus the capacities of the
+// their weights, the clipping kernels: copied from the plan the pass's launches run by — plus the capacities of the
 // buffers themselves.  The loss is not part of it: the one thing of these launches that depends on loss or target, the layers'
 // sums, is taken anew by every pass.
-static GeometryKey geometry_key(const rope_ctx *c, int n_render, int n_shared, const FrameParams &fp)
+static GeometryKey geometry_key(const rope_ctx *c, const PassPlan &plan, int n_render, const FrameParams &fp)
 {
     static_assert(sizeof(FrameParams) <= sizeof(GeometryKey::frame), "GeometryKey::frame holds a FrameParams");
     GeometryKey k = GeometryKey::make();
     k.cand_epoch = c->cand_epoch; k.camera_epoch = c->camera_epoch; k.robot_epoch = c->robot_epoch;
     k.cap_layers = c->d_layers.cap(); k.cap_layer_sums = c->d_layer_sums.cap(); k.cap_bounds = c->d_bounds.cap(); k.cap_mvp = c->d_mvp.cap();
     k.q_segment = c->q_segment;
-    k.C = c->C; k.n_layers = c->n_layers; k.n_parents = c->n_parents; k.n_render = n_render; k.n_shared = n_shared;
+    k.C = c->C; k.n_layers = c->n_layers; k.n_parents = c->n_parents; k.n_render = n_render; k.n_shared = plan.n_shared;
     k.strategy = c->strategy; k.n_cu = c->n_cu;
-    k.parents = use_parents(c, n_shared); k.queue = !(c->strategy & STRATEGY_NO_QUEUE); k.weighted = queue_weights(c) != nullptr; k.clip = use_clip(c);
+    k.parents = plan.parents; k.queue = plan.scoring == SCORE_QUEUE; k.weighted = plan.weighted; k.clip = plan.clip;
     k.set_frame(&fp, sizeof fp);
     return k;
 }
 
 // forward kinematics + link matrices + screen boxes + tile masks (+ cleared sums) of the resident candidates
-static int enqueue_geometry(rope_ctx *c, int n_render, int n_shared, const FrameParams &fp, bool views)
+static int enqueue_geometry(rope_ctx *c, const PassPlan &plan, int n_render, const FrameParams &fp, bool views)
 {
     c->drop_kept();                               // every writer of d_mvp, d_bounds, the masks and the weights comes through here
     const double *PV = views ? c->dv_PV : c->d_PV, *cand = views ? c->dv_cand : c->cand_dev;
     const int32_t *view_of = views ? c->dv_view_of : nullptr;
-    if (c->C <= 256) {                              // one fused launch, one workgroup per candidate
+    const int n_shared = plan.n_shared;
+    if (plan.fused_geometry) {                      // one fused launch, one workgroup per candidate
         HIP_TRY(c, launch_fk_bounds(c->stream, cand, c->C, fp, c->rp, n_render, n_shared, c->d_joint_fixed, c->d_joint_axes, PV,
                                     view_of, c->d_mvp, c->d_bounds, c->d_sums, c->d_mask_lo, c->d_mask_hi, c->mask_words));
         return ROPE_OK;
     }
     HIP_TRY(c, launch_fk(c->stream, cand, c->C, n_render, c->d_joint_fixed, c->d_joint_axes, PV, view_of, c->d_mvp, c->d_sums,
-                         c->d_mask_lo, c->d_mask_hi, c->mask_words, c->d_qctr, queue_weights(c), c->d_tile_tris_lo, c->n_tiles));
-    // weights of the shared links for the layer launch: with the second level in use it draws the last shared link only
-    const int lo_first = use_parents(c, n_shared) ? 2 : 0;
+                         c->d_mask_lo, c->d_mask_hi, c->mask_words, c->d_qctr, queue_weights(c, plan), c->d_tile_tris_lo, c->n_tiles));
     HIP_TRY(c, launch_bounds(c->stream, c->C, fp, c->rp, n_render, n_shared, c->d_mvp, c->d_bounds, c->d_mask_lo, c->d_mask_hi, c->mask_words,
-                             n_shared > 0 ? c->d_layer_of : nullptr, n_shared > 0 ? c->d_layer_rep : nullptr, queue_weights(c), c->d_tile_tris_lo, lo_first));
+                             n_shared > 0 ? c->d_layer_of : nullptr, n_shared > 0 ? c->d_layer_rep : nullptr, queue_weights(c, plan), c->d_tile_tris_lo, plan.lo_first));
     return ROPE_OK;
 }
 
 // One chunk of rows' own links into c->d_fscratch: the MODE_LAYER queue launch with a RasterArgs of its own — the row -> candidate map
 // is the identity from row0 on, "mask_lo" is the candidates' mask_hi (the tiles their own links reach), the weights are the own
 // links', and there is neither a parent level nor sums.  It runs on the layer queue's counters and segment, which a hit pass leaves idle.
-static int draw_own_links(rope_ctx *c, const RasterArgs &a, int loss, const FrameParams &fp, int row0, int rows)
+static int draw_own_links(rope_ctx *c, const PassPlan &plan, const RasterArgs &a, int loss, const FrameParams &fp, int row0, int rows)
 {
     RasterArgs la = base_args(c, a.n_render);
     la.l_begin = a.l_begin; la.l_end = a.n_render;
@@ -651,9 +632,9 @@ static int draw_own_links(rope_ctx *c, const RasterArgs &a, int loss, const Fram
     la.layers = c->d_fscratch;
     int *counters = c->d_qctr + QUEUE_COUNTERS;
     HIP_TRY(c, hipMemsetAsync(counters, 0, QUEUE_COUNTERS * sizeof(int), c->stream));
-    const bool weighted = queue_weights(c) != nullptr;
-    HIP_TRY(c, launch_layer_queue(loss, rows, 2 * c->n_cu, c->stream, fp, c->rp, la, weighted ? c->d_qitems + QUEUE_CLASSES * c->q_segment : c->d_qitems.get(),
-                                  weighted ? c->q_segment : 0, counters, weighted ? c->d_tile_tris.get() : nullptr, use_clip(c)));
+    const bool weighted = plan.weighted;
+    HIP_TRY(c, launch_layer_queue(loss, rows, QUEUE_WG_PER_CU * c->n_cu, c->stream, fp, c->rp, la, weighted ? c->d_qitems + QUEUE_CLASSES * c->q_segment : c->d_qitems.get(),
+                                  weighted ? c->q_segment : 0, counters, queue_weights(c, plan), plan.clip));
     return ROPE_OK;
 }
 
@@ -662,7 +643,7 @@ static int draw_own_links(rope_ctx *c, const RasterArgs &a, int loss, const Fram
 // that builds pays that — and, when the store fits the budget, drawn once more and written to their places.  Two draws instead of
 // one so that nothing is allocated before its size is known.  The scratch and the counts are released at the end, kept or declined.  `a`: the pass's scoring arguments (masks, layers, l_begin).
 // Leaves c->frags serving `key`, or declined for it; the queue counters and sums the pass's own scoring launch needs are untouched.
-static int build_fragments(rope_ctx *c, const GeometryKey &key, const RasterArgs &a, int loss, const FrameParams &fp)
+static int build_fragments(rope_ctx *c, const PassPlan &pass, const GeometryKey &key, const RasterArgs &a, int loss, const FrameParams &fp)
 {
     RopeRange r("rope:fragments-build");
     const int n_tiles = c->n_tiles, C = c->C;
@@ -679,7 +660,7 @@ static int build_fragments(rope_ctx *c, const GeometryKey &key, const RasterArgs
     }
     HIP_TRY(c, hipMemsetAsync(c->d_fcount, 0, n_slots * sizeof(uint32_t), c->stream));
     for (int k = 0; k < plan.chunks; k++) {
-        if (int rc = draw_own_links(c, a, loss, fp, plan.begin(k), plan.count(k, C))) return rc;
+        if (int rc = draw_own_links(c, pass, a, loss, fp, plan.begin(k), plan.count(k, C))) return rc;
         HIP_TRY(c, launch_fragment_count(c->stream, a, c->d_fscratch, plan.begin(k), plan.count(k, C), n_tiles, c->d_fcount));
     }
     std::vector<uint32_t> counts(n_slots);
@@ -700,7 +681,7 @@ static int build_fragments(rope_ctx *c, const GeometryKey &key, const RasterArgs
     HIP_TRY(c, hipMemcpyAsync(c->d_foffs, offs.data(), (n_slots + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));                                         // offs is local
     for (int k = 0; k < plan.chunks; k++) {
-        if (int rc = draw_own_links(c, a, loss, fp, plan.begin(k), plan.count(k, C))) return rc;
+        if (int rc = draw_own_links(c, pass, a, loss, fp, plan.begin(k), plan.count(k, C))) return rc;
         HIP_TRY(c, launch_fragment_fill(c->stream, a, c->d_fscratch, plan.begin(k), plan.count(k, C), n_tiles, c->d_foffs, c->d_fwhere, c->d_ffin, c->d_fbase));
     }
     // the scratch and the counts are the build's alone: let them go, which means one more wait in the pass that waits anyway
@@ -713,46 +694,27 @@ static int build_fragments(rope_ctx *c, const GeometryKey &key, const RasterArgs
 int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, double n_pix, const EvalPlanes &pl, EvalKind kind, hipEvent_t *ev)
 {
     const bool views = kind == EVAL_VIEWS, targets = kind == EVAL_TARGETS;
-    const bool layers = !views && want_layers(c) && layers_pay(c) && !(c->strategy & STRATEGY_NO_LAYERS);
-    const int n_shared = layers ? std::min(3, n_render) : 0;
+    // which launches the pass consists of: decided here, once (rope_passplan.h); below, only the plan and what the context holds
+    const PassPlan plan = plan_pass(pass_inputs(c, n_render, loss, fp, kind, pl.frame_of != nullptr, use_clip(c, views)));
+    const bool layers = plan.layers, geo = plan.own_geometry;
+    const int n_shared = plan.n_shared, split = plan.split;
     if (layers) { int rc = ensure_layers(c); if (rc) return rc; }
-    // A large layered batch against the single target keeps its geometry for the next pass (rope_ctx::geo).  Every other pass
-    // drops it: it either goes through enqueue_geometry or — the small batches that do their own — reuses the same buffers' rows.
-    const bool in_scope = kind == EVAL_SINGLE && layers && c->C > 256 && !pl.frame_of;
-    const bool cacheable = in_scope && !(c->strategy & STRATEGY_NO_GEOMETRY_CACHE) && !ROPE_SKIP(fp, ~0);
+    // A cacheable pass keeps its geometry for the next one (rope_ctx::geo); every other pass drops it.
+    const bool cacheable = plan.cacheable;
     GeometryKey key = GeometryKey::make();
-    if (cacheable) key = geometry_key(c, n_render, n_shared, fp);
+    if (cacheable) key = geometry_key(c, plan, n_render, fp);
     const bool hit = cacheable && c->geo.holds(key);
     c->geo.drop();                                  // a pass that fails half way leaves nothing behind; set again at the end
-    if (in_scope) (hit ? c->geo.hits : c->geo.misses)++;
+    if (plan.cache_scope) (hit ? c->geo.hits : c->geo.misses)++;
     // Kept fragments (rope_ctx::frags): a hit may be scored from them, and builds them when they are not there yet; any other pass
-    // is about to write the geometry they were taken from.  Through the queues only (the build is a queue launch).
+    // is about to write the geometry they were taken from.
     if (!hit) c->frags.drop();
-    const bool frag_scope = hit && loss != ROPE_LOSS_CAMFULL && !(c->strategy & (STRATEGY_NO_KEPT_FRAGMENTS | STRATEGY_NO_QUEUE));
+    const bool frag_scope = hit && plan.fragment_scope;
     const bool served_now = frag_scope && c->frags.serves(key);       // a later hit: the scorer writes every row's sums whole, nothing to clear
     if (ev) HIP_TRY(c, hipEventRecord(ev[0], c->stream));
-    // Few candidates (descent pairs, flips): one workgroup per (tile, candidate) would leave most of the chip idle,
-    // so the meshlets of each tile are split over several workgroups that merge into a tile in global memory.
-    int split = 1;
-    if (!layers && !(c->strategy & STRATEGY_NO_SPLIT)) {
-        // about a third of a frame's tiles hold the robot (all of them when the frame is one or two tiles): the others' workgroups
-        // leave at once.  Too few shares per tile make each workgroup's chain of meshlets long: a floor, lower once the
-        // launch runs to several generations of workgroups anyway (every share pays for clearing and scanning its LDS tile).
-        const int busy_tiles = std::max(std::min(2, c->n_tiles), c->n_tiles / 3);
-        const int floor_ = c->C * busy_tiles <= 256 ? c->split_min : c->split_min_many;
-        split = std::max(std::min(c->split_cap, c->split_target / std::max(1, c->C * busy_tiles)), std::min(floor_, c->split_cap));
-        if (split < 2 || c->C * busy_tiles > 4 * c->split_target) split = 1;       // enough (tile, candidate) pairs to fill the chip whole
-    }
-    // With the split, every workgroup can work out what it needs of the geometry itself — its candidate's six link matrices and
-    // the screen boxes of its own share of the meshlets: the fk + boxes launch (10 us of a 60 us evaluation, most of it the launch)
-    // goes.  (Not for the camera-pose path, whose rows name their own view matrices.)
-    // Up to a few dozen rows: from 64 on, the launch saved is no more than what the matrices cost when every share of every row repeats them.
-    // And on frames of a few tiles only (the Predictor's 160x90 is two): on a 25-tile frame two thirds of the workgroups belong to tiles
-    // the robot does not reach — the masks of the separate launch let them leave at once, here each would do the matrices first.
-    const bool geo = split > 1 && !views && c->C <= c->geo_rows && c->n_tiles <= 4 && !(c->strategy & STRATEGY_SEPARATE_GEOMETRY);
     if (served_now) { }
     else if (hit) HIP_TRY(c, launch_clear_pass(c->stream, c->d_sums, c->C, c->d_qctr));      // what is left of fk_mvp_kernel: cleared sums and queue counters
-    else if (!geo) { RopeRange r("rope:fk+bounds"); int rc = enqueue_geometry(c, n_render, n_shared, fp, views); if (rc) return rc; }
+    else if (!geo) { RopeRange r("rope:fk+bounds"); int rc = enqueue_geometry(c, plan, n_render, fp, views); if (rc) return rc; }
     c->mvp_valid = !geo;
     if (ev) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
     RasterArgs a = base_args(c, n_render);
@@ -769,9 +731,9 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
         RasterArgs sa = a;
         sa.split = split; sa.gtile = c->d_gtile;
         if (geo) {
-            if ((size_t)c->C * c->n_tiles > c->d_touched.cap()) {      // C <= geo_rows <= 256: room for any such batch at once
-                if (int rc = sync_grow(c, c->d_touched, (size_t)256 * c->n_tiles)) return rc;
-                HIP_TRY(c, hipMemsetAsync(c->d_touched, 0, (size_t)256 * c->n_tiles * sizeof(int), c->stream));     // ordered with the kernels that stamp it
+            if ((size_t)c->C * c->n_tiles > c->d_touched.cap()) {      // C <= geo_rows <= OWN_GEOMETRY_MAX_ROWS: room for any such batch at once
+                if (int rc = sync_grow(c, c->d_touched, (size_t)OWN_GEOMETRY_MAX_ROWS * c->n_tiles)) return rc;
+                HIP_TRY(c, hipMemsetAsync(c->d_touched, 0, (size_t)OWN_GEOMETRY_MAX_ROWS * c->n_tiles * sizeof(int), c->stream));     // ordered with the kernels that stamp it
             }
             sa.cand_q = c->cand_dev; sa.joint_fixed = c->d_joint_fixed; sa.joint_axes = c->d_joint_axes; sa.PV = c->d_PV;
             sa.sums = c->d_sums;
@@ -783,7 +745,7 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
             sa.pass_id = ++c->pass_id;
             a.touched = sa.touched; a.pass_id = sa.pass_id;
         }
-        HIP_TRY(c, launch_raster(geo ? MODE_SPLIT_GEO : MODE_SPLIT, loss, c->C, c->stream, fp, c->rp, sa, use_clip(c, views)));
+        HIP_TRY(c, launch_raster(geo ? MODE_SPLIT_GEO : MODE_SPLIT, loss, c->C, c->stream, fp, c->rp, sa, plan.clip));
         a.gtile = c->d_gtile;
     }
     if (layers) {
@@ -794,7 +756,7 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
             RopeRange r("rope:layer-sums");
             la.cand_of_row = c->d_layer_rep; la.layers = c->d_layers;
             HIP_TRY(c, launch_layer_sums(loss, c->n_layers, c->stream, fp, la));
-        } else { RopeRange r("rope:shared-layers"); int rc = enqueue_layers(c, la, loss, n_shared, fp); if (rc) return rc; }
+        } else { RopeRange r("rope:shared-layers"); int rc = enqueue_layers(c, plan, la, loss, fp); if (rc) return rc; }
         a.l_begin = n_shared; a.layer_of = c->d_layer_of; a.layer_rep = c->d_layer_rep; a.layers = c->d_layers; a.layer_sums = c->d_layer_sums;
     }
     a.tq = pl.tq; a.t32 = pl.t32; a.tl = pl.tl; a.frame_of = pl.frame_of; a.sums = c->d_sums;
@@ -805,7 +767,7 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
         if (frag_scope) {
             // first hit: build the store, inside this pass (and this interval of rope_profile_eval); when the count shows it would
             // not fit the budget it is declined for this key and the pass, like every later one, runs as before
-            if (!served_now && !c->frags.refused(key)) { int rc = build_fragments(c, key, a, loss, fp); if (rc) return rc; }
+            if (!served_now && !c->frags.refused(key)) { int rc = build_fragments(c, plan, key, a, loss, fp); if (rc) return rc; }
             if (c->frags.serves(key)) {
                 HIP_TRY(c, launch_fragment_score(loss, c->C, c->stream, fp, a, c->d_foffs, c->d_fwhere, c->d_ffin, c->d_fbase));
                 c->frags.passes_served++;
@@ -813,17 +775,15 @@ int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, dou
             }
         }
         if (served) { }
-        else if (split > 1) {
-            int slices = 1;
-            while (slices < 8 && c->C * c->n_tiles * slices * 2 <= c->score_target) slices *= 2;
-            HIP_TRY(c, launch_score_gtile(loss, c->C, slices, c->stream, fp, a));
+        else if (plan.scoring == SCORE_GTILE) {
+            HIP_TRY(c, launch_score_gtile(loss, c->C, plan.slices, c->stream, fp, a));
             c->gtile_dirty = ROPE_SKIP(fp, ~0);
-        } else if (c->C > 256 && !(c->strategy & STRATEGY_NO_QUEUE)) {
-            // fk_mvp_kernel ran (C > 256) and cleared the queue counters; two 12-wave workgroups fit a CU
-            HIP_TRY(c, launch_raster_queue(loss, c->C, 2 * c->n_cu, c->stream, fp, c->rp, a, c->d_qitems, queue_weights(c) ? c->q_segment : 0, c->d_qctr, queue_weights(c),
-                                           use_clip(c, views)));
+        } else if (plan.scoring == SCORE_QUEUE) {
+            // two 12-wave workgroups fit a CU
+            HIP_TRY(c, launch_raster_queue(loss, c->C, QUEUE_WG_PER_CU * c->n_cu, c->stream, fp, c->rp, a, c->d_qitems, plan.weighted ? c->q_segment : 0, c->d_qctr,
+                                           queue_weights(c, plan), plan.clip));
         } else {
-            HIP_TRY(c, launch_raster(MODE_SCORE, loss, c->C, c->stream, fp, c->rp, a, use_clip(c, views)));
+            HIP_TRY(c, launch_raster(MODE_SCORE, loss, c->C, c->stream, fp, c->rp, a, plan.clip));
         }
     }
     if (ev) HIP_TRY(c, hipEventRecord(ev[3], c->stream));
@@ -920,11 +880,12 @@ static int raster_only(rope_ctx *c, const double *cand, int C, int n_render, int
     if (n_render < 1 || n_render > c->n_links) ARG_FAIL(c, "render: n_render out of range");
     int rc = rope_candidates_upload(c, cand, C);
     if (rc) return rc;
-    rc = enqueue_geometry(c, n_render, 0, c->fp, false);
+    const PassPlan plan = plan_geometry(pass_inputs(c, n_render, ROPE_LOSS_DEPTH, c->fp, EVAL_SINGLE, false, use_clip(c)), false);
+    rc = enqueue_geometry(c, plan, n_render, c->fp, false);
     if (rc) return rc;
     RasterArgs a = base_args(c, n_render);
     a.cover = c->d_cover;
-    HIP_TRY(c, launch_raster(mode, ROPE_LOSS_DEPTH, c->C, c->stream, c->fp, c->rp, a, use_clip(c)));
+    HIP_TRY(c, launch_raster(mode, ROPE_LOSS_DEPTH, c->C, c->stream, c->fp, c->rp, a, plan.clip));
     c->last_n_render = n_render;
     return ROPE_OK;
 }
@@ -1013,7 +974,7 @@ static int render_chunks(rope_ctx *c, const RenderAsk &ask, const double *q, con
         c->dv_view_of = PV ? reinterpret_cast<const int32_t *>(c->d_vstage + off_vo) : nullptr;
         c->C = n;
         c->n_layers = n;                                      // nothing shared: every row draws all its links
-        rc = enqueue_geometry(c, n_render, 0, fp, true);
+        rc = enqueue_geometry(c, plan_geometry(pass_inputs(c, n_render, ROPE_LOSS_DEPTH, fp, EVAL_SINGLE, false, clip), false), n_render, fp, true);
         if (rc) return rc;
         if (ask.depth) HIP_TRY(c, hipMemsetAsync(c->d_rdepth, 0, (size_t)n * px * sizeof(float), c->stream));
         if (ask.ids) HIP_TRY(c, hipMemsetAsync(c->d_rids, 0xFF, (size_t)n * px, c->stream));
@@ -1138,20 +1099,22 @@ extern "C" int rope_lookup_build(rope_ctx *c, const double *cand, int C, int n_r
         const int n = std::min(MAX_ROWS, C - lo);
         int rc = rope_candidates_upload(c, cand + 6 * (size_t)lo, n);
         if (rc) return rc;
-        const bool layers = want_layers(c);
-        const int n_shared = layers ? std::min(3, n_render) : 0;
+        // (a table is built once: shared layers whenever the rows share, whatever the strategy says about scoring passes)
+        const PassPlan plan = plan_geometry(pass_inputs(c, n_render, ROPE_LOSS_LOOKUP, fp, EVAL_SINGLE, false, use_clip(c)), layers_wanted(c->n_layers, c->C));
+        const bool layers = plan.layers;
+        const int n_shared = plan.n_shared;
         if (layers) { rc = ensure_layers(c); if (rc) return rc; }
-        rc = enqueue_geometry(c, n_render, n_shared, fp, false);
+        rc = enqueue_geometry(c, plan, n_render, fp, false);
         if (rc) return rc;
         RasterArgs a = base_args(c, n_render);
         if (layers) {
             // layer pass without loss sums (layer_sums == nullptr): no target is needed to build a table
-            rc = enqueue_layers(c, a, ROPE_LOSS_DEPTH, n_shared, c->fp);
+            rc = enqueue_layers(c, plan, a, ROPE_LOSS_DEPTH, c->fp);
             if (rc) return rc;
             a.l_begin = n_shared; a.layer_of = c->d_layer_of; a.layer_rep = c->d_layer_rep; a.layers = c->d_layers;
         }
         a.table = c->d_table + (size_t)lo * px;
-        HIP_TRY(c, launch_raster(MODE_TABLE, ROPE_LOSS_LOOKUP, c->C, c->stream, fp, c->rp, a, use_clip(c)));
+        HIP_TRY(c, launch_raster(MODE_TABLE, ROPE_LOSS_LOOKUP, c->C, c->stream, fp, c->rp, a, plan.clip));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     // keep of every row only the groups of samples that hold something (the crop is the box of all poses together, and a pose
@@ -1228,10 +1191,7 @@ extern "C" int rope_debug_mvp(rope_ctx *c, float *mvp_out, int C, int n_render)
     if (!c->mvp_valid) {
         // the last pass worked the matrices out inside its raster workgroups: form them the way any other pass does
         if (!c->cand_valid) ARG_FAIL(c, "rope_debug_mvp: no resident candidates");
-        const int keep = c->strategy;
-        c->strategy |= STRATEGY_SEPARATE_GEOMETRY;
-        const int rc = enqueue_geometry(c, n_render, 0, c->fp, false);
-        c->strategy = keep;
+        const int rc = enqueue_geometry(c, plan_geometry(pass_inputs(c, n_render, ROPE_LOSS_DEPTH, c->fp, EVAL_SINGLE, false, use_clip(c)), false), n_render, c->fp, false);
         if (rc) return rc;
         c->results_valid = false;                     // that launch cleared the sums
         c->mvp_valid = true;

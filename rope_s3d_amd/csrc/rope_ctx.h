@@ -14,6 +14,7 @@
 #include "rope_fragstore.h"
 #include "rope_geomcache.h"
 #include "rope_kernels.h"
+#include "rope_passplan.h"
 
 using namespace rope;
 
@@ -179,11 +180,7 @@ struct rope_ctx {
     bool mvp_valid = false;                // d_mvp holds the resident candidates' matrices (not after a pass that kept them in LDS)
     DevBuf<uint32_t> d_gtile;
     bool gtile_dirty = true;
-    // MODE_SPLIT: busy workgroups aimed at per launch (one generation: 2 per CU), fewest / most per (tile, candidate), and the
-    // workgroups per launch of the scoring pass that follows.  Measured at 160x90, 640x360 and 640x480 (tools/r02_split_tune.sh).
-    int split_target = 512, split_min = 8, split_min_many = 3, split_cap = 64, score_target = 6144;
-    int geo_rows = 48;                     // most rows of a small batch whose raster workgroups do their own forward kinematics and boxes
-    int layer_min_wg = 64;                 // fewest busy workgroups of a shared-layer launch for it to pay in a small batch (layers_pay)
+    PassTunables tune;                     // the numbers the launch structure is chosen by (rope_passplan.h; rope_create reads the environment)
     int strategy = 0;                          // STRATEGY_* bits (rope_set_strategy): launch structure only, never a result
     // large batches: queue of the (candidate, tile) pairs with something to draw, worked off by a grid that just fills the chip
     DevBuf<uint32_t> d_qitems, d_tile_tris, d_tile_tris_lo;
@@ -327,9 +324,6 @@ struct EvalPlanes {
     const uint64_t *tl;                     // per-link planes (ROPE_LOSS_CAMFULL), or nullptr
     const int32_t *frame_of;                // nullptr: every row against the one frame
 };
-// Who finalises: EVAL_SINGLE errors and their argmin against the single target's totals and flags; EVAL_TARGETS every row against its
-// own frame's (no argmin: rows of many frames), up to TARGET_HOST_ROWS rows through mapped host memory; EVAL_VIEWS nobody — the rows
-// are (view, frame) pairs with a view matrix of their own and no shared layers, and rope_eval_views takes the sums as they are.
-enum EvalKind { EVAL_SINGLE, EVAL_TARGETS, EVAL_VIEWS };
+// (EvalKind, who finalises: rope_passplan.h)
 int enqueue_eval(rope_ctx *c, int n_render, int loss, const FrameParams &fp, double n_pix, const EvalPlanes &pl, EvalKind kind,
                  hipEvent_t *ev = nullptr /* 5 events */);

@@ -10,14 +10,11 @@ DESIGN.md §6a records.  So each case here builds a batch for which the host cod
   * holds about ten sampled rows to the CPU oracle, bit for bit;
   * where the camera is near, counts on the CPU (cut_triangles) that triangles of the sampled rows do cross the near plane.
 
-Which kernel a batch gets (rope_abi.hip):
-  Q  enqueue_eval: the scoring queue (raster_queue_kernel<.., SCORE, ..>) for more than 256 rows when the batch is not split,
-     and a batch without layers is split unless rows * busy_tiles > 2048 (busy_tiles = max(min(2, tiles), tiles / 3): 2 at
-     160x120, 3 at 320x240) — so 1025 rows or more at 160x120, 683 or more at 320x240; with layers there is no split;
-  L  enqueue_layers + queue_weights: the layer queue (raster_queue_kernel<.., LAYER, ..>) when layers are engaged (4 x distinct
-     (S, L) pairs <= rows, and more than 256 rows), the frame has at most 256 tiles and rows * busy_tiles <= 512 x CUs;
-  S  256 rows or fewer and rows * busy_tiles <= 2048: the split path, raster_score_kernel<DEPTH, SPLIT, ..> + score_gtile_kernel;
-  C  use_clip: the CLIP kernels when near_plane_in_reach(camera) — on the camera-pose path, when it holds for ANY view of the call.
+Which kernel a batch gets is plan_pass() of csrc/rope_passplan.h, where the rules and their thresholds are: the cases below name
+them Q (the scoring queue, raster_queue_kernel<.., SCORE, ..>), L (the layer queue, raster_queue_kernel<.., LAYER, ..>), S (the split
+path, raster_score_kernel<DEPTH, SPLIT, ..> + score_gtile_kernel) and C (the CLIP kernels: use_clip of rope_abi.hip, the camera within
+the robot's reach of the near plane — on the camera-pose path, ANY view of the call).  tests/test_passplan_host.py pins the plan of
+every batch built here, at the borders the cases count on.
 profiles/kernel_trace_instantiations.txt lists the kernels a run of the GPU suite launched.
 """
 import os
