@@ -420,9 +420,14 @@ int rope_depth_holes(float *depth_dev, int N, int H, int W, uint32_t frame0, uin
  * n_frames x 8 flag bytes; any pointer may be NULL. */
 int rope_debug_targets(rope_ctx *ctx, uint64_t *tq, float *t32, float *t32_tsweep, uint8_t *flags);
 
+/* The number of resident targets (rope_set_targets / rope_commit_targets); 0 when there are none — nothing set yet, a single
+ * target (rope_set_target) only, or the planes taken by rope_set_frames — and for a NULL context. */
+int rope_resident_targets(rope_ctx *ctx);
+
 /* rope_predict for the n_frames resident targets of rope_set_targets, in lockstep: the same stage list, limits and camera for all of
  * them (args as rope_predict; lookup_angles_live must be NULL — the table aliasing makes frames depend on their order — and so must
- * on_eval).  A frame
+ * on_eval).  n_frames must EQUAL the number of resident targets (rope_resident_targets): frame f is resident target f, and any other
+ * count, smaller or larger, is refused with ROPE_E_ARG before anything runs.  A frame
  * that leaves a Descent stage early simply contributes no rows to the later batches of that stage.  Every frame's angles and trace
  * are those of rope_predict on that frame alone.
  *   angles_out  n_frames x 6;  trace_out  n_frames x n_stages x 6 or NULL;  n_evals  total poses rendered and scored, or NULL */

@@ -16,6 +16,15 @@ from . import oracle as orc
 
 HISTORY_LENGTH = 5                                   # predict.py:30
 
+# what predict_reference(events=...) can report, per stage kind
+EVENT_LABELS = {
+    'descent': ('init_rate_set', 'lr_cut', 'under_outside', 'over_outside', 'step_over', 'step_under', 'step_tie',
+                'break_err', 'break_spread', 'break_still', 'ran_out'),
+    'sflip': ('sign0', 'inside_taken', 'inside_kept', 'outside', 'close', 'endpoint_taken', 'endpoint_kept'),
+    'isweep': ('which0', 'which1', 'which2', 'clip_lo', 'clip_hi', 'whole_range', 'nan_spline', 'spline_tie'),
+    'tsweep': ('clip_lo', 'clip_hi', 'whole_range', 'one_division', 'all_nan'),
+}
+
 # stage lists, written out as data (robotpose/prediction/stages.py:138-168)
 STAGES = {
     'SL': [('lookup',), ('sflip', 4), ('isweep', 4, 10, 'L', 0.1), ('isweep', 4, 10, 'S', 0.1), ('sflip', 4)],
@@ -32,7 +41,7 @@ def _mask(letters):
 
 def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue, joint_limits, camera_pose,
                       lookup_angles, lookup_crop, do_angles='SLU', min_ang_inc=None, stages=None, seg_masks=None,
-                      lookup_depth=None, lookup_live=None, evaluated=None):
+                      lookup_depth=None, lookup_live=None, evaluated=None, events=None):
     """-> (final angles, trace [(stage kind, angles after it)], number of E(a) evaluations).
 
     Synthetic mode (default): masks are read from `tgt_blue` as _loadSynthetic does.  Segmentation mode:
@@ -47,7 +56,15 @@ def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue,
     None: every frame starts from a copy of the grid row.
 
     `evaluated`: a list that receives (links drawn, pose) of every pose rendered after the Lookup grid, in the order
-    rendered (the reference's preview shows exactly those, predict.py:153-157)."""
+    rendered (the reference's preview shows exactly those, predict.py:153-157).
+
+    `events`: a list that receives a label '<stage kind>.<branch>' at every decision, in order (EVENT_LABELS has them all): which
+    way each branch below went.  It is written to and never read: the run is the same with and without it."""
+    kind = None
+
+    def note(label):
+        if events is not None:
+            events.append(kind + '.' + label)
     min_ang_inc = np.array([.005] * 6) if min_ang_inc is None else np.asarray(min_ang_inc, float)
     tgt_depth = np.asarray(tgt_depth, np.float64)
     H, W = tgt_depth.shape
@@ -116,45 +133,73 @@ def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue,
                 for i in range(6):
                     if init_rate[i] is not None:
                         lr[i] = init_rate[i]
+                        note('init_rate_set')
                 for _ in range(its):
                     for idx in np.where(_mask(letters))[0]:
                         if abs(np.mean(history, 0)[idx] - angles[idx]) <= lr[idx]:
                             lr[idx] *= redux
+                            note('lr_cut')
                         lr = np.max((lr, min_ang_inc), 0)
                         temp = angles.copy()
                         temp[idx] -= lr[idx]
-                        under_err = E(n, temp) if lim[idx][0] <= temp[idx] <= lim[idx][1] else np.inf
+                        if lim[idx][0] <= temp[idx] <= lim[idx][1]:
+                            under_err = E(n, temp)
+                        else:
+                            under_err = np.inf
+                            note('under_outside')
                         temp[idx] += 2 * lr[idx]
-                        over_err = E(n, temp) if lim[idx][0] <= temp[idx] <= lim[idx][1] else np.inf
+                        if lim[idx][0] <= temp[idx] <= lim[idx][1]:
+                            over_err = E(n, temp)
+                        else:
+                            over_err = np.inf
+                            note('over_outside')
                         if over_err < under_err:
                             angles[idx] += lr[idx]
+                            note('step_over')
                         elif over_err > under_err:
                             angles[idx] -= lr[idx]
+                            note('step_under')
+                        else:
+                            note('step_tie')
                     history[1:] = history[:-1]
                     history[0] = angles
                     err_history[1:] = err_history[:-1]
                     err_history[0] = min(over_err, under_err)
                     if abs(np.mean(err_history) - err_history[0]) / err_history[0] < early:
+                        note('break_err')
                         break
                     sp = history.max(0) - history.min(0)
                     if ((sp <= min_ang_inc) + np.isclose(sp, min_ang_inc)).all():
+                        note('break_spread')
                         break
                     if (history[:3] == history[0]).all():
+                        note('break_still')
                         break
+                else:
+                    note('ran_out')
 
             elif kind == 'sflip':                      # predict.py:232-281
                 n = st[1]
                 base_err = E(n, angles)
                 temp = angles.copy()
                 a = cam[5] * np.abs(np.cos(cam[3])) + cam[4] * np.abs(np.sin(cam[3]))
+                if np.sign(temp[0]) == 0:
+                    note('sign0')
                 temp[0] = -temp[0] + 2 * a * np.sign(temp[0])
                 close = 0.15 > abs(lim[0, 0] - temp[0]) or 0.15 > abs(lim[0, 1] - temp[0])
                 inside = lim[0, 0] <= temp[0] <= lim[0, 1]
+                if not inside:
+                    note('outside')
+                if close:
+                    note('close')
                 if inside:
                     err = E(n, temp)
                     if err < base_err:
                         angles = temp
                         base_err = err
+                        note('inside_taken')
+                    else:
+                        note('inside_kept')
                 if not inside or close:
                     for endpoint in lim[0]:            # comparison is outside the loop in the reference
                         temp[0] = endpoint
@@ -162,6 +207,9 @@ def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue,
                     if err < base_err:
                         angles = temp
                         base_err = err
+                        note('endpoint_taken')
+                    else:
+                        note('endpoint_kept')
 
             elif kind == 'isweep':                     # predict.py:283-338
                 _, n, div, letters, rng = st
@@ -170,18 +218,31 @@ def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue,
                     lo, hi = angles.copy(), angles.copy()
                     if rng is None:
                         lo[idx], hi[idx] = lim[idx, 0], lim[idx, 1]
+                        note('whole_range')
                     else:
+                        if lim[idx, 0] > lo[idx] - rng:
+                            note('clip_lo')
+                        if lim[idx, 1] < hi[idx] + rng:
+                            note('clip_hi')
                         lo[idx] = max(lo[idx] - rng, lim[idx, 0])
                         hi[idx] = min(hi[idx] + rng, lim[idx, 1])
                     space = np.linspace(lo, hi, div)
                     space_err = [E(n, a_) for a_ in space]
                     x = np.linspace(lo[idx], hi[idx], div * 5)
                     pred = interp1d(space[:, idx], np.array(space_err), kind='cubic')(x)
+                    if np.isnan(pred).all():
+                        note('nan_spline')
+                    elif np.sum(pred - pred.min() <= 1e-9 * max(1.0, abs(pred.min()))) > 1:
+                        # a second point of the spline within 1e-9 of its minimum (equal samples, or two samples that tie for
+                        # the smallest): which one argmin takes is rounding noise of interp1d's solver, so the pose rendered
+                        # next is not a decision another implementation of the same spline can be held to
+                        note('spline_tie')
                     angs = angles.copy()
                     angs[idx] = x[pred.argmin()]
                     pred_min_err = E(n, angs)
                     errs = [base_err, min(space_err), pred_min_err]
                     which = errs.index(min(errs))
+                    note('which%d' % which)
                     if which == 1:
                         angles = space[space_err.index(min(space_err))]
                         err_history[1:] = err_history[:-1]
@@ -199,10 +260,17 @@ def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue,
                     lo, hi = angles.copy(), angles.copy()
                     if rng is None:
                         lo[idx], hi[idx] = lim[idx, 0], lim[idx, 1]
+                        note('whole_range')
                     else:
+                        if lim[idx, 0] > lo[idx] - rng:
+                            note('clip_lo')
+                        if lim[idx, 1] < hi[idx] + rng:
+                            note('clip_hi')
                         lo[idx] = max(lo[idx] - rng, lim[idx, 0])
                         hi[idx] = min(hi[idx] + rng, lim[idx, 1])
                     space = np.linspace(lo, hi, div)
+                    if div == 1:
+                        note('one_division')
                     score = np.empty(div)
                     for i, a_ in enumerate(space):
                         if evaluated is not None:
@@ -210,6 +278,8 @@ def predict_reference(o: orc.Oracle, tgt_depth, tgt_blue, link_names, link_blue,
                         key = o.raster_key(a_, n)
                         score[i] = o.finalize(o.sums(key, orc.LOSS_TSWEEP, n, None, t_full), orc.LOSS_TSWEEP, n, n_pix, flags)
                     count[0] += div
+                    if np.isnan(score).all():
+                        note('all_nan')
                     angles = space[int(np.argmin(score))]               # mean * -std: the `*-` of predict.py:367
             else:
                 raise ValueError(kind)

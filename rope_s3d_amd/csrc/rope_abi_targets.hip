@@ -366,6 +366,9 @@ extern "C" int rope_debug_targets(rope_ctx *c, uint64_t *tq, float *t32, float *
     return rc;
 }
 
+// How many targets are resident: what rope_predict_batch (rope_predict.cpp, written against the public ABI) holds n_frames to
+extern "C" int rope_resident_targets(rope_ctx *c) { return c ? c->n_targets() : 0; }
+
 // The staged set becomes the resident one (and the resident buffers the next staging space): waits for the upload and for the
 // context's own stream, then swaps the sets whole — a buffer the staged set did not fill comes along unread (has_t32 / has_ts).
 extern "C" int rope_commit_targets(rope_ctx *c)

@@ -25,6 +25,9 @@
 void rope_set_error(rope_ctx *c, const std::string &msg);       // rope_abi.hip
 void rope_range_push(const char *name);                         // roctx ranges, one per stage (rope_abi.hip; no-ops without the library)
 void rope_range_pop();
+// A weak reference: the library always has it (rope_abi_targets.hip).  A host build of this file over stand-ins for the ABI that
+// offer no resident count still links and loads — rope_predict runs there; rope_predict_batch, which cannot check n_frames, refuses.
+extern "C" int rope_resident_targets(rope_ctx *ctx) __attribute__((weak));
 
 namespace {
 
@@ -101,9 +104,11 @@ void push_front(double (*hist)[6], const Vec6 &v)
 }
 
 // np.linspace(start, stop, num)[i] for scalar arguments (numpy/_core/function_base.py): i*step + start, unless the
-// step is zero; the last sample is `stop` itself
+// step is zero; the last sample is `stop` itself — but only when there is more than one (numpy: `if endpoint and num > 1`):
+// np.linspace(start, stop, 1) is [start], computed as 0 * delta + start (a start of -0.0 comes out as +0.0)
 double linspace_scalar(double start, double stop, int num, int i)
 {
+    if (num == 1) return 0.0 * (stop - start) + start;
     if (i == num - 1) return stop;
     const double div = (double)(num - 1), delta = stop - start, step = delta / div;
     return step == 0.0 ? ((double)i / div) * delta + start : (double)i * step + start;
@@ -113,6 +118,11 @@ double linspace_scalar(double start, double stop, int num, int i)
 // down its (i / div) * delta + start formula for every column
 Vec6 linspace_rows(const Vec6 &lo, const Vec6 &hi, int num, int i)
 {
+    if (num == 1) {                                             // one sample: the start, as np.linspace(lo, hi, 1) — 0 * delta + lo
+        Vec6 r;
+        for (int j = 0; j < 6; j++) r[j] = 0.0 * (hi[j] - lo[j]) + lo[j];
+        return r;
+    }
     if (i == num - 1) return hi;
     Vec6 r;
     const double div = (double)(num - 1);
@@ -476,6 +486,16 @@ int run_stages(rope_ctx *c, const rope_predict_args *a, bool batch, int B, doubl
     if (batch && a->lookup_angles_live) return fail("rope_predict_batch: the reference's table aliasing makes frames depend on their order (lookup_angles_live must be NULL)");
     if (batch && a->on_eval) return fail("rope_predict_batch: on_eval is for one frame (rope_predict); it must be NULL");
     if (B < 1) return fail("rope_predict_batch: no frames");
+    if (batch) {
+        // one state per resident target: rope_lookup_score_targets writes one entry per resident target, and every row names its frame
+        if (!rope_resident_targets) return fail("rope_predict_batch: this build cannot tell how many targets are resident (no rope_resident_targets)");
+        const int resident = rope_resident_targets(c);
+        if (B != resident) {
+            rope_set_error(c, "rope_predict_batch: n_frames is " + std::to_string(B) + " but " + std::to_string(resident) +
+                                  " targets are resident (rope_set_targets / rope_commit_targets): they must be equal");
+            return (int)ROPE_E_ARG;
+        }
+    }
     for (int i = 0; i < a->n_stages; i++) {
         const rope_stage &s = a->stages[i];
         switch (s.kind) {

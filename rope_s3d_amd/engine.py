@@ -34,7 +34,7 @@ ABI_SYMBOLS = (
     'rope_seg_rpn_targets', 'rope_seg_roi_targets', 'rope_seg_roi_align_float', 'rope_seg_roi_align_backward',
     'rope_set_target_tsweep', 'rope_set_targets', 'rope_stage_targets', 'rope_commit_targets', 'rope_eval_targets', 'rope_lookup_score_targets', 'rope_predict_batch',
     'rope_prepare_synthetic', 'rope_host_alloc', 'rope_host_free', 'rope_build_id', 'rope_camera_matrix', 'rope_lookup_grid', 'rope_crop_divisions',
-    'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets',
+    'rope_prepare_segmented', 'rope_stage_targets_segmented', 'rope_debug_targets', 'rope_resident_targets',
     'rope_render_batch_device', 'rope_stage_targets_synthetic', 'rope_hole_thresholds', 'rope_depth_holes', 'rope_frame_agreement',
     'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align',
     'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace', 'rope_camera_normal_equations',
@@ -208,6 +208,7 @@ def load_library(path: str = None):
     lib.rope_commit_targets.argtypes = [vp]
     lib.rope_stage_targets_segmented.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, vp]
     lib.rope_debug_targets.argtypes = [vp, vp, vp, vp, vp]
+    lib.rope_resident_targets.argtypes = [vp]
     lib.rope_render_batch_device.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.rope_stage_targets_synthetic.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp]
     lib.rope_hole_thresholds.argtypes = [dbl, dbl, i32, vp, C.POINTER(i32)]

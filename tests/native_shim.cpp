@@ -1,6 +1,6 @@
 // Test scaffolding only: lets rope_predict.cpp (pure host code over the C ABI) run WITHOUT the HIP engine, by
 // answering its rope_eval calls through a callback the test installs (which scores the poses with the CPU oracle).
-// Built by tests/test_native_host.py into a scratch directory; never part of librope_hip.so.
+// Built by tests/test_native_host.py and tests/test_stage_landscapes_host.py into a scratch directory; never part of librope_hip.so.
 #include <cstdint>
 #include <string>
 
@@ -28,8 +28,19 @@ int rope_eval(rope_ctx *, const double *cand, int C, int n_render, int loss, con
     return g_cb ? g_cb(cand, C, n_render, loss, crop, err_out, best_idx) : ROPE_E_ARG;
 }
 
-int rope_lookup_score(rope_ctx *, double *, int32_t *, double *)
+// The stored table's two entry points are answered by callbacks as well, once a test installs them (without one: no table).  A
+// callback fills best_idx — one entry for rope_lookup_score, `n` = the resident count for rope_lookup_score_targets, which is how
+// many the library's call writes whatever its caller expected.
+typedef int (*shim_table_cb)(int32_t *best_idx, int n);
+static shim_table_cb g_table_cb = nullptr, g_table_targets_cb = nullptr;
+static int g_resident = 0;       // what rope_resident_targets answers: the test sets it as rope_set_targets would
+void shim_set_table_callbacks(shim_table_cb one, shim_table_cb targets) { g_table_cb = one; g_table_targets_cb = targets; }
+void shim_set_resident(int n) { g_resident = n; }
+int rope_resident_targets(rope_ctx *) { return g_resident; }
+
+int rope_lookup_score(rope_ctx *, double *, int32_t *best_idx, double *)
 {
+    if (g_table_cb) return g_table_cb(best_idx, 1);
     g_err = "shim: no stored table";
     return ROPE_E_ARG;
 }
@@ -44,8 +55,9 @@ int rope_eval_targets(rope_ctx *, const double *cand, const int32_t *frame_of, i
     return g_tcb ? g_tcb(cand, frame_of, R, n_render, loss, crop, err_out) : ROPE_E_ARG;
 }
 
-int rope_lookup_score_targets(rope_ctx *, int32_t *, double *, double *)
+int rope_lookup_score_targets(rope_ctx *, int32_t *best_idx, double *, double *)
 {
+    if (g_table_targets_cb) return g_table_targets_cb(best_idx, g_resident);
     g_err = "shim: no stored table";
     return ROPE_E_ARG;
 }

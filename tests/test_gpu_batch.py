@@ -302,3 +302,78 @@ def test_predict_batch_segmentation_path_and_tensor_sweep():
                                   blue=resize_linear(colors[i], intr.width, intr.height)[..., 0], link_blue=link_blue, stages=ref_stages)
     finally:
         predict_mod.getStages = orig
+
+
+# ---- the n_frames rule and a one-division TensorSweep, at 80x60 (seconds each)
+
+@pytest.fixture(scope='module')
+def small():
+    """Engine and CPU oracle at 80x60, three rendered frames resident with all their planes, a 27-row grid and its stored table."""
+    import stage_landscapes
+    rb = helpers.robot()
+    lim = rb.joint_limits
+    intr, PV = helpers.camera('640_480_color', ds=8, as_predictor=True)
+    e = eng.Engine(0)
+    e.set_robot(rb)
+    e.set_camera(PV, intr.width, intr.height, ZNEAR, ZFAR)
+    o = helpers.make_oracle(rb, intr, PV)
+    rng = np.random.default_rng(2718)
+    frames = []
+    for _ in range(3):
+        q = rng.uniform(lim[:, 0], lim[:, 1]) * np.array([1, 1, 1, 0, 0, 0])
+        depth, ids = o.render(q, 6)
+        tq, t32, flags, tgt, _, _ = helpers.synthetic_target(depth, ids)
+        blue = np.where(ids == 255, 0, np.asarray(LINK_BLUE)[np.minimum(ids, 5)]).astype(np.uint8)
+        frames.append(dict(tq=tq, t32=t32, flags=flags, tgt=tgt, blue=blue, full=np.ascontiguousarray(tgt, np.float32)))
+    grid = helpers.slu_grid(lim, 3)
+    crop = np.array([0, intr.height - 1, 0, intr.width - 1], np.int32)
+    e.lookup_build(grid, 6, crop)
+    e.set_targets(*(np.stack([f[k] for f in frames]) for k in ('tq', 't32', 'flags', 'full')))
+    return e, o, rb, frames, grid, crop, stage_landscapes.native_stages
+
+
+def test_predict_batch_refuses_a_frame_count_other_than_the_resident_one(small):
+    """Three targets resident: rope_predict_batch with n_frames 2 and 4, with and without the stored table, answers ROPE_E_ARG and
+    names both counts; the context then predicts the three frames exactly as it did before."""
+    import ctypes as C
+    e, o, rb, frames, grid, crop, native_stages = small
+    lim = rb.joint_limits
+    stages = native_stages(predictor_ref.STAGES['SL'])
+    inc = np.array([.005] * 6)
+    before = {t: e.predict_batch(stages, lim, DEFAULT_CAMERA_POSE, inc, grid, crop, use_table=t) for t in (True, False)}
+    assert e._lib.rope_resident_targets(e._ctx) == 3 == e.n_targets
+    for use_table in (True, False):
+        a, keep = e._predict_args(stages, lim, DEFAULT_CAMERA_POSE, inc, grid, crop, use_table, 3, None)
+        for n_frames in (2, 4):
+            out, trace, cnt = np.full((4, 6), -7.0), np.full((4, len(stages), 6), -7.0), C.c_int64(-1)
+            rc = e._lib.rope_predict_batch(e._ctx, C.byref(a), n_frames, out.ctypes.data_as(C.c_void_p), trace.ctypes.data_as(C.c_void_p), C.byref(cnt))
+            assert rc == -1, (use_table, n_frames)
+            msg = e._lib.rope_last_error(e._ctx).decode()
+            assert str(n_frames) in msg and '3' in msg and 'resident' in msg, msg
+            assert (out == -7.0).all() and (trace == -7.0).all() and cnt.value == -1          # refused before anything ran
+    for t in (True, False):
+        after = e.predict_batch(stages, lim, DEFAULT_CAMERA_POSE, inc, grid, crop, use_table=t)
+        assert after[0].tobytes() == before[t][0].tobytes() and after[1].tobytes() == before[t][1].tobytes() and after[2] == before[t][2]
+    assert before[True][1].tobytes() == before[False][1].tobytes()
+
+
+def test_one_division_tensor_sweep_on_the_engine(small):
+    """A list with a one-division TensorSweep (np.linspace(lo, hi, 1) is [lo]: the sweep's lower end) and a whole-range
+    four-division InterpolativeSweep, three rendered frames in lockstep against the sequential restatement with the CPU oracle."""
+    e, o, rb, frames, grid, crop, native_stages = small
+    lim = rb.joint_limits
+    names = rb.link_names
+    blue_of = {nm: int(LINK_BLUE[i]) for i, nm in enumerate(names)}
+    ref_stages = [('lookup',), ('sflip', 4), ('tsweep', 6, 1, 'U', 0.3), ('isweep', 6, 4, 'U', None), ('tsweep', 4, 1, 'S', 0.2),
+                  ('descent', 4, 3, 'SL', [0.05, 0.05, 0.1, 0.5, 0.5, 0.5], 0.5, 0.1)]
+    got, trace, n = e.predict_batch(native_stages(ref_stages), lim, DEFAULT_CAMERA_POSE, np.array([.005] * 6), grid, crop, use_table=False)
+    for f, fr in enumerate(frames):
+        with np.errstate(all='ignore'):
+            want, ref_trace, _ = predictor_ref.predict_reference(o, fr['tgt'], fr['blue'], names, blue_of, lim, DEFAULT_CAMERA_POSE, grid, crop,
+                                                                     stages=ref_stages)
+        for k, (kind, ang) in enumerate(ref_trace):
+            assert np.array_equal(_bits(trace[f, k]), _bits(ang)), f"frame {f} stage {k} ({kind}): {trace[f, k]} vs reference {ang}"
+        assert np.array_equal(_bits(got[f]), _bits(want))
+        # the one-division sweeps really moved the pose to the lower end of their range
+        assert trace[f, 2, 2] == max(trace[f, 1, 2] - 0.3, lim[2, 0]) and trace[f, 4, 0] == max(trace[f, 3, 0] - 0.2, lim[0, 0])
+    assert n >= 3 * len(grid)

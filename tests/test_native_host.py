@@ -187,9 +187,10 @@ def test_frames_in_lockstep_equal_frame_by_frame(shim):
     shim.shim_set_targets_callback(C.cast(answer_targets, C.c_void_p))
     shim.shim_set_callback(answer_single)
     shim.rope_predict_batch.argtypes = [C.c_void_p, C.POINTER(PredictArgs), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    shim.shim_set_resident(len(targets))                     # as rope_set_targets would: n_frames has to equal it
     limits, cam, inc = np.ascontiguousarray(lim, np.float64), np.asarray(pose, np.float64), np.array([.005] * 6)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    tsweep = StageDesc(4, 6, 7, 1 << 2)                      # ROPE_STAGE_TSWEEP over U, 7 divisions, whole range
+    tsweep = StageDesc(4, 6, 7, 1 << 2)                     # ROPE_STAGE_TSWEEP over U, 7 divisions, whole range
     tsweep.range = NAN
     tsweep.init_rate[:] = [NAN] * 6
     for label, stages in (('SLU', _stages('SLU')), ('SL', _stages('SL')), ('custom', _stages('SL')[:2] + [tsweep] + _stages('SLU')[2:4])):
