@@ -1250,7 +1250,7 @@ extern "C" int rope_set_fragment_budget(rope_ctx *c, uint64_t bytes)
 namespace rope { hipError_t read_clock_stamps(unsigned long long *out); hipError_t read_bounds_violations(unsigned int *out); }
 
 // Profiling build: how many indices into the raster kernels' shared arrays / queue segments were out of range since the library
-// was loaded (ROPE_CHECK_INDEX in rope_kernels.hip)
+// was loaded (ROPE_CHECK_INDEX in rope_kernels.hip: the raster code, which is why it and its counter stay in that one file)
 extern "C" int rope_debug_bounds(rope_ctx *c, int *violations)
 {
     if (!c || !violations) return ROPE_E_ARG;

@@ -1,4 +1,5 @@
-// rope_kernels.h — shared between the kernels (rope_kernels.hip) and the C-ABI host side (rope_abi.hip).
+// rope_kernels.h — shared between the kernel files (rope_kernels.hip, rope_fragments.hip, rope_table.hip and the
+// target / mask / synthetic ones) and the C-ABI host side (rope_abi*.hip): constants, argument structs and every launch function.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -148,6 +149,7 @@ struct RasterArgs {
     int pass_id;
 };
 
+// rope_kernels.hip: geometry, the rasteriser and its queue, the split tiles, a kept grid's pass, the two ends of the sums
 hipError_t launch_fk(hipStream_t st, const double *cand, int C, int n_render, const double *joint_fixed,
                      const double *joint_axes, const double *PV, const int32_t *view_of, float *mvp, uint64_t *sums,
                      uint32_t *mask_lo, uint32_t *mask_hi, int mask_words,
@@ -185,6 +187,21 @@ hipError_t launch_layer_queue(int loss, int rows, int workgroups, hipStream_t st
 // pairs whose mask_lo bit is set are stored, the others are left alone (nobody reads them).
 hipError_t launch_clear_pass(hipStream_t st, uint64_t *sums, int C, int *queue_counters);
 hipError_t launch_layer_sums(int loss, int n_layers, hipStream_t st, const FrameParams &fp, const RasterArgs &a);
+// scores what a MODE_SPLIT launch merged into a.gtile; `slices` row slices per tile (a divisor of TILE_H)
+hipError_t launch_score_gtile(int loss, int rows, int slices, hipStream_t st, const FrameParams &fp, const RasterArgs &a);
+// "nothing rendered" sums of n_frames frames (planes back to back): empty_sums n_frames x n_tiles x SUM_WORDS of scratch,
+// total n_frames x SUM_WORDS
+hipError_t launch_empty(int loss, hipStream_t st, const FrameParams &fp, const uint64_t *tq, const float *t32, const uint64_t *tl,
+                        uint64_t *empty_sums, uint64_t *total, int n_frames = 1);
+hipError_t launch_finalize(hipStream_t st, uint64_t *sums, const uint64_t *total_empty, int C, int loss, int n_render,
+                           double n_pix, const LinkFlags &lf, double *err /* C + 2: errors, best error, best index */);
+// batches over several frames' targets (rope_eval_targets / rope_lookup_score_targets)
+hipError_t launch_finalize_frames(hipStream_t st, uint64_t *sums, const uint64_t *totals /* frames x SUM_WORDS */, const int32_t *frame_of,
+                                  const LinkFlags *flags /* per frame, device */, int C, int loss, int n_render, double n_pix, double *err /* C */);
+// first argmin of n_sets sets of C doubles: best[2 k] error, best[2 k + 1] index
+hipError_t launch_argmin_sets(hipStream_t st, const double *err, int C, int n_sets, double *best);
+
+// rope_fragments.hip
 // The kept fragments of a fixed grid (rope_ctx::frags, rope_fragstore.h).  `own`: rows x n_tiles key tiles that a MODE_LAYER launch
 // over the own links of rows row0 .. row0 + rows - 1 left (a.cand_of_row = the identity from row0 on, a.mask_lo = the context's
 // mask_hi); `a` here carries the pass's own a.mask_lo / a.mask_hi / a.layer_of / a.layer_rep / a.layers.  launch_fragment_count: per
@@ -197,14 +214,8 @@ hipError_t launch_fragment_fill(hipStream_t st, const RasterArgs &a, const uint3
                                 const unsigned long long *offs, uint32_t *where, uint4 *finished, uint4 *base_keys);
 hipError_t launch_fragment_score(int loss, int rows, hipStream_t st, const FrameParams &fp, const RasterArgs &a, const unsigned long long *offs,
                                  const uint32_t *where, const uint4 *finished, const uint4 *base_keys);
-// scores what a MODE_SPLIT launch merged into a.gtile; `slices` row slices per tile (a divisor of TILE_H)
-hipError_t launch_score_gtile(int loss, int rows, int slices, hipStream_t st, const FrameParams &fp, const RasterArgs &a);
-// "nothing rendered" sums of n_frames frames (planes back to back): empty_sums n_frames x n_tiles x SUM_WORDS of scratch,
-// total n_frames x SUM_WORDS
-hipError_t launch_empty(int loss, hipStream_t st, const FrameParams &fp, const uint64_t *tq, const float *t32, const uint64_t *tl,
-                        uint64_t *empty_sums, uint64_t *total, int n_frames = 1);
-hipError_t launch_finalize(hipStream_t st, uint64_t *sums, const uint64_t *total_empty, int C, int loss, int n_render,
-                           double n_pix, const LinkFlags &lf, double *err /* C + 2: errors, best error, best index */);
+
+// rope_table.hip
 // The stored lookup table keeps, of every row, the groups of four consecutive samples of a crop row in which anything was drawn:
 // counts[k] groups from offs[k] on in goff (offset of the group's first sample inside the crop) / gval (its four values).
 // launch_table_count: dense rows (C x ch x cw) -> counts / offs, *used = groups in all (zero it first); launch_table_fill writes them.
@@ -222,11 +233,6 @@ static inline size_t table_crop_words(const FrameParams &fp)
 // total: ROPE_SUM_WORDS words of scratch
 hipError_t launch_table_score(hipStream_t st, const FrameParams &fp, const uint32_t *counts, const unsigned long long *offs, const uint32_t *goff,
                               const float4 *gval, int C, const float *t32, float *t32c, uint64_t *total, uint64_t *sums);
-// batches over several frames' targets (rope_eval_targets / rope_lookup_score_targets)
-hipError_t launch_finalize_frames(hipStream_t st, uint64_t *sums, const uint64_t *totals /* frames x SUM_WORDS */, const int32_t *frame_of,
-                                  const LinkFlags *flags /* per frame, device */, int C, int loss, int n_render, double n_pix, double *err /* C */);
-// first argmin of n_sets sets of C doubles: best[2 k] error, best[2 k + 1] index
-hipError_t launch_argmin_sets(hipStream_t st, const double *err, int C, int n_sets, double *best);
 // the stored table against the float32 planes of n_frames frames: t32c n_frames x table_crop_words floats of scratch, totals n_frames x
 // SUM_WORDS of scratch, scores n_frames x C, best n_frames x 2 (score, row)
 hipError_t launch_table_score_frames(hipStream_t st, const FrameParams &fp, const uint32_t *counts, const unsigned long long *offs,

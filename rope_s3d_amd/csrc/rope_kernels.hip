@@ -1,6 +1,6 @@
 // rope_kernels.hip — CDNA4 (gfx950) kernels of the render-and-compare pose engine.
 //
-// One pass over a batch of candidate joint vectors:
+// One pass over a batch of candidate joint vectors (this file, unless another is named; rope_lossmath.h holds the loss terms):
 //   fk_mvp_kernel           per candidate: joint angles -> link world transforms -> P·V·M; clears the
 //                           candidate's accumulators (stands in for klampt FK,
 //                           robotpose/simulation/kinematics.py:36-55, and pyrender's node poses, render.py:88-90)
@@ -15,13 +15,15 @@
 //                             SPLIT  few candidates: a tile's meshlets over several workgroups, merged by atomicMin
 //                             TABLE  rows of the stored lookup table (cropped sqrt-depth)
 //                             DUMP / COVER  single-pose render, crop search
+//   raster_queue_kernel     the same over a queue of (row, tile) pairs that score_queue_kernel sorts by weight
 //   score_gtile_kernel      after SPLIT: scores the merged images in row bands and hands the buffer back empty
 //   clear_pass_kernel /     a pass over a grid whose geometry the context kept: clears the sums, and takes the stored layer
 //   layer_sums_kernel       tiles' loss sums against the new target — fk, bounds and LAYER do not run
-//   finalize_argmin_kernel  integer sums -> float64 errors, wave-shuffle argmin
-//   table_score_kernel      Lookup stage against the stored table: pure streaming
 //   camera-pose path        the same kernels with a view matrix per candidate (fk) and target planes per frame
 //                           (RasterArgs::frame_of); ROPE_LOSS_CAMFULL = CameraPredictor._error's sums
+//   finalize_argmin_kernel  integer sums -> float64 errors, wave-shuffle argmin
+//   rope_fragments.hip      a fixed grid's kept fragments: count, fill, score by streaming
+//   rope_table.hip          table_score_kernel and its kin: Lookup stage against the stored table, pure streaming
 //
 // Arithmetic contract: all floating point steps are single IEEE-754
 // operations in the written order (built with -ffp-contract=off; fmaf where fused),
@@ -33,6 +35,8 @@
 #include <algorithm>
 
 #include "rope_kernels.h"
+#include "rope_lossmath.h"    // score_pixel, score_tile: the loss terms every kernel file shares
+#include "rope_launch.h"      // with_loss: run-time loss -> template argument
 #include "rope_fk.h"          // det_sincos, aff_mul, joint_matrix: the chain rope_polish.hip shares
 
 namespace rope {
@@ -76,262 +80,6 @@ fk_mvp_kernel(const double *__restrict__ cand, int C, int n_render, const double
         for (int r = 0; r < 4; r++)
 #pragma unroll
             for (int k = 0; k < 4; k++) o[4 * r + k] = mvp_element(PV, T, r, k);
-    }
-}
-
-// --------------------------------------------------------------- pixel maths ----
-__device__ static inline float linear_depth(uint32_t d24, float c_num, float c_sum, float c_dif)
-{
-    float d = (float)d24 / 16777215.0f;
-    float t = 2.0f * d - 1.0f;
-    float u = t * c_dif;
-    float den = c_sum - u;
-    return c_num / den;
-}
-
-// floor(z * 2^32) for a finite z >= 0 (same value as (uint64_t)((double)z * 2^32)).
-// Any size: by shifting the significand.
-__device__ static inline uint64_t q32_of_f32_wide(float z)
-{
-    const uint32_t b = __float_as_uint(z);
-    const int ex = (int)(b >> 23) & 0xFF;
-    // zero and denormals are below one unit of 2^-32; no branches: both shifts are always executed, one of them by 0
-    const uint64_t m = ex ? (uint64_t)((b & 0x7FFFFFu) | 0x800000u) : 0ull;
-    const int sh = ex - 127 - 23 + 32;                        // z = m * 2^(ex-150)
-    return (m << min(max(sh, 0), 63)) >> min(max(-sh, 0), 63);
-}
-
-// Below 2^32 (every depth and depth difference there is: the far plane is at 100 m) in five full-rate operations instead of a
-// dozen with 64-bit shifts: z = trunc(z) + fraction, both parts exact in float32; the integer part is the high word, and
-// fraction * 2^32 — a power-of-two scaling, exact, below 2^32 — truncated is the low word.
-__device__ static inline uint64_t q32_of_f32(float z)
-{
-    if (__builtin_expect(!(z < 4294967296.0f), 0)) return q32_of_f32_wide(z);
-    const float whole = truncf(z);
-    const uint32_t hi = (uint32_t)whole, lo = (uint32_t)((z - whole) * 4294967296.0f);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// floor(sqrt(x) * 2^32) for x given in Q32: sqrt(dq * 2^-32) * 2^32 = sqrt(dq) * 2^16; one correctly rounded
-// float64 square root (dq < 2^39 converts exactly), then truncation
-__device__ static inline uint64_t sqrt_q32(uint64_t dq) { return (uint64_t)(sqrt((double)dq) * 65536.0); }
-
-// NEG subtracts instead of adds (modulo 2^64): lets "sums(tile) - sums(base)" live in one set of registers
-template <bool NEG>
-__device__ static inline void acc(uint64_t &w, uint64_t x) { if (NEG) w -= x; else w += x; }
-
-template <bool NEG>
-__device__ static inline void acc_sq(uint64_t *s, uint64_t dq)
-{
-    uint32_t a = (uint32_t)(dq >> 20), b = (uint32_t)(dq & 0xFFFFFu);
-    acc<NEG>(s[SUM_S1], dq);
-    acc<NEG>(s[SUM_AA], (uint64_t)a * a);
-    acc<NEG>(s[SUM_AB], (uint64_t)a * b);
-    acc<NEG>(s[SUM_BB], (uint64_t)b * b);
-}
-
-// The same for the differences of the float losses, which reach 2^32 (a lookup target just below it where nothing is drawn):
-// a = dq >> 20 has up to 44 bits there, and the products are taken modulo 2^64 as the oracle takes them.
-template <bool NEG>
-__device__ static inline void acc_sq_wide(uint64_t *s, uint64_t dq)
-{
-    const uint64_t a = dq >> 20, b = dq & 0xFFFFFu;
-    acc<NEG>(s[SUM_S1], dq);
-    acc<NEG>(s[SUM_AA], a * a);
-    acc<NEG>(s[SUM_AB], a * b);
-    acc<NEG>(s[SUM_BB], b * b);
-}
-
-// Loss terms of one pixel given its z-buffer key.  `pix` indexes the H x W target planes.
-template <int LOSS, bool NEG = false>
-__device__ static inline void score_pixel(uint32_t key, size_t pix, int n_render, const uint64_t t /* tq[pix] */,
-                                          const float ta /* t32[pix] */, const uint64_t *__restrict__ tl, size_t plane,
-                                          float c_num, float c_sum, float c_dif, uint64_t *s, uint64_t *pk = nullptr,
-                                          unsigned link_mask = 0xFFu /* ROPE_LOSS_FULL: the links whose terms are wanted (uniform) */)
-{
-    const bool empty = (key == KEY_EMPTY);
-    float z = empty ? 0.0f : linear_depth(key >> 8, c_num, c_sum, c_dif);
-    if (LOSS == ROPE_LOSS_LOOKUP || LOSS == ROPE_LOSS_TSWEEP) {
-        float a = ta;
-        if (LOSS == ROPE_LOSS_TSWEEP) a = sqrtf(a);
-        float diff = fabsf(a - sqrtf(z));
-        uint64_t dq = q32_of_f32(diff);
-        if (dq) acc_sq_wide<NEG>(s, dq);
-        return;
-    }
-    if (LOSS == ROPE_LOSS_CAMFULL) {
-        // CameraPredictor._error (camera_pose_prediction.py:933-970): every difference enters as its square root;
-        // per link (base_link included) mask mismatches and the mean of sqrt|T_l - D*R_l| over its non-zero entries
-        const uint64_t T = t & 0x7FFFFFFFFFull, zq = q32_of_f32(z);
-        const uint64_t dq = T > zq ? T - zq : zq - T;
-        if (dq) { acc<NEG>(s[SUM_CNT], 1); acc<NEG>(s[SUM_S1], dq); acc<NEG>(s[SUM_AA], sqrt_q32(dq)); }
-        const int id = empty ? 255 : (int)(key & 0xFF);
-#pragma unroll
-        for (int l = 0; l < ROPE_MAX_LINKS; l++) {
-            if (l < n_render) {
-                const uint64_t tll = tl[(size_t)l * plane + pix];
-                // the reference compares blue values (:943-946), and base_link's blue is 0 — the black background's too
-                // (constants.py:82-89): its render mask also holds every pixel nothing was drawn on
-                const bool M = (tll >> 40) & 1, R = (id == l) || (l == 0 && empty);
-                if (!M && !R && !(tll & 0x7FFFFFFFFFull)) continue;
-                const uint64_t a = tll & 0x7FFFFFFFFFull, b = R ? zq : 0;
-                const uint64_t dl = a > b ? a - b : b - a;
-                pk[NEG ? 1 : 0] += (uint64_t)(M != R) << (10 * l);          // six 10-bit fields (see ROPE_LOSS_FULL below)
-                pk[NEG ? 3 : 2] += (uint64_t)(dl != 0) << (10 * l);
-                if (dl) acc<NEG>(s[SUM_LINK0 + 3 * l + 2], sqrt_q32(dl));
-            }
-        }
-        return;
-    }
-    if (empty && t == 0) return;                  // nothing rendered, no target: every term is zero
-    const uint64_t T = t & 0x7FFFFFFFFFull, zq = q32_of_f32(z);
-    const uint64_t dq = T > zq ? T - zq : zq - T;
-    acc<NEG>(s[SUM_CNT], (uint64_t)(dq != 0));    // unconditional: a zero difference adds zeros
-    acc_sq<NEG>(s, dq);
-    if (LOSS == ROPE_LOSS_FULL) {
-        const unsigned mask = (unsigned)(t >> 40) & 0xFFu;
-        const int id = empty ? 255 : (int)(key & 0xFF);
-#pragma unroll
-        for (int l = 1; l < ROPE_MAX_LINKS; l++) {
-            if (l < n_render && ((link_mask >> l) & 1u)) {
-                const bool M = (mask >> l) & 1, R = (id == l);
-                const uint64_t a = M ? T : 0, b = R ? zq : 0;
-                const uint64_t dl = a > b ? a - b : b - a;
-                // the two counts of every link live as 12-bit fields of packed words (a thread of score_tile meets at most 16 samples;
-                // fragment_score_kernel, whose threads meet any number, empties the words before a field can fill up):
-                // pk[0]/pk[1] mask mismatches added / subtracted, pk[2]/pk[3] non-zero link differences added / subtracted
-                pk[NEG ? 1 : 0] += (uint64_t)(M != R) << (12 * (l - 1));
-                pk[NEG ? 3 : 2] += (uint64_t)(dl != 0) << (12 * (l - 1));
-                acc<NEG>(s[SUM_LINK0 + 3 * l + 2], dl);
-            }
-        }
-    }
-}
-
-// Pixels of a tile that take part in the loss: inside the image and, for the lookup loss, the crop.
-__device__ static inline bool pixel_active(int row, int col, int W, int H, int r0, int r1, int c0, int c1)
-{
-    return row < H && col < W && row >= r0 && row <= r1 && col >= c0 && col <= c1;
-}
-
-// Loss sums of one tile.  DELTA = false: plain sums of a tile with nothing rendered.
-// DELTA = true: sums(tile) - sums(base tile), which only the samples whose key differs contribute to —
-// all others are skipped without touching the target planes.  Arithmetic is
-// modulo 2^64, the frame total of the "nothing rendered" sums is added back by finalize_argmin_kernel.
-// Rows [r_lo, r_hi] and 4-sample column groups [g_lo, g_hi] of a tile that a launch may have drawn into.
-struct TileRect { int r_lo, r_hi, g_lo, g_hi; int block_g; };   // block_g: log2 of a wave's block width in groups (3, 4 or 5)
-
-template <int LOSS, bool DELTA>
-__device__ static inline void score_tile(const uint32_t *tile, const uint32_t *__restrict__ base /* global, or nullptr = nothing */,
-                                         int row0, int col0, const FrameParams &fp, int n_render,
-                                         const uint64_t *__restrict__ tq, const float *__restrict__ t32,
-                                         const uint64_t *__restrict__ tl, uint64_t *lds_sums, const TileRect rc)
-{
-    const size_t plane = (size_t)fp.W * fp.H;
-    uint64_t s[ROPE_SUM_WORDS];
-#pragma unroll
-    for (int k = 0; k < ROPE_SUM_WORDS; k++) s[k] = 0;
-    uint64_t pk[4] = {0, 0, 0, 0};                      // ROPE_LOSS_FULL: packed per-link counts (score_pixel)
-    if (DELTA) {
-        // Only samples whose key differs from the base tile (the shared layer, or nothing) change the sums, and only
-        // the rectangle this launch could draw into can hold any.  The z-test is a minimum over keys, so the tile
-        // holds this launch's own samples and min(tile, base) is the finished image: the base is never copied to LDS.
-        // A wave takes a compact block of the tile — 2^BLOCK_G groups wide, 64 >> BLOCK_G rows high — instead of two
-        // whole rows: the robot's image is a blob, and the blocks inside it keep all their lanes busy.
-        static_assert((TILE_W / 4) == 32, "block mapping below assumes 32 four-sample groups per tile row");
-        const int bg = rc.block_g, brows = 64 >> bg, bpr_sh = 5 - bg;            // blocks per band of rows: 32 >> bg
-        const int n_items = (rc.r_hi - rc.r_lo + 1) * (TILE_W / 4);
-        for (int it = threadIdx.x; it < n_items; it += blockDim.x) {
-            const int b = it >> 6, l = it & 63;
-            const int g = ((b & ((1 << bpr_sh) - 1)) << bg) | (l & ((1 << bg) - 1));
-            const int i4 = (rc.r_lo + (b >> bpr_sh) * brows + (l >> bg)) * (TILE_W / 4) + g;
-            uint4 k4 = reinterpret_cast<const uint4 *>(tile)[i4];
-            const uint4 b4 = base ? reinterpret_cast<const uint4 *>(base)[i4] : make_uint4(KEY_EMPTY, KEY_EMPTY, KEY_EMPTY, KEY_EMPTY);
-            k4.x = min(k4.x, b4.x); k4.y = min(k4.y, b4.y); k4.z = min(k4.z, b4.z); k4.w = min(k4.w, b4.w);
-            if (k4.x == b4.x && k4.y == b4.y && k4.z == b4.z && k4.w == b4.w) continue;
-            const uint32_t keys[4] = {k4.x, k4.y, k4.z, k4.w}, bas[4] = {b4.x, b4.y, b4.z, b4.w};
-            const int row = row0 + (4 * i4) / TILE_W, colg = col0 + (4 * i4) % TILE_W;
-            if (row >= fp.H || colg >= fp.W) continue;
-            const size_t pixg = (size_t)row * fp.W + colg;
-            // the four samples sit side by side: fetch their target words together, one wait instead of four
-            constexpr bool USE_F = (LOSS == ROPE_LOSS_LOOKUP || LOSS == ROPE_LOSS_TSWEEP);
-            uint64_t tw[4] = {0, 0, 0, 0};
-            float tf[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (colg + 3 < fp.W && !(fp.W & 3)) {
-                if (USE_F) {
-                    const float4 f = *reinterpret_cast<const float4 *>(t32 + pixg);
-                    tf[0] = f.x; tf[1] = f.y; tf[2] = f.z; tf[3] = f.w;
-                } else {
-                    const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(tq + pixg), b = *reinterpret_cast<const ulonglong2 *>(tq + pixg + 2);
-                    tw[0] = a.x; tw[1] = a.y; tw[2] = b.x; tw[3] = b.y;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (colg + j < fp.W) { if (USE_F) tf[j] = t32[pixg + j]; else tw[j] = tq[pixg + j]; }
-            }
-            // ROPE_LOSS_FULL: a link's terms at a sample depend on the image only through "is this the link drawn here", so in
-            // sums(tile) - sums(base) every link that is drawn in neither cancels, sample by sample and exactly.  The links that
-            // are drawn somewhere in this wave's block (usually one or two of the five) are the only ones whose terms are worked
-            // out: a uniform branch per link, taken from a vote.
-            unsigned links = 0xFFu;
-            if (LOSS == ROPE_LOSS_FULL) {
-                unsigned mine = 0;
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (keys[j] != bas[j]) mine |= (keys[j] == KEY_EMPTY ? 0u : 1u << (keys[j] & 7u)) | (bas[j] == KEY_EMPTY ? 0u : 1u << (bas[j] & 7u));
-                links = 0;
-#pragma unroll
-                for (int l = 1; l < ROPE_MAX_LINKS; l++) links |= __ballot((mine >> l) & 1u) ? 1u << l : 0u;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                if (keys[j] == bas[j]) continue;
-                if (!pixel_active(row, colg + j, fp.W, fp.H, fp.r0, fp.r1, fp.c0, fp.c1)) continue;
-                score_pixel<LOSS, false>(keys[j], pixg + j, n_render, tw[j], tf[j], tl, plane, fp.c_num, fp.c_sum, fp.c_dif, s, pk, links);
-                score_pixel<LOSS, true>(bas[j], pixg + j, n_render, tw[j], tf[j], tl, plane, fp.c_num, fp.c_sum, fp.c_dif, s, pk, links);
-            }
-        }
-    } else {
-        for (int i = threadIdx.x; i < TILE_W * TILE_H; i += blockDim.x) {
-            int row = row0 + i / TILE_W, col = col0 + i % TILE_W;
-            if (!pixel_active(row, col, fp.W, fp.H, fp.r0, fp.r1, fp.c0, fp.c1)) continue;
-            const size_t pix = (size_t)row * fp.W + col;
-            constexpr bool USE_F = (LOSS == ROPE_LOSS_LOOKUP || LOSS == ROPE_LOSS_TSWEEP);
-            score_pixel<LOSS>(KEY_EMPTY, pix, n_render, USE_F ? 0ull : tq[pix], USE_F ? t32[pix] : 0.0f, tl, plane, fp.c_num, fp.c_sum, fp.c_dif, s, pk);
-        }
-    }
-    if (LOSS == ROPE_LOSS_CAMFULL) {
-#pragma unroll
-        for (int l = 0; l < ROPE_MAX_LINKS; l++) {
-            s[SUM_LINK0 + 3 * l] = ((pk[0] >> (10 * l)) & 0x3FFull) - ((pk[1] >> (10 * l)) & 0x3FFull);
-            s[SUM_LINK0 + 3 * l + 1] = ((pk[2] >> (10 * l)) & 0x3FFull) - ((pk[3] >> (10 * l)) & 0x3FFull);
-        }
-    }
-    if (LOSS == ROPE_LOSS_FULL) {
-#pragma unroll
-        for (int l = 1; l < ROPE_MAX_LINKS; l++) {
-            s[SUM_LINK0 + 3 * l] = ((pk[0] >> (12 * (l - 1))) & 0xFFFull) - ((pk[1] >> (12 * (l - 1))) & 0xFFFull);
-            s[SUM_LINK0 + 3 * l + 1] = ((pk[2] >> (12 * (l - 1))) & 0xFFFull) - ((pk[3] >> (12 * (l - 1))) & 0xFFFull);
-        }
-    }
-    // one LDS atomic per word and wave: the partial sums (modulo 2^64) are added up across the lanes first, and
-    // waves that met no sample skip the whole step
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < ROPE_SUM_WORDS; k++) any = any || s[k] != 0;
-    if (__ballot(any) == 0) return;
-#pragma unroll
-    for (int k = 0; k < ROPE_SUM_WORDS; k++) {
-        const bool used = (LOSS == ROPE_LOSS_FULL || LOSS == ROPE_LOSS_CAMFULL) ? true : (k < SUM_LINK0);
-        if (!used) continue;
-        uint64_t v = s[k];
-        // a word nobody in the wave added to (the terms of a link that is drawn nowhere in the wave's block: most of the 20 words
-        // of the full loss) needs no exchange — the twelve steps of one cost more than a thread's share of the samples
-        if ((LOSS == ROPE_LOSS_FULL || LOSS == ROPE_LOSS_CAMFULL) && __ballot(v != 0) == 0) continue;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd((unsigned long long *)&lds_sums[k], (unsigned long long)v);
     }
 }
 
@@ -1472,425 +1220,7 @@ layer_sums_kernel(FrameParams fp, RasterArgs ra)
     if (tid < ROPE_SUM_WORDS) ra.layer_sums[slot * ROPE_SUM_WORDS + tid] = lds_sums[tid];
 }
 
-// ----------------------------------------------------------- kept fragments -----
-// What the scoring launch draws of a row — its own links l_begin .. n_render - 1 into a tile, tested against the row's shared layer —
-// is a function of geometry alone, and of all the samples of a (row, tile) pair only those where the row's own links
-// beat the layer enter the row's sums: score_tile<.., DELTA> skips every 16-byte group in which min(own, base) == base.  A grid
-// that is scored again and again keeps exactly those groups (rope_ctx::frags): a MODE_LAYER launch over the rows' own links leaves
-// whole key tiles in a scratch, chunk of rows by chunk of rows, fragment_count_kernel / fragment_fill_kernel compact them into one
-// store (the pattern of the lookup table's kernels below), and fragment_score_kernel streams a row's groups against the target.
-
-// the row's shared layer over this tile, or nullptr where the layer's representative has no mask_lo bit (raster_tile's layer_tile)
-__device__ static inline const uint4 *fragment_base_tile(const RasterArgs &ra, int cand, int tile_id, int n_tiles)
-{
-    const int layer = ra.layer_of[cand];
-    const bool lo = (ra.mask_lo[(size_t)ra.layer_rep[layer] * ra.mask_words + (tile_id >> 5)] >> (tile_id & 31)) & 1u;
-    return lo ? reinterpret_cast<const uint4 *>(ra.layers + ((size_t)layer * n_tiles + tile_id) * (TILE_W * TILE_H)) : nullptr;
-}
-
-__device__ static inline bool fragment_beats(const uint4 k, const uint4 b) { return k.x < b.x || k.y < b.y || k.z < b.z || k.w < b.w; }
-
-// Grid = (tiles, rows of the chunk): own = the chunk's key tiles (rows x tiles x TILE_W*TILE_H, written by the MODE_LAYER launch
-// for the pairs whose mask_hi bit is set; the others hold anything and are not read).  counts: C x tiles, zeroed before the first chunk.
-__global__ void __launch_bounds__(256)
-fragment_count_kernel(RasterArgs ra, const uint32_t *__restrict__ own, int row0, int n_tiles, uint32_t *__restrict__ counts)
-{
-    __shared__ int s_n;
-    const int tile_id = blockIdx.x, cand = row0 + (int)blockIdx.y;
-    if (!((ra.mask_hi[(size_t)cand * ra.mask_words + (tile_id >> 5)] >> (tile_id & 31)) & 1u)) return;
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    const uint4 *k4 = reinterpret_cast<const uint4 *>(own + ((size_t)blockIdx.y * n_tiles + tile_id) * (TILE_W * TILE_H));
-    const uint4 *b4 = fragment_base_tile(ra, cand, tile_id, n_tiles);
-    const uint4 none = make_uint4(KEY_EMPTY, KEY_EMPTY, KEY_EMPTY, KEY_EMPTY);
-    int mine = 0;
-    for (int g = threadIdx.x; g < TILE_W * TILE_H / 4; g += blockDim.x) mine += fragment_beats(k4[g], b4 ? b4[g] : none);
-    if (mine) atomicAdd(&s_n, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) counts[(size_t)cand * n_tiles + tile_id] = (uint32_t)s_n;
-}
-
-// The same walk, writing: the groups of a (row, tile) pair from offs[row * tiles + tile] on, IN ORDER of their place in the tile
-// (table_fill_kernel's compaction), so that a row's list is ordered by tile, then group, and neighbouring lanes of the scorer read
-// neighbouring pieces of the target.
-__global__ void __launch_bounds__(256)
-fragment_fill_kernel(RasterArgs ra, const uint32_t *__restrict__ own, int row0, int n_tiles, const unsigned long long *__restrict__ offs,
-                     uint32_t *__restrict__ where, uint4 *__restrict__ finished, uint4 *__restrict__ base_keys)
-{
-    __shared__ int s_wave[4];
-    const int tile_id = blockIdx.x, cand = row0 + (int)blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (!((ra.mask_hi[(size_t)cand * ra.mask_words + (tile_id >> 5)] >> (tile_id & 31)) & 1u)) return;
-    const size_t slot = (size_t)cand * n_tiles + tile_id;
-    const unsigned long long first = offs[slot], last = offs[slot + 1];
-    if (last == first) return;                                                         // nothing of this pair is kept (uniform)
-    const uint4 *k4 = reinterpret_cast<const uint4 *>(own + ((size_t)blockIdx.y * n_tiles + tile_id) * (TILE_W * TILE_H));
-    const uint4 *b4 = fragment_base_tile(ra, cand, tile_id, n_tiles);
-    const uint4 none = make_uint4(KEY_EMPTY, KEY_EMPTY, KEY_EMPTY, KEY_EMPTY);
-    static_assert((TILE_W * TILE_H / 4) % 256 == 0 && TILE_W * TILE_H / 4 <= 4096, "whole rounds of 256 groups; a group index fits 12 bits");
-    int running = 0;
-    for (int g0 = 0; g0 < TILE_W * TILE_H / 4; g0 += 256) {
-        const int g = g0 + (int)threadIdx.x;
-        uint4 k = k4[g];
-        const uint4 b = b4 ? b4[g] : none;
-        const bool any = fragment_beats(k, b);
-        const unsigned long long m = __ballot(any);
-        if (lane == 0) s_wave[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < 4; w++) { before += w < wave ? s_wave[w] : 0; all += s_wave[w]; }
-        const unsigned long long pos = first + (unsigned long long)(running + before + __popcll(m & ((1ull << lane) - 1ull)));
-        if (any && pos < last) {                                // never past the place the count pass reserved for this pair
-            k.x = min(k.x, b.x); k.y = min(k.y, b.y); k.z = min(k.z, b.z); k.w = min(k.w, b.w);
-            where[pos] = ((uint32_t)tile_id << 12) | (uint32_t)g;
-            finished[pos] = k;
-            base_keys[pos] = b;
-        }
-        running += all;
-        __syncthreads();
-    }
-}
-
-// One workgroup per row: the row's kept groups against the target — the body of score_tile's delta loop on stored keys instead of
-// an LDS tile (score_pixel on the finished key, score_pixel<.., NEG> on the base key, for the samples where they differ and that
-// take part in the loss; the full loss's vote over the links drawn in the wave, its packed counts) — then the loss sums of the row's
-// layer over every tile the layer reaches (ra.layer_sums, this pass's), and the row's 23 words stored whole: nothing is accumulated
-// into, so nothing has to be cleared.  Integer sums modulo 2^64: the words of raster_queue_kernel<LOSS, SCORE>, bit for bit.
-template <int LOSS>
-__global__ void __launch_bounds__(256)
-fragment_score_kernel(FrameParams fp, RasterArgs ra, const unsigned long long *__restrict__ offs, const uint32_t *__restrict__ where,
-                      const uint4 *__restrict__ finished, const uint4 *__restrict__ base_keys)
-{
-    __shared__ uint64_t lds_sums[ROPE_SUM_WORDS];
-    const int tid = threadIdx.x, cand = blockIdx.x, n_tiles = fp.tiles_x * fp.tiles_y;
-    const size_t plane = (size_t)fp.W * fp.H;
-    const uint64_t *__restrict__ tq = ra.tq;
-    const float *__restrict__ t32 = ra.t32;
-    const int n_render = ra.n_render;
-    if (tid < ROPE_SUM_WORDS) lds_sums[tid] = 0;
-    __syncthreads();
-    uint64_t s[ROPE_SUM_WORDS];
-#pragma unroll
-    for (int k = 0; k < ROPE_SUM_WORDS; k++) s[k] = 0;
-    uint64_t pk[4] = {0, 0, 0, 0};
-    const unsigned long long begin = offs[(size_t)cand * n_tiles], end = offs[(size_t)(cand + 1) * n_tiles];
-    constexpr bool USE_F = (LOSS == ROPE_LOSS_LOOKUP || LOSS == ROPE_LOSS_TSWEEP);
-    // The full loss's packed counts are 12-bit fields and a round adds at most 4 to one: they are emptied into the sums every
-    // FRAGMENT_PK_ROUNDS rounds (4 x 1000 < 4096), since nothing bounds the rounds of a row — a 4K frame gives a thread thousands.
-    constexpr int FRAGMENT_PK_ROUNDS = 1000;
-    int rounds = 0;
-    for (unsigned long long i0 = begin; i0 < end; i0 += 256) {                        // uniform: every lane takes every round
-        if (LOSS == ROPE_LOSS_FULL && ++rounds > FRAGMENT_PK_ROUNDS) {
-#pragma unroll
-            for (int l = 1; l < ROPE_MAX_LINKS; l++) {
-                s[SUM_LINK0 + 3 * l] += ((pk[0] >> (12 * (l - 1))) & 0xFFFull) - ((pk[1] >> (12 * (l - 1))) & 0xFFFull);
-                s[SUM_LINK0 + 3 * l + 1] += ((pk[2] >> (12 * (l - 1))) & 0xFFFull) - ((pk[3] >> (12 * (l - 1))) & 0xFFFull);
-            }
-            pk[0] = pk[1] = pk[2] = pk[3] = 0;
-            rounds = 1;
-        }
-        const unsigned long long i = i0 + (unsigned long long)tid;
-        bool use = i < end;
-        uint32_t w = 0;
-        uint4 k4 = make_uint4(KEY_EMPTY, KEY_EMPTY, KEY_EMPTY, KEY_EMPTY), b4 = k4;
-        if (use) { w = where[i]; k4 = finished[i]; b4 = base_keys[i]; }
-        const int tile_id = (int)(w >> 12), i4 = (int)(w & 0xFFFu);
-        const int row = (tile_id / fp.tiles_x) * TILE_H + (4 * i4) / TILE_W, colg = (tile_id % fp.tiles_x) * TILE_W + (4 * i4) % TILE_W;
-        use = use && row < fp.H && colg < fp.W;
-        const uint32_t keys[4] = {k4.x, k4.y, k4.z, k4.w}, bas[4] = {b4.x, b4.y, b4.z, b4.w};
-        const size_t pixg = (size_t)row * fp.W + colg;
-        uint64_t tw[4] = {0, 0, 0, 0};
-        float tf[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (use) {
-            if (colg + 3 < fp.W && !(fp.W & 3)) {
-                if (USE_F) {
-                    const float4 f = *reinterpret_cast<const float4 *>(t32 + pixg);
-                    tf[0] = f.x; tf[1] = f.y; tf[2] = f.z; tf[3] = f.w;
-                } else {
-                    const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(tq + pixg), b = *reinterpret_cast<const ulonglong2 *>(tq + pixg + 2);
-                    tw[0] = a.x; tw[1] = a.y; tw[2] = b.x; tw[3] = b.y;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (colg + j < fp.W) { if (USE_F) tf[j] = t32[pixg + j]; else tw[j] = tq[pixg + j]; }
-            }
-        }
-        unsigned links = 0xFFu;
-        if (LOSS == ROPE_LOSS_FULL) {
-            unsigned mine = 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (use && keys[j] != bas[j]) mine |= (keys[j] == KEY_EMPTY ? 0u : 1u << (keys[j] & 7u)) | (bas[j] == KEY_EMPTY ? 0u : 1u << (bas[j] & 7u));
-            links = 0;
-#pragma unroll
-            for (int l = 1; l < ROPE_MAX_LINKS; l++) links |= __ballot((mine >> l) & 1u) ? 1u << l : 0u;
-        }
-        if (!use) continue;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (keys[j] == bas[j]) continue;
-            if (!pixel_active(row, colg + j, fp.W, fp.H, fp.r0, fp.r1, fp.c0, fp.c1)) continue;
-            score_pixel<LOSS, false>(keys[j], pixg + j, n_render, tw[j], tf[j], nullptr, plane, fp.c_num, fp.c_sum, fp.c_dif, s, pk, links);
-            score_pixel<LOSS, true>(bas[j], pixg + j, n_render, tw[j], tf[j], nullptr, plane, fp.c_num, fp.c_sum, fp.c_dif, s, pk, links);
-        }
-    }
-    if (LOSS == ROPE_LOSS_FULL) {
-#pragma unroll
-        for (int l = 1; l < ROPE_MAX_LINKS; l++) {
-            s[SUM_LINK0 + 3 * l] += ((pk[0] >> (12 * (l - 1))) & 0xFFFull) - ((pk[1] >> (12 * (l - 1))) & 0xFFFull);
-            s[SUM_LINK0 + 3 * l + 1] += ((pk[2] >> (12 * (l - 1))) & 0xFFFull) - ((pk[3] >> (12 * (l - 1))) & 0xFFFull);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < ROPE_SUM_WORDS; k++) {
-        if (LOSS != ROPE_LOSS_FULL && k >= SUM_LINK0) continue;
-        uint64_t v = s[k];
-        if (__ballot(v != 0) == 0) continue;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if ((tid & 63) == 0 && v) atomicAdd((unsigned long long *)&lds_sums[k], (unsigned long long)v);
-    }
-    __syncthreads();
-    if (tid < ROPE_SUM_WORDS) {
-        uint64_t v = lds_sums[tid];
-        const int layer = ra.layer_of[cand];
-        const uint32_t *lo = ra.mask_lo + (size_t)ra.layer_rep[layer] * ra.mask_words;
-        for (int wd = 0; 32 * wd < n_tiles; wd++)
-            for (uint32_t m = lo[wd]; m; m &= m - 1)
-                v += ra.layer_sums[((size_t)layer * n_tiles + 32 * wd + __ffs((int)m) - 1) * ROPE_SUM_WORDS + tid];
-        ra.sums[(size_t)cand * ROPE_SUM_WORDS + tid] = v;
-    }
-}
-
-// ------------------------------------------------------------- lookup table -----
-// Lookup stage against a stored table (predict.py:165-171): per row k of the table, the exact sums of |T - sqrtD_k| in Q32
-// over the crop.  The crop is the box of every pose of the grid; one pose covers a fraction of it, and where a row holds
-// nothing the term is |T - 0|, the same for every row.  So a row is stored as the groups of samples that hold something
-// (table_count_kernel / table_fill_kernel), the sums of |T| over the whole crop are taken once per frame (crop_total_kernel), and
-// a row's sums are total + sum over its groups of (|T - D| - |T|) — integers, so exactly the sums over the whole crop.
-
-// One workgroup: the crop of the target plane as one contiguous array — rows padded with zeros to a multiple of four samples, so
-// that a group of the table (columns 4k .. 4k+3 of a crop row) is one aligned float4 at offset 4 x (its number) — and the sums of |T|
-// over it.  (The same sums group by group, for a table row to subtract instead of working them out again per (row, frame), made the
-// scoring kernel half as slow again, 9.8 against 6.6 ms for 256 frames x 15 625 rows: it waits for its gathers, not for its arithmetic.)
-// grid = frames: frame f's plane starts f planes into t32, its crop f crops into t32c, its totals f x ROPE_SUM_WORDS into total
-__global__ void __launch_bounds__(1024)
-crop_total_kernel(FrameParams fp, const float *__restrict__ t32, float *__restrict__ t32c, uint64_t *__restrict__ total /* ROPE_SUM_WORDS */)
-{
-    __shared__ uint64_t lds[4];
-    const int cw = fp.c1 - fp.c0 + 1, ch = fp.r1 - fp.r0 + 1, gw = (cw + 3) >> 2, n_groups = gw * ch;
-    t32 += (size_t)blockIdx.x * fp.W * fp.H;
-    t32c += (size_t)blockIdx.x * n_groups * 4;
-    total += (size_t)blockIdx.x * ROPE_SUM_WORDS;
-    if (threadIdx.x < 4) lds[threadIdx.x] = 0;
-    __syncthreads();
-    uint64_t s[ROPE_SUM_WORDS];
-    s[SUM_S1] = s[SUM_AA] = s[SUM_AB] = s[SUM_BB] = 0;
-    for (int g = threadIdx.x; g < n_groups; g += blockDim.x) {
-        const int r = g / gw, c = 4 * (g - r * gw);
-        const float *src = t32 + (size_t)(fp.r0 + r) * fp.W + fp.c0 + c;
-        float t[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            t[j] = c + j < cw ? src[j] : 0.0f;
-            acc_sq_wide<false>(s, q32_of_f32(fabsf(t[j] - 0.0f)));
-        }
-        reinterpret_cast<float4 *>(t32c)[g] = make_float4(t[0], t[1], t[2], t[3]);
-    }
-    const int words[4] = {SUM_S1, SUM_AA, SUM_AB, SUM_BB};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        uint64_t v = s[words[k]];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd((unsigned long long *)&lds[k], (unsigned long long)v);
-    }
-    __syncthreads();
-    if (threadIdx.x < ROPE_SUM_WORDS) {
-        uint64_t v = 0;
-        for (int k = 0; k < 4; k++) if ((int)threadIdx.x == words[k]) v = lds[k];
-        total[threadIdx.x] = v;
-    }
-}
-
-// Build time.  A dense row (the cropped sqrt-depth image of one grid pose) is mostly zeros: the crop is the box of every pose of the
-// grid together, one pose covers a fraction of it, and the robot a fraction of its own bounding box.  A sample that holds nothing
-// contributes |T - 0| - |T| = 0 to the row's sums, exactly — so the stored table keeps only the GROUPS of four consecutive samples
-// of a crop row (columns 4k .. 4k+3) in which anything was drawn: per group four times its number — the offset of its first
-// sample in a crop whose rows are padded to whole groups (crop_total_kernel's layout) — and its four values (columns past the
-// crop's edge read as 0).  table_count_kernel counts a row's groups and reserves their place,
-// table_fill_kernel writes them (in the order of their place in the crop: neighbouring lanes then read neighbouring samples).
-__global__ void __launch_bounds__(256)
-table_count_kernel(int cw, int ch, const float *__restrict__ table, uint32_t *__restrict__ counts, unsigned long long *__restrict__ offs,
-                   unsigned long long *__restrict__ used)
-{
-    __shared__ int s_n;
-    const int gw = (cw + 3) >> 2, n_groups = gw * ch;
-    const float *row = table + (size_t)blockIdx.x * cw * ch;
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    int mine = 0;
-    for (int g = threadIdx.x; g < n_groups; g += blockDim.x) {
-        const int r = g / gw, c = 4 * (g - r * gw);
-        bool any = false;
-        for (int j = 0; j < 4; j++) any = any || (c + j < cw && row[(size_t)r * cw + c + j] != 0.0f);
-        mine += any;
-    }
-    if (mine) atomicAdd(&s_n, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        counts[blockIdx.x] = (uint32_t)s_n;
-        offs[blockIdx.x] = s_n ? atomicAdd(used, (unsigned long long)s_n) : 0ull;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-table_fill_kernel(int cw, int ch, const float *__restrict__ table, const unsigned long long *__restrict__ offs, uint32_t *__restrict__ goff,
-                  float4 *__restrict__ gval)
-{
-    // The groups of a row are written IN ORDER of their place in the crop: the scoring kernels hand consecutive groups to
-    // consecutive lanes, and a run of groups inside the robot's outline is then a run of neighbouring 16-byte pieces of the target —
-    // eight lanes to a cache line instead of one line per lane.
-    __shared__ int s_wave[4];
-    const int gw = (cw + 3) >> 2, n_groups = gw * ch, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float *row = table + (size_t)blockIdx.x * cw * ch;
-    const unsigned long long base = offs[blockIdx.x];
-    int running = 0;
-    for (int g0 = 0; g0 < n_groups; g0 += 256) {
-        const int g = g0 + (int)threadIdx.x;
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        bool any = false;
-        if (g < n_groups) {
-            const int r = g / gw, c = 4 * (g - r * gw);
-            for (int j = 0; j < 4; j++) { v[j] = c + j < cw ? row[(size_t)r * cw + c + j] : 0.0f; any = any || v[j] != 0.0f; }
-        }
-        const unsigned long long b = __ballot(any);
-        if (lane == 0) s_wave[wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < 4; w++) { before += w < wave ? s_wave[w] : 0; all += s_wave[w]; }
-        if (any) {
-            const int pos = running + before + __popcll(b & ((1ull << lane) - 1ull));
-            goff[base + pos] = (uint32_t)(4 * g);
-            gval[base + pos] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-        running += all;
-        __syncthreads();
-    }
-}
-
-// One group against one cropped target: s += sum of |T - D| minus sum of |T| over its four samples (words S1, AA, AB, BB), modulo 2^64.
-__device__ static inline void table_group_delta(const float4 t, const float4 d, uint64_t *s)
-{
-    acc_sq_wide<false>(s, q32_of_f32(fabsf(t.x - d.x))); acc_sq_wide<true>(s, q32_of_f32(fabsf(t.x - 0.0f)));
-    acc_sq_wide<false>(s, q32_of_f32(fabsf(t.y - d.y))); acc_sq_wide<true>(s, q32_of_f32(fabsf(t.y - 0.0f)));
-    acc_sq_wide<false>(s, q32_of_f32(fabsf(t.z - d.z))); acc_sq_wide<true>(s, q32_of_f32(fabsf(t.z - 0.0f)));
-    acc_sq_wide<false>(s, q32_of_f32(fabsf(t.w - d.w))); acc_sq_wide<true>(s, q32_of_f32(fabsf(t.w - 0.0f)));
-}
-
-__global__ void __launch_bounds__(256)
-table_score_kernel(const uint32_t *__restrict__ counts, const unsigned long long *__restrict__ offs, const uint32_t *__restrict__ goff,
-                   const float4 *__restrict__ gval, const float *__restrict__ t32c, const uint64_t *__restrict__ total, uint64_t *__restrict__ sums)
-{
-    __shared__ uint64_t lds[4];
-    if (threadIdx.x < 4) lds[threadIdx.x] = 0;
-    __syncthreads();
-    const int n = (int)counts[blockIdx.x];
-    const unsigned long long base = offs[blockIdx.x];
-    uint64_t s[ROPE_SUM_WORDS];
-    s[SUM_S1] = s[SUM_AA] = s[SUM_AB] = s[SUM_BB] = 0;
-    for (int g = threadIdx.x; g < n; g += blockDim.x) table_group_delta(*reinterpret_cast<const float4 *>(t32c + goff[base + g]), gval[base + g], s);
-    const int words[4] = {SUM_S1, SUM_AA, SUM_AB, SUM_BB};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        uint64_t v = s[words[k]];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd((unsigned long long *)&lds[k], (unsigned long long)v);
-    }
-    __syncthreads();
-    if (threadIdx.x < ROPE_SUM_WORDS) {
-        uint64_t v = 0;
-        for (int k = 0; k < 4; k++) if ((int)threadIdx.x == words[k]) v = total[words[k]] + lds[k];
-        sums[(size_t)blockIdx.x * ROPE_SUM_WORDS + threadIdx.x] = v;
-    }
-}
-
-__device__ static inline double mean_std_parts(const uint64_t *s, double N, double &m1);
-
-// The same for the targets of many frames (rope_lookup_score_targets): grid = (table rows, frame chunks), and inside a workgroup
-// one group of LANES lanes per (row, TABLE_FRAMES frames) — a row's few hundred groups are a handful per lane, so this needs no
-// barrier and no LDS: a lane reads a group of the row once and holds it against TABLE_FRAMES frames' samples at that place (their
-// loads in flight together), the lanes' partial sums meet by lane exchange and the group's first lane writes the finished lookup
-// scores (finalize_one's steps for ROPE_LOSS_LOOKUP on the same sums: same bits) to scores[frame x rows + row].  The kernel lives on its arithmetic
-// (two Q32 conversions and six 64-bit multiply-adds per sample) and on the waves in flight: few frames per wave, see the launch.
-template <int TABLE_FRAMES, int LANES /* of a wave that share one frame: 64, or 16 (four frames side by side in a wave) */>
-__global__ void __launch_bounds__(256)
-table_score_frames_kernel(int crop_px /* padded: 4 x groups */, const uint32_t *__restrict__ counts, const unsigned long long *__restrict__ offs,
-                          const uint32_t *__restrict__ goff, const float4 *__restrict__ gval, const float *__restrict__ t32c /* frames x crop_px */,
-                          const uint64_t *__restrict__ totals /* frames x ROPE_SUM_WORDS */, int n_frames, double n_pix,
-                          double *__restrict__ scores)
-{
-    // With LANES = 16 a wave holds four frame groups side by side: a row's few hundred groups are then twenty per lane instead of
-    // five with the last step a third empty, the lane exchange is four steps instead of six and serves four times the frames, and
-    // the float64 epilogue of four frames runs in four lanes at once.
-    constexpr int PARTS = 64 / LANES, PER_WAVE = PARTS * TABLE_FRAMES;
-    const int n = (int)counts[blockIdx.x], lane = threadIdx.x & 63, wave = threadIdx.x >> 6, part = lane / LANES, sub = lane % LANES;
-    const unsigned long long base = offs[blockIdx.x];
-    const int per = (n_frames + (int)gridDim.y - 1) / (int)gridDim.y, f_lo = (int)blockIdx.y * per, f_hi = min(f_lo + per, n_frames);
-    for (int fw = f_lo + wave * PER_WAVE; fw < f_hi; fw += 4 * PER_WAVE) {
-        const int f0 = fw + part * TABLE_FRAMES;                 // this lane group's first frame
-        const int nf = max(0, min(TABLE_FRAMES, f_hi - f0));
-        uint64_t s[TABLE_FRAMES][SUM_BB + 1];
-#pragma unroll
-        for (int j = 0; j < TABLE_FRAMES; j++)
-#pragma unroll
-            for (int k = 0; k <= SUM_BB; k++) s[j][k] = 0;
-        const float *__restrict__ t0 = t32c + (size_t)min(f0, n_frames - 1) * crop_px;
-        if (nf > 0)
-            for (int g = sub; g < n; g += LANES) {
-                const uint32_t off = goff[base + g];
-                const float4 d = gval[base + g];
-                float4 t[TABLE_FRAMES];
-#pragma unroll
-                for (int j = 0; j < TABLE_FRAMES; j++)
-                    t[j] = j < nf ? *reinterpret_cast<const float4 *>(t0 + (size_t)j * crop_px + off) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll
-                for (int j = 0; j < TABLE_FRAMES; j++) table_group_delta(t[j], d, s[j]);
-            }
-#pragma unroll
-        for (int j = 0; j < TABLE_FRAMES; j++) {
-            uint64_t r[ROPE_SUM_WORDS];
-#pragma unroll
-            for (int k = SUM_S1; k <= SUM_BB; k++) {
-                uint64_t v = s[j][k];
-#pragma unroll
-                for (int off = LANES / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);      // stays inside the lane group
-                r[k] = v;
-            }
-            if (sub == 0 && j < nf) {
-                const uint64_t *total = totals + (size_t)(f0 + j) * ROPE_SUM_WORDS;
-#pragma unroll
-                for (int k = SUM_S1; k <= SUM_BB; k++) r[k] += total[k];
-                double m1;
-                const double sd = mean_std_parts(r, n_pix, m1);
-                scores[(size_t)(f0 + j) * gridDim.x + blockIdx.x] = m1 * sd;
-            }
-        }
-    }
-}
-
 // ---------------------------------------------------------------- finalize -----
-__device__ static inline double mean_std_parts(const uint64_t *s, double N, double &m1)
-{
-    m1 = ((double)s[SUM_S1] * 0x1p-32) / N;
-    double S2 = ((double)s[SUM_AA] * 0x1p40 + (double)s[SUM_AB] * 0x1p21) + (double)s[SUM_BB];
-    double m2 = (S2 * 0x1p-64) / N;
-    double var = m2 - m1 * m1;
-    if (var < 0.0) var = 0.0;
-    return sqrt(var);
-}
-
 // sums -> float64 error of one candidate (the reference's order of operations, predict.py:480-509)
 __device__ static inline double finalize_one(uint64_t *__restrict__ sums, const uint64_t *__restrict__ total_empty, int c, int loss,
                                              int n_render, double n_pix, const LinkFlags &lf)
@@ -2090,45 +1420,46 @@ hipError_t launch_raster(int mode, int loss, int rows, hipStream_t st, const Fra
     return hipGetLastError();
 }
 
+// score_queue_kernel sorts the (row, tile) pairs that have something to draw into the queue by `weights`, then `workgroups`
+// resident workgroups of raster_queue_kernel<loss, mode> drain it.  The camera-pose loss has no shared layers: MODE_LAYER has no
+// instantiation for it.
+static hipError_t launch_queue(int mode, int loss, int rows, int workgroups, hipStream_t st, const FrameParams &fp, const RobotParams &rp,
+                               const RasterArgs &a, uint32_t *items, size_t segment, int *counters, const uint32_t *weights, bool clip)
+{
+    const int n_tiles = fp.tiles_x * fp.tiles_y;
+    hipLaunchKernelGGL(score_queue_kernel, dim3((rows + 7) / 8, a.mask_words), dim3(256), 0, st, a, rows, n_tiles, items, segment, counters, weights);
+    const dim3 grid(workgroups);
+    if (mode == MODE_LAYER) {
+        if (loss == ROPE_LOSS_DEPTH) launch_queue_one<ROPE_LOSS_DEPTH, MODE_LAYER>(grid, st, fp, rp, a, items, segment, counters, clip);
+        else if (loss == ROPE_LOSS_FULL) launch_queue_one<ROPE_LOSS_FULL, MODE_LAYER>(grid, st, fp, rp, a, items, segment, counters, clip);
+        else if (loss == ROPE_LOSS_LOOKUP) launch_queue_one<ROPE_LOSS_LOOKUP, MODE_LAYER>(grid, st, fp, rp, a, items, segment, counters, clip);
+        else launch_queue_one<ROPE_LOSS_TSWEEP, MODE_LAYER>(grid, st, fp, rp, a, items, segment, counters, clip);
+    }
+    else if (loss == ROPE_LOSS_DEPTH) launch_queue_one<ROPE_LOSS_DEPTH, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip);
+    else if (loss == ROPE_LOSS_FULL) launch_queue_one<ROPE_LOSS_FULL, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip);
+    else if (loss == ROPE_LOSS_LOOKUP) launch_queue_one<ROPE_LOSS_LOOKUP, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip);
+    else if (loss == ROPE_LOSS_CAMFULL) launch_queue_one<ROPE_LOSS_CAMFULL, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip);
+    else launch_queue_one<ROPE_LOSS_TSWEEP, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip);
+    return hipGetLastError();
+}
+
 hipError_t launch_raster_queue(int loss, int rows, int workgroups, hipStream_t st, const FrameParams &fp, const RobotParams &rp,
                                const RasterArgs &a, uint32_t *items, size_t segment, int *counters, const uint32_t *tile_tris, bool clip)
 {
-    const int n_tiles = fp.tiles_x * fp.tiles_y;
-    hipLaunchKernelGGL(score_queue_kernel, dim3((rows + 7) / 8, a.mask_words), dim3(256), 0, st, a, rows, n_tiles, items, segment, counters, tile_tris);
-    const dim3 grid(workgroups);
-    switch (loss) {
-    case ROPE_LOSS_DEPTH: launch_queue_one<ROPE_LOSS_DEPTH, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip); break;
-    case ROPE_LOSS_FULL: launch_queue_one<ROPE_LOSS_FULL, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip); break;
-    case ROPE_LOSS_LOOKUP: launch_queue_one<ROPE_LOSS_LOOKUP, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip); break;
-    case ROPE_LOSS_CAMFULL: launch_queue_one<ROPE_LOSS_CAMFULL, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip); break;
-    default: launch_queue_one<ROPE_LOSS_TSWEEP, MODE_SCORE>(grid, st, fp, rp, a, items, segment, counters, clip); break;
-    }
-    return hipGetLastError();
+    return launch_queue(MODE_SCORE, loss, rows, workgroups, st, fp, rp, a, items, segment, counters, tile_tris, clip);
 }
 
 hipError_t launch_layer_queue(int loss, int rows, int workgroups, hipStream_t st, const FrameParams &fp, const RobotParams &rp,
                               const RasterArgs &a, uint32_t *items, size_t segment, int *counters, const uint32_t *tile_tris_lo, bool clip)
 {
-    const int n_tiles = fp.tiles_x * fp.tiles_y;
-    hipLaunchKernelGGL(score_queue_kernel, dim3((rows + 7) / 8, a.mask_words), dim3(256), 0, st, a, rows, n_tiles, items, segment, counters, tile_tris_lo);
-    const dim3 grid(workgroups);
-    if (loss == ROPE_LOSS_DEPTH) launch_queue_one<ROPE_LOSS_DEPTH, MODE_LAYER>(grid, st, fp, rp, a, items, segment, counters, clip);
-    else if (loss == ROPE_LOSS_FULL) launch_queue_one<ROPE_LOSS_FULL, MODE_LAYER>(grid, st, fp, rp, a, items, segment, counters, clip);
-    else if (loss == ROPE_LOSS_LOOKUP) launch_queue_one<ROPE_LOSS_LOOKUP, MODE_LAYER>(grid, st, fp, rp, a, items, segment, counters, clip);
-    else launch_queue_one<ROPE_LOSS_TSWEEP, MODE_LAYER>(grid, st, fp, rp, a, items, segment, counters, clip);
-    return hipGetLastError();
+    return launch_queue(MODE_LAYER, loss, rows, workgroups, st, fp, rp, a, items, segment, counters, tile_tris_lo, clip);
 }
 
 hipError_t launch_score_gtile(int loss, int rows, int slices, hipStream_t st, const FrameParams &fp, const RasterArgs &a)
 {
     dim3 grid(fp.tiles_x * fp.tiles_y, rows, slices);
-    switch (loss) {
-    case ROPE_LOSS_DEPTH: hipLaunchKernelGGL(score_gtile_kernel<ROPE_LOSS_DEPTH>, grid, dim3(256), 0, st, fp, a); break;
-    case ROPE_LOSS_FULL: hipLaunchKernelGGL(score_gtile_kernel<ROPE_LOSS_FULL>, grid, dim3(256), 0, st, fp, a); break;
-    case ROPE_LOSS_LOOKUP: hipLaunchKernelGGL(score_gtile_kernel<ROPE_LOSS_LOOKUP>, grid, dim3(256), 0, st, fp, a); break;
-    case ROPE_LOSS_CAMFULL: hipLaunchKernelGGL(score_gtile_kernel<ROPE_LOSS_CAMFULL>, grid, dim3(256), 0, st, fp, a); break;
-    default: hipLaunchKernelGGL(score_gtile_kernel<ROPE_LOSS_TSWEEP>, grid, dim3(256), 0, st, fp, a); break;
-    }
+    const auto launch = [&](auto l) { hipLaunchKernelGGL(score_gtile_kernel<decltype(l)::value>, grid, dim3(256), 0, st, fp, a); };
+    if (!with_loss<LOSSES_ALL>(loss, launch)) launch(std::integral_constant<int, ROPE_LOSS_TSWEEP>{});      // any other value: as ROPE_LOSS_TSWEEP
     return hipGetLastError();
 }
 
@@ -2142,40 +1473,8 @@ hipError_t launch_clear_pass(hipStream_t st, uint64_t *sums, int C, int *queue_c
 hipError_t launch_layer_sums(int loss, int n_layers, hipStream_t st, const FrameParams &fp, const RasterArgs &a)
 {
     const dim3 grid(fp.tiles_x * fp.tiles_y, n_layers);
-    switch (loss) {
-    case ROPE_LOSS_DEPTH: hipLaunchKernelGGL(layer_sums_kernel<ROPE_LOSS_DEPTH>, grid, dim3(NTHREADS), 0, st, fp, a); break;
-    case ROPE_LOSS_FULL: hipLaunchKernelGGL(layer_sums_kernel<ROPE_LOSS_FULL>, grid, dim3(NTHREADS), 0, st, fp, a); break;
-    case ROPE_LOSS_LOOKUP: hipLaunchKernelGGL(layer_sums_kernel<ROPE_LOSS_LOOKUP>, grid, dim3(NTHREADS), 0, st, fp, a); break;
-    case ROPE_LOSS_TSWEEP: hipLaunchKernelGGL(layer_sums_kernel<ROPE_LOSS_TSWEEP>, grid, dim3(NTHREADS), 0, st, fp, a); break;
-    default: return hipErrorInvalidValue;          // the camera-pose loss has no shared layers
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_fragment_count(hipStream_t st, const RasterArgs &a, const uint32_t *own, int row0, int rows, int n_tiles, uint32_t *counts)
-{
-    hipLaunchKernelGGL(fragment_count_kernel, dim3(n_tiles, rows), dim3(256), 0, st, a, own, row0, n_tiles, counts);
-    return hipGetLastError();
-}
-
-hipError_t launch_fragment_fill(hipStream_t st, const RasterArgs &a, const uint32_t *own, int row0, int rows, int n_tiles,
-                                const unsigned long long *offs, uint32_t *where, uint4 *finished, uint4 *base_keys)
-{
-    hipLaunchKernelGGL(fragment_fill_kernel, dim3(n_tiles, rows), dim3(256), 0, st, a, own, row0, n_tiles, offs, where, finished, base_keys);
-    return hipGetLastError();
-}
-
-hipError_t launch_fragment_score(int loss, int rows, hipStream_t st, const FrameParams &fp, const RasterArgs &a, const unsigned long long *offs,
-                                 const uint32_t *where, const uint4 *finished, const uint4 *base_keys)
-{
-    const dim3 grid(rows);
-    switch (loss) {
-    case ROPE_LOSS_DEPTH: hipLaunchKernelGGL(fragment_score_kernel<ROPE_LOSS_DEPTH>, grid, dim3(256), 0, st, fp, a, offs, where, finished, base_keys); break;
-    case ROPE_LOSS_FULL: hipLaunchKernelGGL(fragment_score_kernel<ROPE_LOSS_FULL>, grid, dim3(256), 0, st, fp, a, offs, where, finished, base_keys); break;
-    case ROPE_LOSS_LOOKUP: hipLaunchKernelGGL(fragment_score_kernel<ROPE_LOSS_LOOKUP>, grid, dim3(256), 0, st, fp, a, offs, where, finished, base_keys); break;
-    case ROPE_LOSS_TSWEEP: hipLaunchKernelGGL(fragment_score_kernel<ROPE_LOSS_TSWEEP>, grid, dim3(256), 0, st, fp, a, offs, where, finished, base_keys); break;
-    default: return hipErrorInvalidValue;          // the camera-pose loss has no shared layers, so no kept fragments either
-    }
+    if (!with_loss<LOSSES_LAYERED>(loss, [&](auto l) { hipLaunchKernelGGL(layer_sums_kernel<decltype(l)::value>, grid, dim3(NTHREADS), 0, st, fp, a); }))
+        return hipErrorInvalidValue;               // the camera-pose loss has no shared layers
     return hipGetLastError();
 }
 
@@ -2183,13 +1482,8 @@ hipError_t launch_empty(int loss, hipStream_t st, const FrameParams &fp, const u
                         uint64_t *empty_sums, uint64_t *total, int n_frames)
 {
     dim3 grid(fp.tiles_x * fp.tiles_y, n_frames);
-    switch (loss) {
-    case ROPE_LOSS_DEPTH: hipLaunchKernelGGL(empty_tile_kernel<ROPE_LOSS_DEPTH>, grid, dim3(NTHREADS), 0, st, fp, tq, t32, tl, empty_sums); break;
-    case ROPE_LOSS_FULL: hipLaunchKernelGGL(empty_tile_kernel<ROPE_LOSS_FULL>, grid, dim3(NTHREADS), 0, st, fp, tq, t32, tl, empty_sums); break;
-    case ROPE_LOSS_LOOKUP: hipLaunchKernelGGL(empty_tile_kernel<ROPE_LOSS_LOOKUP>, grid, dim3(NTHREADS), 0, st, fp, tq, t32, tl, empty_sums); break;
-    case ROPE_LOSS_CAMFULL: hipLaunchKernelGGL(empty_tile_kernel<ROPE_LOSS_CAMFULL>, grid, dim3(NTHREADS), 0, st, fp, tq, t32, tl, empty_sums); break;
-    default: hipLaunchKernelGGL(empty_tile_kernel<ROPE_LOSS_TSWEEP>, grid, dim3(NTHREADS), 0, st, fp, tq, t32, tl, empty_sums); break;
-    }
+    const auto launch = [&](auto l) { hipLaunchKernelGGL(empty_tile_kernel<decltype(l)::value>, grid, dim3(NTHREADS), 0, st, fp, tq, t32, tl, empty_sums); };
+    if (!with_loss<LOSSES_ALL>(loss, launch)) launch(std::integral_constant<int, ROPE_LOSS_TSWEEP>{});      // any other value: as ROPE_LOSS_TSWEEP
     hipLaunchKernelGGL(total_tiles_kernel, dim3(n_frames), dim3(64), 0, st, empty_sums, fp.tiles_x * fp.tiles_y, total);
     return hipGetLastError();
 }
@@ -2214,54 +1508,6 @@ hipError_t launch_finalize_frames(hipStream_t st, uint64_t *sums, const uint64_t
 hipError_t launch_argmin_sets(hipStream_t st, const double *err, int C, int n_sets, double *best)
 {
     hipLaunchKernelGGL(argmin_sets_kernel, dim3(n_sets), dim3(C <= 64 ? 64 : (C <= 256 ? 256 : 1024)), 0, st, err, C, best);
-    return hipGetLastError();
-}
-
-hipError_t launch_table_score_frames(hipStream_t st, const FrameParams &fp, const uint32_t *counts, const unsigned long long *offs,
-                                     const uint32_t *goff, const float4 *gval, int C, const float *t32, int n_frames, float *t32c, uint64_t *totals,
-                                     double *scores, double *best)
-{
-    const int cw = fp.c1 - fp.c0 + 1, ch = fp.r1 - fp.r0 + 1;
-    hipLaunchKernelGGL(crop_total_kernel, dim3(n_frames), dim3(1024), 0, st, fp, t32, t32c, totals);
-    // A workgroup takes 4 x F frames (F per wave), and the grid walks the table once per such chunk of frames (rows fastest): the
-    // chunk's cropped targets stay in L2 while every row gathers from them, and the table streams past once per chunk.
-    // Measured for 256 frames x 15 625 rows at 160x90 (tools/r03_tbl_run.sh), a whole wave per frame group: F = 8 7.2 ms (221
-    // registers, two waves per SIMD), F = 4 5.1 ms, F = 2 4.8-5.0 ms; one frame per wave and every frame in one workgroup (round 3's
-    // first form) 6.6 ms.  With F = 2 and the wave split into lane groups of 32 / 16 / 8: 4.0 / 3.4 / 3.2 ms.
-    static const int F = [] { const char *e = std::getenv("ROPE_TABLE_FRAMES"); const int v = e ? std::atoi(e) : 2; return v == 4 || v == 8 ? v : 2; }();
-    static const int LANES = [] { const char *e = std::getenv("ROPE_TABLE_LANES"); const int v = e ? std::atoi(e) : 16; return v == 64 || v == 8 ? v : 16; }();
-    const int per_wg = 4 * F * (64 / LANES);
-    const int chunks = std::max(1, (n_frames + per_wg - 1) / per_wg);
-    const dim3 grid(C, chunks);
-    const int words = (int)table_crop_words(fp);
-    const double n_pix = (double)cw * (double)ch;
-#define ROPE_TABLE_LAUNCH(F_, L_) hipLaunchKernelGGL((table_score_frames_kernel<F_, L_>), grid, dim3(256), 0, st, words, counts, offs, goff, gval, t32c, totals, n_frames, n_pix, scores)
-    if (LANES == 16) { if (F == 2) ROPE_TABLE_LAUNCH(2, 16); else if (F == 4) ROPE_TABLE_LAUNCH(4, 16); else ROPE_TABLE_LAUNCH(8, 16); }
-    else if (LANES == 8) { if (F == 2) ROPE_TABLE_LAUNCH(2, 8); else ROPE_TABLE_LAUNCH(4, 8); }
-    else { if (F == 2) ROPE_TABLE_LAUNCH(2, 64); else if (F == 4) ROPE_TABLE_LAUNCH(4, 64); else ROPE_TABLE_LAUNCH(8, 64); }
-#undef ROPE_TABLE_LAUNCH
-    hipLaunchKernelGGL(argmin_sets_kernel, dim3(n_frames), dim3(C <= 64 ? 64 : (C <= 256 ? 256 : 1024)), 0, st, scores, C, best);
-    return hipGetLastError();
-}
-
-hipError_t launch_table_count(hipStream_t st, int cw, int ch, const float *table, int C, uint32_t *counts, unsigned long long *offs,
-                              unsigned long long *used)
-{
-    hipLaunchKernelGGL(table_count_kernel, dim3(C), dim3(256), 0, st, cw, ch, table, counts, offs, used);
-    return hipGetLastError();
-}
-
-hipError_t launch_table_fill(hipStream_t st, int cw, int ch, const float *table, int C, const unsigned long long *offs, uint32_t *goff, float4 *gval)
-{
-    hipLaunchKernelGGL(table_fill_kernel, dim3(C), dim3(256), 0, st, cw, ch, table, offs, goff, gval);
-    return hipGetLastError();
-}
-
-hipError_t launch_table_score(hipStream_t st, const FrameParams &fp, const uint32_t *counts, const unsigned long long *offs, const uint32_t *goff,
-                              const float4 *gval, int C, const float *t32, float *t32c, uint64_t *total, uint64_t *sums)
-{
-    hipLaunchKernelGGL(crop_total_kernel, dim3(1), dim3(1024), 0, st, fp, t32, t32c, total);
-    hipLaunchKernelGGL(table_score_kernel, dim3(C), dim3(256), 0, st, counts, offs, goff, gval, t32c, total, sums);
     return hipGetLastError();
 }
 

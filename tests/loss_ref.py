@@ -3,7 +3,7 @@
 sums_ref is written from the contract alone — DESIGN.md §3 steps 6-7, its "Camera-pose path" section for the ROPE_LOSS_CAMFULL
 words, and the comments on rope_set_target / rope_set_frames in include/rope_s3d.h: one loop over the pixels of the image, no
 tiles, no delta form, "nothing rendered" is z = 0 and nothing else.  The builders below make the targets whose VALUES take the
-branches of score_pixel / score_tile (rope_kernels.hip) that a render of the robot a few degrees away never takes.
+branches of score_pixel / score_tile (rope_lossmath.h) that a render of the robot a few degrees away never takes.
 
 Domain.  Bits 39 and 48-63 of a tq word are outside the header's contract, and the builders never set them.  Non-finite or
 negative float targets are outside it too — there the oracle's q32_of_f32 is a C conversion with no defined result — and the
@@ -164,7 +164,7 @@ def n_pix_of(loss, W, H, crop):
 
 # ------------------------------------------------------------------------------------------------ the kernels' block mapping
 def samples_per_thread(n_threads, r_lo, r_hi, block_g, live):
-    """score_tile's delta form (rope_kernels.hip): item `it` of rows r_lo..r_hi of a tile is the four-sample group g of tile row
+    """score_tile's delta form (rope_lossmath.h): item `it` of rows r_lo..r_hi of a tile is the four-sample group g of tile row
     `row`; thread t takes the items t, t + n_threads, ...  -> the most samples of live (TILE_H, TILE_W bool) one thread meets."""
     bg, brows, bpr_sh = block_g, 64 >> block_g, 5 - block_g
     n_items = (r_hi - r_lo + 1) * (TILE_W // 4)

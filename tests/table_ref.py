@@ -1,5 +1,5 @@
-"""The stored lookup table (rope_kernels.hip: crop_total / table_count / table_fill / table_score / table_score_frames /
-argmin_sets / finalize for ROPE_LOSS_LOOKUP) restated plainly, and the inputs the GPU tests feed those kernels.
+"""The stored lookup table (rope_table.hip: crop_total / table_count / table_fill / table_score / table_score_frames;
+rope_kernels.hip: argmin_sets / finalize for ROPE_LOSS_LOOKUP) restated plainly, and the inputs the GPU tests feed those kernels.
 
 The reference is dense and exact: no compaction, no "total minus what the groups change" — every sample of the unpadded crop is
 converted and summed as Python integers, and the float64 epilogue is mean_std_parts' written order in Python floats (IEEE

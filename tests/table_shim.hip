@@ -1,11 +1,11 @@
-// The stored lookup table's launch helpers (rope_kernels.hip: table_count / table_fill / crop_total / table_score /
-// table_score_frames<F, LANES> / argmin_sets / finalize) on tables, target planes and errors the test supplies: the library only
+// The stored lookup table's launch helpers (rope_table.hip: table_count / table_fill / crop_total / table_score /
+// table_score_frames<F, LANES>; rope_kernels.hip: argmin_sets / finalize) on tables, target planes and errors the test supplies: the library only
 // ever feeds them rows the rasteriser has just drawn, and entry points of their own in rope_abi.hip would change rope_build_id.
 // Built by tests/test_gpu_table_kernels.py with build.HIPCC_FLAGS into a temporary directory and LINKED against the built
 // librope_hip.so (the helpers are plain members of namespace rope and the library is built with default visibility), so the
 // kernels that run are the shipped ones; never part of librope_hip.so.
 //
-// FrameParams is built from (W, H, r0, r1, c0, c1) with every other member zero.  By reading rope_kernels.hip: crop_total_kernel
+// FrameParams is built from (W, H, r0, r1, c0, c1) with every other member zero.  By reading rope_table.hip: crop_total_kernel
 // reads fp.W, fp.H, fp.r0, fp.r1, fp.c0, fp.c1 and nothing else; launch_table_score_frames and table_crop_words read r0, r1, c0,
 // c1; no other kernel of this group takes a FrameParams.  launch_finalize is given ROPE_LOSS_LOOKUP's arguments: finalize_one
 // reads the LinkFlags and n_render only for ROPE_LOSS_FULL, so zero flags and n_render = 0 stand for any.

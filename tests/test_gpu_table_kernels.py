@@ -1,5 +1,5 @@
-"""The stored lookup table's kernels (rope_kernels.hip: crop_total, table_count, table_fill, table_score,
-table_score_frames<F, LANES>, argmin_sets and the ROPE_LOSS_LOOKUP branch of finalize) on tables and targets the test supplies,
+"""The stored lookup table's kernels (rope_table.hip: crop_total, table_count, table_fill, table_score,
+table_score_frames<F, LANES>; rope_kernels.hip: argmin_sets and the ROPE_LOSS_LOOKUP branch of finalize) on tables and targets the test supplies,
 through tests/table_shim.hip — bit for bit against the dense reference of tests/table_ref.py, which tests/test_table_refs.py
 holds to the oracle on the CPU and whose builders it shows to reach the edges they are named for.  The engine only ever feeds
 these kernels rows the robot happens to draw, at crops with cw % 4 == 1; here: every cw % 4, cw < 4, one crop row, the whole image,

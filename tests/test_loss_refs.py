@@ -153,7 +153,7 @@ def test_packed_count_fields_hold_the_all_masks_tile():
     thread's count per link is the number of samples it meets.  768 threads over a whole tile (raster_tile, layer_sums_kernel,
     empty_tile_kernel) and 256 threads over 96 / bands rows (score_gtile_kernel) must stay below the 10-bit fields of
     ROPE_LOSS_CAMFULL, so below the 12-bit ones of ROPE_LOSS_FULL too.  The mapping, the thread counts, the block widths 2 / 4 / 4
-    and the band counts are restated here from rope_kernels.hip and rope_abi.hip: this is arithmetic on a copy, no guard on the
+    and the band counts are restated here from rope_lossmath.h, rope_kernels.hip and rope_abi.hip: this is arithmetic on a copy, no guard on the
     kernels — whoever changes the mapping there has to change it in loss_ref.py as well for the test to say anything."""
     live = np.ones((R.TILE_H, R.TILE_W), bool)
     most = {'raster_tile': R.samples_per_thread(768, 0, 95, 2, live), 'layer_sums': R.samples_per_thread(768, 0, 95, 4, live),

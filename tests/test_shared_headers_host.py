@@ -1,11 +1,12 @@
 """CPU: the text the normal-equation files and the polish files share exists once.  csrc/rope_neq.h and csrc/rope_solve.h are
-headers: part of the build id, no translation units; and no source file of the library defines a copy of what they hold."""
+headers: part of the build id, no translation units; and no source file of the library defines a copy of what they hold.
+csrc/rope_lossmath.h and csrc/rope_launch.h, which the kernel files share, are held to the first half of that."""
 import os
 import re
 
 from rope_s3d_amd import build
 
-HEADERS = ('rope_neq.h', 'rope_solve.h')
+HEADERS = ('rope_neq.h', 'rope_solve.h', 'rope_lossmath.h', 'rope_launch.h')
 
 
 def _text(name):
