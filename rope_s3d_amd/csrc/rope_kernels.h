@@ -180,6 +180,10 @@ hipError_t launch_raster_queue(int loss, int rows, int workgroups, hipStream_t s
 // the same for a MODE_LAYER launch (a.cand_of_row set): (layer, tile) pairs of the representatives' shared links, by their weight
 hipError_t launch_layer_queue(int loss, int rows, int workgroups, hipStream_t st, const FrameParams &fp, const RobotParams &rp,
                               const RasterArgs &a, uint32_t *items, size_t segment, int *counters, const uint32_t *tile_tris_lo, bool clip);
+// the queue alone, as the two launches above build it before they drain it: a.mask_lo, a.mask_hi, a.mask_words, a.layer_of, a.layer_rep,
+// a.layer_sums, a.cand_of_row and a.sums are read; counters[2 + k] counts the pairs of class k, counters[0 .. 1] are left alone
+hipError_t launch_score_queue(hipStream_t st, const RasterArgs &a, int rows, int n_tiles, uint32_t *items, size_t segment, int *counters,
+                              const uint32_t *weights);
 // A pass that keeps the last one's geometry (rope_ctx::geo).  launch_clear_pass: what fk_mvp_kernel clears besides working out
 // matrices — the C rows of sums and the 2 x QUEUE_COUNTERS queue counters (or nullptr).  launch_layer_sums: the loss sums of every
 // stored layer tile against the current target, what the MODE_LAYER launch leaves in a.layer_sums — a.cand_of_row (layer ->

@@ -1420,6 +1420,14 @@ hipError_t launch_raster(int mode, int loss, int rows, hipStream_t st, const Fra
     return hipGetLastError();
 }
 
+// The first half of launch_queue on its own: eight rows a workgroup, one grid row per mask word
+hipError_t launch_score_queue(hipStream_t st, const RasterArgs &a, int rows, int n_tiles, uint32_t *items, size_t segment, int *counters,
+                              const uint32_t *weights)
+{
+    hipLaunchKernelGGL(score_queue_kernel, dim3((rows + 7) / 8, a.mask_words), dim3(256), 0, st, a, rows, n_tiles, items, segment, counters, weights);
+    return hipGetLastError();
+}
+
 // score_queue_kernel sorts the (row, tile) pairs that have something to draw into the queue by `weights`, then `workgroups`
 // resident workgroups of raster_queue_kernel<loss, mode> drain it.  The camera-pose loss has no shared layers: MODE_LAYER has no
 // instantiation for it.
@@ -1427,7 +1435,7 @@ static hipError_t launch_queue(int mode, int loss, int rows, int workgroups, hip
                                const RasterArgs &a, uint32_t *items, size_t segment, int *counters, const uint32_t *weights, bool clip)
 {
     const int n_tiles = fp.tiles_x * fp.tiles_y;
-    hipLaunchKernelGGL(score_queue_kernel, dim3((rows + 7) / 8, a.mask_words), dim3(256), 0, st, a, rows, n_tiles, items, segment, counters, weights);
+    if (hipError_t e = launch_score_queue(st, a, rows, n_tiles, items, segment, counters, weights)) return e;
     const dim3 grid(workgroups);
     if (mode == MODE_LAYER) {
         if (loss == ROPE_LOSS_DEPTH) launch_queue_one<ROPE_LOSS_DEPTH, MODE_LAYER>(grid, st, fp, rp, a, items, segment, counters, clip);

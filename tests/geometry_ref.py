@@ -6,6 +6,8 @@ box_exact      meshlet_box one float32 IEEE operation at a time (the library is 
 box_bounds64   the same eight corners projected in float64, in no particular order of operations, and what the design promises of a
                box: conservative, tight, the flag bits; check_boxes() holds any boxes (box_exact's or a kernel's) to it.
 finalize_ref   finalize_one / mean_std_parts: Python integers modulo 2^64, numpy float64 in the kernel's order; argmin() its rule.
+queue_ref      score_queue_kernel: the (row, tile) pairs of every weight class, their counts and the sums after the layer-only tiles,
+               a loop over rows and tiles in Python integers; clear_pass_ref: clear_pass_kernel's zeros.
 
 fmaf: a float32 fused multiply-add rounds ONCE.  float64 a * b + c rounds twice (the product of two float32 is exact in float64, the
 sum is rounded to 53 bits and then to 24), and so would math.fma on doubles followed by a conversion — this Python (3.10) has no
@@ -42,7 +44,8 @@ def constants():
         return int(m.group(1))
     c = dict(TILE_W=num('ROPE_TILE_W'), TILE_H=num('ROPE_TILE_H'), MAX_MASK_WORDS=num('MAX_MASK_WORDS'),
              QUEUE_WEIGHT_TILES=num('QUEUE_WEIGHT_TILES'), QUEUE_COUNTERS=2 + num('ROPE_QUEUE_CLASSES'), COMPACT_PX=num('COMPACT_PX'),
-             SUM_WORDS=num('ROPE_SUM_WORDS'), MAX_LINKS=num('ROPE_MAX_LINKS'), MAX_MESHLETS=num('MAX_MESHLETS'))
+             SUM_WORDS=num('ROPE_SUM_WORDS'), MAX_LINKS=num('ROPE_MAX_LINKS'), MAX_MESHLETS=num('MAX_MESHLETS'),
+             QUEUE_CLASSES=num('ROPE_QUEUE_CLASSES'), QUEUE_TOP_LOG2=num('ROPE_QUEUE_TOP_LOG2'))
     for k, name in enumerate(('DEPTH', 'FULL', 'LOOKUP', 'TSWEEP')):
         c['LOSS_' + name] = num('ROPE_LOSS_' + name)
         assert c['LOSS_' + name] == k
@@ -50,7 +53,7 @@ def constants():
 
 
 SHIM_CONSTANTS = ('TILE_W', 'TILE_H', 'MAX_MASK_WORDS', 'QUEUE_WEIGHT_TILES', 'QUEUE_COUNTERS', 'COMPACT_PX', 'SUM_WORDS', 'MAX_LINKS',
-                  'LOSS_DEPTH', 'LOSS_FULL', 'LOSS_LOOKUP', 'LOSS_TSWEEP', 'MAX_MESHLETS')         # shim_constant(i), in this order
+                  'LOSS_DEPTH', 'LOSS_FULL', 'LOSS_LOOKUP', 'LOSS_TSWEEP', 'MAX_MESHLETS', 'QUEUE_CLASSES', 'QUEUE_TOP_LOG2')   # shim_constant(i), in this order
 SUM_CNT, SUM_S1, SUM_AA, SUM_AB, SUM_BB, SUM_LINK0 = range(6)                                      # rope_kernels.h's enum
 EMPTY_BOX = (1, 0, 1, 0)
 
@@ -837,3 +840,200 @@ def finalize_frames_case(C, loss, n_render, n_pix=76800):
     err, words = finalize_ref(sums, totals[frame_of], loss, n_render, n_pix, flags[frame_of])
     return dict(C=C, loss=loss, n_render=n_render, n_pix=float(n_pix), flags=flags, totals=totals, frame_of=frame_of, sums=sums, err=err,
                 words=words, final=rows)
+
+
+# ------------------------------------------------------------------------------------------------ the raster queue's builder
+# score_queue_kernel in its three forms (what raster_queue_kernel, bounds_kernel and rope_abi.hip rely on):
+#   plain       neither map: a row's pairs are the tiles in hi | lo of the row itself, weighed at the row
+#   layers      layer_of set: the pairs are the tiles in hi; lo is that of the row's layer's representative, and every tile in lo & ~hi
+#               adds the layer's stored sums of that tile into the row's sums (modulo 2^64)
+#   for_layers  cand_of_row set: the pairs are the tiles in lo of rep = cand_of_row[row], weighed at rep; the item names the row
+# A pair of weight t goes to class clamp(QUEUE_TOP_LOG2 - floor(log2(t | 1)), 0, QUEUE_CLASSES - 1), t an unsigned 32-bit number;
+# without weights every pair goes to the last class.  An item is row | tile << 16.
+QUEUE_FORMS = ('plain', 'layers', 'for_layers', 'unweighted plain', 'unweighted layers')
+WRONG_QUEUE = ('class one up', 'class one down', 'weights at the row for rep', 'weights at rep for the row', 'lo of the row itself',
+               'layer_sums by candidate', 'store for add', 'hi | lo queued with layers')
+
+
+def queue_class(tris, shift=0):
+    k = constants()
+    assert 0 <= tris < 1 << 32
+    return min(max(k['QUEUE_TOP_LOG2'] - ((tris | 1).bit_length() - 1) + shift, 0), k['QUEUE_CLASSES'] - 1)
+
+
+def queue_weight_table():
+    """0, 1, every power of two from 2^(TOP - CLASSES) to 2^(TOP + 1) with its two neighbours, 2^31 and 2^32 - 1: each side of every
+    class border, both clamps, a weight __clz sees as a negative int."""
+    k = constants()
+    top, n = k['QUEUE_TOP_LOG2'], k['QUEUE_CLASSES']
+    assert top - n >= 1 and top + 1 < 31
+    t = [0, 1, 1 << 31, 0xFFFFFFFF]
+    for e in range(top - n, top + 2):
+        t += [(1 << e) - 1, 1 << e, (1 << e) + 1]
+    return sorted(set(t))
+
+
+def _rows_of(a):
+    return None if a is None else np.asarray(a).tolist()
+
+
+def queue_ref(form, mask_lo, mask_hi, n_tiles, weights, layer_of, layer_rep, layer_sums, cand_of_row, sums, wrong=()):
+    """mask_lo, mask_hi (candidates, mask_words) uint32; weights (candidates, n_tiles) uint32 or None; layer_of (rows,), layer_rep
+    (layers,), layer_sums (layers, n_tiles, SUM_WORDS) uint64 with form 'layers'; cand_of_row (rows,) with 'for_layers'; sums (at least
+    rows, SUM_WORDS) uint64.  -> dict: items (per class, the sorted packed pairs), counts, sums (as given but for the rows' additions).
+    wrong: names of deliberate mistakes (WRONG_QUEUE), for tests/test_geometry_refs.py only."""
+    k = constants()
+    n_cls, n_words = k['QUEUE_CLASSES'], k['SUM_WORDS']
+    assert form in ('plain', 'layers', 'for_layers') and (layer_of is not None) == (form == 'layers') and (cand_of_row is not None) == (form == 'for_layers')
+    lo_rows, hi_rows, w_rows = _rows_of(mask_lo), _rows_of(mask_hi), _rows_of(weights)
+    layer_of, layer_rep, cand_of_row, lsums = _rows_of(layer_of), _rows_of(layer_rep), _rows_of(cand_of_row), _rows_of(layer_sums)
+    out = _rows_of(sums)
+    rows = len(cand_of_row) if form == 'for_layers' else len(hi_rows)
+    words = len(lo_rows[0])
+    assert 32 * (words - 1) < n_tiles <= 32 * words and rows <= 1 << 16 and n_tiles <= 1 << 16
+    past = [t for t in range(n_tiles, 32 * words)]
+    bit = lambda row, t: (row[t >> 5] >> (t & 31)) & 1
+    shift = 1 if 'class one up' in wrong else -1 if 'class one down' in wrong else 0
+    items = [[] for _ in range(n_cls)]
+    for row in range(rows):
+        layer = None
+        if form == 'for_layers':
+            rep = cand_of_row[row]
+            lo, hi, weigh_at = lo_rows[rep], None, (row if 'weights at the row for rep' in wrong else rep)
+        elif form == 'layers':
+            layer = layer_of[row]
+            lo = lo_rows[row if 'lo of the row itself' in wrong else layer_rep[layer]]
+            hi, weigh_at = hi_rows[row], (layer_rep[layer] if 'weights at rep for the row' in wrong else row)
+        else:
+            lo, hi, weigh_at = lo_rows[row], hi_rows[row], row
+        assert not any(bit(lo, t) or (hi is not None and bit(hi, t)) for t in past), "mask bits at or past n_tiles: bounds_kernel sets none"
+        acc = [0] * n_words
+        for t in range(n_tiles):
+            l, h = bit(lo, t), (bit(hi, t) if hi is not None else 0)
+            if form == 'for_layers':
+                work = l
+            elif form == 'layers':
+                work = (h | l) if 'hi | lo queued with layers' in wrong else h
+            else:
+                work = h | l
+            if work:
+                cls = n_cls - 1 if w_rows is None else queue_class(w_rows[weigh_at][t], shift)
+                items[cls].append(row | (t << 16))
+            if form == 'layers' and l and not h:
+                src = lsums[row % len(lsums) if 'layer_sums by candidate' in wrong else layer][t]
+                for w in range(n_words):
+                    acc[w] += src[w]
+        for w in range(n_words):
+            if acc[w] & M64:
+                out[row][w] = acc[w] & M64 if 'store for add' in wrong else (out[row][w] + acc[w]) & M64
+    return dict(items=[sorted(v) for v in items], counts=[len(v) for v in items], sums=np.array(out, np.uint64).reshape(np.asarray(sums).shape))
+
+
+def same_queue(a, b):
+    return a['items'] == b['items'] and a['counts'] == b['counts'] and np.array_equal(a['sums'], b['sums'])
+
+
+QUEUE_ROWS, QUEUE_TILES = (1, 7, 8, 9, 257), (1, 4, 32, 33, 80, 256)       # either side of the eight rows a workgroup; 1, 2, 3 and 8 mask words
+QUEUE_SIZES = [(r, t) for r in QUEUE_ROWS for t in QUEUE_TILES] + [(65535, 4)]  # and the last row the 16 bits of an item can name
+QUEUE_SPARE_ROWS = 2                                     # rows of sums past the last: nothing writes them
+
+
+def _pack_bits(bits, words):
+    n = len(bits)
+    full = np.zeros((n, words * 32), np.uint64)
+    full[:, :bits.shape[1]] = bits
+    return (full.reshape(n, words, 32) << np.arange(32, dtype=np.uint64)).sum(-1).astype(np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def queue_case(form, rows, n_tiles, seed=0):
+    """Deterministic inputs of one launch_score_queue, inside the contract bounds_kernel and rope_abi.hip give the kernel: no mask bit
+    at or past n_tiles, no mask_lo bit on a candidate that is not its layer's representative, segment = rows x mask_words x 32 (0 and
+    one class without weights).  The i-th queued pair has the i-th weight of queue_weight_table() (from a drawn start, cyclically).
+    With layers, where the sizes allow: `span` is a candidate whose layer-only tiles lie in mask words 0 and 1, `wrapped` one whose
+    sums word SUM_S1 takes a layer word of 2^64 - 1 on top of a nonzero start, `zero_layer` a layer whose stored sums are all zero
+    (its representative has a layer-only tile), `covered` a candidate whose hi holds all of its layer's lo.
+    -> dict of the arguments (args: queue_ref's, in order), the reference's answer (want) and those names."""
+    k = constants()
+    n_words, n_cls = k['SUM_WORDS'], k['QUEUE_CLASSES']
+    base, weighted = form.replace('unweighted ', ''), not form.startswith('unweighted')
+    assert form in QUEUE_FORMS and base in ('plain', 'layers', 'for_layers')
+    words = (n_tiles + 31) // 32
+    rng = np.random.default_rng(QUEUE_FORMS.index(form) * 1000003 + rows * 1009 + n_tiles * 7 + seed)
+    n_cands = rows + 3 if base == 'for_layers' else rows
+    lo, hi = rng.random((n_cands, n_tiles)) < 0.5, rng.random((n_cands, n_tiles)) < 0.4
+    layer_of = layer_rep = layer_sums = cand_of_row = None
+    named = dict(span=None, wrapped=None, zero_layer=None, covered=None)
+    sums = rng.integers(0, 1 << 64, (rows + QUEUE_SPARE_ROWS, n_words), dtype=np.uint64) | np.uint64(1)
+    hi[rows - 1, n_tiles - 1] = True                     # the last row is queued, whatever was drawn
+    if base == 'for_layers':
+        perm = rng.permutation(n_cands)
+        if perm[0] == 0:
+            perm[[0, rows]] = perm[[rows, 0]]            # row 0 is not its own representative
+        cand_of_row = perm[:rows].astype(np.int32)
+        lo[cand_of_row[rows - 1], n_tiles - 1] = True
+        weigh_at, work = cand_of_row, lo[cand_of_row]
+    elif base == 'layers':
+        n_layers = max(1, min(rows // 2, 37))
+        perm = rng.permutation(rows)
+        layer_rep = perm[:n_layers].astype(np.int32)
+        layer_of = rng.integers(0, n_layers, rows).astype(np.int32)
+        layer_of[layer_rep] = np.arange(n_layers)
+        others = perm[n_layers:].tolist()
+        lo[others] = False                               # bounds_kernel skips the shared links of these
+        layer_sums = rng.integers(0, 1 << 64, (n_layers, n_tiles, n_words), dtype=np.uint64)
+        rep_of = lambda c: int(layer_rep[layer_of[c]])
+        if words >= 2 and len(others) >= 2:
+            c = named['span'] = others[1]
+            lo[rep_of(c), [0, 32]] = True
+            hi[c, [0, 32]] = False
+        c = named['wrapped'] = named['span'] if named['span'] is not None else (others[-1] if others else 0)
+        lo[rep_of(c), 0] = True
+        hi[c, 0] = False
+        layer_sums[layer_of[c], 0, SUM_S1] = M64
+        if n_layers >= 2:
+            z = named['zero_layer'] = (int(layer_of[c]) + 1) % n_layers
+            layer_sums[z] = 0
+            lo[layer_rep[z], n_tiles - 1] = True
+            hi[layer_rep[z], n_tiles - 1] = False
+        if others and named['wrapped'] != others[0]:
+            c = named['covered'] = others[0]
+            lo[rep_of(c), 0] = True
+            hi[c] |= lo[rep_of(c)]
+        weigh_at, work = np.arange(rows), hi
+    else:
+        weigh_at, work = np.arange(rows), hi | lo
+    weights = None
+    if weighted:
+        table = np.array(queue_weight_table(), np.uint32)
+        weights = table[rng.integers(0, len(table), (n_cands, n_tiles))]
+        at = np.argwhere(work)
+        weights[np.asarray(weigh_at)[at[:, 0]], at[:, 1]] = table[(np.arange(len(at)) + int(rng.integers(0, len(table)))) % len(table)]
+    mask_lo, mask_hi = _pack_bits(lo, words), _pack_bits(hi, words)
+    args = (base, mask_lo, mask_hi, n_tiles, weights, layer_of, layer_rep, layer_sums, cand_of_row, sums)
+    segment = rows * words * 32
+    return dict(form=form, base=base, rows=rows, n_tiles=n_tiles, words=words, n_cands=n_cands, args=args, mask_lo=mask_lo, mask_hi=mask_hi,
+                weights=weights, layer_of=layer_of, layer_rep=layer_rep, layer_sums=layer_sums, cand_of_row=cand_of_row, sums=sums,
+                segment=segment if weighted else 0, n_items=n_cls * segment if weighted else segment, want=queue_ref(*args), **named)
+
+
+# ------------------------------------------------------------------------------------------------ a kept grid's clearing
+CLEAR_SIZES = (0, 1, 11, 12, 256, 257)                   # rows x SUM_WORDS on either side of the 2 x QUEUE_COUNTERS counters (0 rows
+#                                                          alone lie below them) and of the 256 threads of one workgroup
+WRONG_CLEAR = ('one word short', 'one row more', 'one counter short', "one queue's counters only", 'counters although null')
+
+
+def clear_pass_ref(sums, C, counters, wrong=()):
+    """clear_pass_kernel: the first C x SUM_WORDS words of sums are zero, and the 2 x QUEUE_COUNTERS first ints of counters when there
+    are any -> (sums, counters or None), copies."""
+    k = constants()
+    sums = np.array(sums, np.uint64).reshape(-1)
+    n = C * k['SUM_WORDS'] + (-1 if 'one word short' in wrong and C else k['SUM_WORDS'] if 'one row more' in wrong else 0)
+    assert n <= len(sums)
+    sums[:n] = 0
+    if counters is None:
+        return sums, (np.zeros(2 * k['QUEUE_COUNTERS'], np.int32) if 'counters although null' in wrong else None)
+    counters = np.array(counters, np.int32).reshape(-1)
+    n = k['QUEUE_COUNTERS'] if "one queue's counters only" in wrong else 2 * k['QUEUE_COUNTERS'] - ('one counter short' in wrong)
+    counters[:n] = 0
+    return sums, counters

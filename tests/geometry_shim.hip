@@ -1,7 +1,7 @@
 // The first and the last kernels of every evaluation pass (rope_kernels.hip: fk_mvp / bounds / fk_bounds and finalize_only /
-// finalize_frames / finalize_argmin), each launched on its own on matrices, meshlet tables and sums the test supplies: the library
-// only ever runs them inside a whole pass, on the robot's meshlets at the poses a caller asks for, and entry points of their own in
-// rope_abi.hip would change rope_build_id.  Built by tests/test_gpu_geometry_kernels.py with build.HIPCC_FLAGS into a temporary
+// finalize_frames / finalize_argmin), the raster queue's builder (score_queue) and a kept grid's clearing (clear_pass), each launched
+// on its own on matrices, meshlet tables, masks and sums the test supplies: the library only ever runs them inside a whole pass, on
+// the robot's meshlets at the poses a caller asks for, and entry points of their own in rope_abi.hip would change rope_build_id.  Built by tests/test_gpu_geometry_kernels.py with build.HIPCC_FLAGS into a temporary
 // directory and LINKED against the built librope_hip.so (the helpers are plain members of namespace rope and the library is built
 // with default visibility), so the kernels that run are the shipped ones; never part of librope_hip.so.
 //
@@ -32,7 +32,7 @@ static rope::RobotParams robot_of(const uint32_t *ml_header, const float *ml_aab
 }
 
 // 0 TILE_W, 1 TILE_H, 2 MAX_MASK_WORDS, 3 QUEUE_WEIGHT_TILES, 4 QUEUE_COUNTERS, 5 COMPACT_PX, 6 ROPE_SUM_WORDS, 7 ROPE_MAX_LINKS,
-// 8 .. 11 ROPE_LOSS_DEPTH / FULL / LOOKUP / TSWEEP, 12 MAX_MESHLETS; anything else -1
+// 8 .. 11 ROPE_LOSS_DEPTH / FULL / LOOKUP / TSWEEP, 12 MAX_MESHLETS, 13 QUEUE_CLASSES, 14 QUEUE_TOP_LOG2; anything else -1
 extern "C" int shim_constant(int which)
 {
     switch (which) {
@@ -49,6 +49,8 @@ extern "C" int shim_constant(int which)
     case 10: return ROPE_LOSS_LOOKUP;
     case 11: return ROPE_LOSS_TSWEEP;
     case 12: return rope::MAX_MESHLETS;
+    case 13: return rope::QUEUE_CLASSES;
+    case 14: return rope::QUEUE_TOP_LOG2;
     }
     return -1;
 }
@@ -96,4 +98,23 @@ extern "C" int shim_finalize_frames(uint64_t *sums, const uint64_t *totals, cons
 {
     return (int)rope::launch_finalize_frames((hipStream_t)stream, sums, totals, frame_of_row, (const rope::LinkFlags *)flags, C, loss,
                                              n_render, n_pix, err);
+}
+
+// The queue builder alone (launch_score_queue: score_queue_kernel without the drain).  RasterArgs holds the masks, the layer maps,
+// the layers' stored sums, the row -> candidate map and the rows' sums; every other member is zero.  By reading rope_kernels.hip:
+// score_queue_kernel reads ra.cand_of_row, ra.layer_of, ra.layer_rep, ra.mask_lo, ra.mask_hi, ra.mask_words, ra.layer_sums and
+// ra.sums, and nothing else of ra.
+extern "C" int shim_score_queue(const uint32_t *mask_lo, const uint32_t *mask_hi, int mask_words, const int32_t *layer_of,
+                                const int32_t *layer_rep, uint64_t *layer_sums, const int32_t *cand_of_row, uint64_t *sums, int rows,
+                                int n_tiles, uint32_t *items, unsigned long long segment, int *counters, const uint32_t *weights, void *stream)
+{
+    rope::RasterArgs a = {};
+    a.mask_lo = mask_lo; a.mask_hi = mask_hi; a.mask_words = mask_words;
+    a.layer_of = layer_of; a.layer_rep = layer_rep; a.layer_sums = layer_sums; a.cand_of_row = cand_of_row; a.sums = sums;
+    return (int)rope::launch_score_queue((hipStream_t)stream, a, rows, n_tiles, items, (size_t)segment, counters, weights);
+}
+
+extern "C" int shim_clear_pass(uint64_t *sums, int C, int *queue_counters, void *stream)
+{
+    return (int)rope::launch_clear_pass((hipStream_t)stream, sums, C, queue_counters);
 }

@@ -1,6 +1,6 @@
 """tests/geometry_ref.py on the CPU: the exact float32 fma, every input builder reaches the edge it is named for, box_exact keeps the
-promises of box_bounds64 on every input, and the inputs tell box_exact / finalize_ref / argmin from deliberately wrong versions of
-themselves.  tests/test_gpu_geometry_kernels.py then holds the kernels to the same references on the same inputs."""
+promises of box_bounds64 on every input, and the inputs tell box_exact / finalize_ref / argmin / queue_ref / clear_pass_ref from
+deliberately wrong versions of themselves.  tests/test_gpu_geometry_kernels.py then holds the kernels to the same references on the same inputs."""
 import numpy as np
 import pytest
 
@@ -283,3 +283,128 @@ def test_inputs_tell_finalize_ref_and_argmin_from_wrong_ones():
         hit['last index wins a tie'] += R.argmin_last(f['err']) != f['best']
     assert all(v >= 3 for v in hit.values()), hit
     assert R.argmin([np.nan, 2.0, 1.0, 1.0, np.nan]) == 2 and R.argmin([np.nan, np.nan]) == 0 and R.argmin([np.inf, np.inf]) == 0 and R.argmin([0.0, -0.0]) == 0
+
+
+# ------------------------------------------------------------------------------------------------ the raster queue's builder
+def test_queue_weight_table_lies_on_every_class_border():
+    top, n = K['QUEUE_TOP_LOG2'], K['QUEUE_CLASSES']
+    table = R.queue_weight_table()
+    assert {0, 1, 1 << 31, 0xFFFFFFFF} <= set(table) and all(0 <= t < 1 << 32 for t in table)
+    for e in range(top - n, top + 2):
+        assert {(1 << e) - 1, 1 << e, (1 << e) + 1} <= set(table)
+        below, at, above = (R.queue_class(t) for t in ((1 << e) - 1, 1 << e, (1 << e) + 1))
+        assert at == above == min(max(top - e, 0), n - 1) and below == min(max(top - e + 1, 0), n - 1), e
+    assert {R.queue_class(t) for t in table} == set(range(n))
+    assert R.queue_class(0) == R.queue_class(1) == n - 1 and R.queue_class(1 << 31) == R.queue_class(0xFFFFFFFF) == 0
+    assert R.queue_class((1 << top) - 1) == 1 and R.queue_class(1 << top) == 0 and R.queue_class((1 << (top - n + 2)) - 1) == n - 1
+    assert R.queue_class(1 << (top - n + 2)) == n - 2                         # the last border that is not a clamp
+
+
+def _bits(mask_row, n_tiles):
+    return [(int(mask_row[t >> 5]) >> (t & 31)) & 1 for t in range(n_tiles)]
+
+
+@pytest.mark.parametrize('form', R.QUEUE_FORMS)
+def test_queue_cases_reach_their_edges(form):
+    n_cls, table = K['QUEUE_CLASSES'], R.queue_weight_table()
+    assert {r for r, _ in R.QUEUE_SIZES} == {1, 7, 8, 9, 257, 65535} and {(t + 31) // 32 for _, t in R.QUEUE_SIZES} == {1, 2, 3, 8}
+    assert {(r, t) for r, t in R.QUEUE_SIZES if r < 65535} == {(r, t) for r in (1, 7, 8, 9, 257) for t in (1, 4, 32, 33, 80, 256)} and (65535, 4) in R.QUEUE_SIZES
+    seen_classes = set()
+    for rows, n_tiles in R.QUEUE_SIZES:
+        c = R.queue_case(form, rows, n_tiles)
+        want, words = c['want'], c['words']
+        who = (form, rows, n_tiles)
+        # the contract: no mask bit at or past n_tiles, a segment holds every pair of the launch, a row fits an item's 16 bits
+        for m in (c['mask_lo'], c['mask_hi']):
+            assert m.shape == (c['n_cands'], words) and m.dtype == np.uint32
+            if n_tiles % 32:
+                assert not (m[:, -1] >> np.uint32(n_tiles % 32)).any(), who
+        assert words == (n_tiles + 31) // 32 and n_tiles <= K['QUEUE_WEIGHT_TILES'] and rows <= 65535
+        assert c['segment'] == (rows * words * 32 if c['weights'] is not None else 0) and c['n_items'] == max(c['segment'] * n_cls, rows * words * 32)
+        assert sum(want['counts']) <= rows * n_tiles and all(n <= max(c['segment'], rows * words * 32) for n in want['counts'])
+        if rows == 65535:                               # the last row an item's 16 bits are asked to name (rope_abi.hip: C <= 65535)
+            assert any(i & 0xFFFF == rows - 1 for v in want['items'] for i in v), (who, 'the last row is not queued')
+        assert all(i & 0xFFFF < rows and i >> 16 < n_tiles for v in want['items'] for i in v)
+        assert c['sums'].all() and c['sums'].shape == (rows + R.QUEUE_SPARE_ROWS, K['SUM_WORDS'])
+        assert np.array_equal(want['sums'][rows:], c['sums'][rows:])
+        if c['weights'] is None:
+            assert not any(want['counts'][:-1]) and (want['counts'][-1] > 0 or rows * n_tiles == 1), who
+        else:
+            at = (lambda i: c['cand_of_row'][i & 0xFFFF]) if c['base'] == 'for_layers' else (lambda i: i & 0xFFFF)
+            weight = lambda i: int(c['weights'][at(i), i >> 16])
+            assert all(R.queue_class(weight(i)) == cls for cls, v in enumerate(want['items']) for i in v)
+            seen_classes |= {cls for cls, n in enumerate(want['counts']) if n}
+            if sum(want['counts']) >= len(table):       # every weight of the table is queued: every class, both clamps, bit 31
+                assert {weight(i) for v in want['items'] for i in v} == set(table), who
+                assert all(want['counts']), who
+                assert {1 << 31, 0xFFFFFFFF} <= {weight(i) for i in want['items'][0]}, who
+                assert 0 in {weight(i) for i in want['items'][-1]}, who
+            assert (rows, n_tiles) != (65535, 4) or sum(want['counts']) >= len(table)
+        if c['base'] == 'for_layers':
+            assert c['cand_of_row'][0] != 0 and len(set(c['cand_of_row'].tolist())) == rows and c['n_cands'] > rows
+            assert np.array_equal(want['sums'], c['sums']), who
+            if rows >= 7:                               # rows and representatives weigh differently: the classes say which was read
+                assert any(R.queue_class(int(c['weights'][i & 0xFFFF, i >> 16])) != cls for cls, v in enumerate(want['items']) for i in v)
+        if c['base'] == 'plain':
+            assert np.array_equal(want['sums'], c['sums']), who
+        if c['base'] != 'layers':
+            continue
+        of, rep, ls = c['layer_of'], c['layer_rep'], c['layer_sums']
+        own = [i for i in range(rows) if rep[of[i]] == i]
+        assert own and len(own) == len(rep) and not np.delete(c['mask_lo'], own, axis=0).any(), who
+        only = lambda i: [l & ~h & 1 for l, h in zip(_bits(c['mask_lo'][rep[of[i]]], n_tiles), _bits(c['mask_hi'][i], n_tiles))]
+        w = c['wrapped']
+        tiles = [t for t, b in enumerate(only(w)) if b]
+        start, added = int(c['sums'][w, R.SUM_S1]), [int(ls[of[w], t, R.SUM_S1]) for t in tiles]
+        assert start > 0 and R.M64 in added and start + sum(added) >= 1 << 64, (who, 'no wrap')
+        assert int(want['sums'][w, R.SUM_S1]) == (start + sum(added)) % (1 << 64) != sum(added) % (1 << 64)         # an add, and no store
+        if rows >= 7:
+            z, cov = c['zero_layer'], c['covered']
+            assert z is not None and not ls[z].any() and any(only(int(rep[z]))) and np.array_equal(want['sums'][rep[z]], c['sums'][rep[z]]), who
+            assert cov is not None and not any(only(cov)) and c['mask_lo'][rep[of[cov]]].any() and np.array_equal(want['sums'][cov], c['sums'][cov]), who
+            assert any(rep[of[i]] != i and any(only(i)) for i in range(min(rows, 300))), who
+        if rows >= 7 and words >= 2:
+            s = c['span']
+            assert s is not None and only(s)[0] and only(s)[32], (who, 'no layer-only tile in a mask word past the first')
+            assert (want['sums'][s] != c['sums'][s]).any()
+    if form.startswith('unweighted'):
+        assert not seen_classes
+    else:
+        assert seen_classes == set(range(n_cls))
+
+
+@pytest.mark.parametrize('wrong', R.WRONG_QUEUE)
+def test_inputs_tell_queue_ref_from_a_wrong_one(wrong):
+    hits = []
+    for form in R.QUEUE_FORMS:
+        for rows, n_tiles in R.QUEUE_SIZES:
+            if rows > 300:
+                continue
+            c = R.queue_case(form, rows, n_tiles)
+            if not R.same_queue(R.queue_ref(*c['args'], wrong=(wrong,)), c['want']):
+                hits.append((form, rows, n_tiles))
+    assert len(hits) >= 2, (wrong, hits)
+    forms = {h[0] for h in hits}
+    if wrong.startswith('class one'):                   # without weights there is no class to get wrong
+        assert forms == {'plain', 'layers', 'for_layers'}, forms
+    if wrong in ('lo of the row itself', 'layer_sums by candidate', 'store for add', 'hi | lo queued with layers'):
+        assert forms == {'layers', 'unweighted layers'}, forms
+
+
+def test_clear_sizes_and_wrong_clears():
+    n_ctr, n_words = 2 * K['QUEUE_COUNTERS'], K['SUM_WORDS']
+    words = [C * n_words for C in R.CLEAR_SIZES]
+    assert {1, 11, 12, 256, 257} <= set(R.CLEAR_SIZES)
+    assert min(words) < n_ctr < max(words) and any(0 < w <= 256 for w in words) and any(256 < w <= 512 for w in words) and any(w > 512 for w in words)
+    assert 11 * n_words <= 256 < 12 * n_words or n_words != 23
+    hit = {w: 0 for w in R.WRONG_CLEAR}
+    for C in R.CLEAR_SIZES:
+        sums = np.full((C + 2) * n_words, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        for counters in (np.full(n_ctr + 4, 0x25A5A5A5, np.int32), None):
+            s, q = R.clear_pass_ref(sums, C, counters)
+            assert not s[:C * n_words].any() and (s[C * n_words:] == sums[0]).all() and (sums == sums[0]).all()
+            assert (q is None) if counters is None else (not q[:n_ctr].any() and (q[n_ctr:] == counters[0]).all())
+            for wrong in R.WRONG_CLEAR:
+                s2, q2 = R.clear_pass_ref(sums, C, counters, wrong=(wrong,))
+                hit[wrong] += not (np.array_equal(s, s2) and ((q is None and q2 is None) or (q is not None and q2 is not None and np.array_equal(q, q2))))
+    assert all(v >= 1 for v in hit.values()), hit

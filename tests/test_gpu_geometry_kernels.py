@@ -1,7 +1,8 @@
 """The first and the last kernels of every evaluation pass (rope_kernels.hip: fk_mvp, bounds, fk_bounds; finalize_only,
-finalize_frames, finalize_argmin), each launched on its own through tests/geometry_shim.hip on inputs the test supplies — bit for bit
-against tests/geometry_ref.py (box_exact, finalize_ref) and the oracle's link matrices, and by inequality only against the float64
-projection (box_bounds64, whose slack is derived there).  tests/test_geometry_refs.py shows on the CPU that the inputs reach the
+finalize_frames, finalize_argmin), the raster queue's builder (score_queue) and a kept grid's clearing (clear_pass), each launched on
+its own through tests/geometry_shim.hip on inputs the test supplies — bit for bit against tests/geometry_ref.py (box_exact,
+finalize_ref, queue_ref, clear_pass_ref) and the oracle's link matrices, and by inequality only against the float64 projection
+(box_bounds64, whose slack is derived there).  tests/test_geometry_refs.py shows on the CPU that the inputs reach the
 edges they are named for and that they tell the references from deliberately wrong ones.
 
 Every output buffer lies between guard bytes and starts out as 0xA5 bytes (table_child.Out)."""
@@ -41,6 +42,8 @@ def shim(tmp_path_factory):
     lib.shim_fk_bounds.argtypes = [i32] * 4 + [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.shim_finalize.argtypes = [vp, vp, i32, i32, i32, C.c_double, vp, vp, vp]
     lib.shim_finalize_frames.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_double, vp, vp]
+    lib.shim_score_queue.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, C.c_ulonglong, vp, vp, vp]
+    lib.shim_clear_pass.argtypes = [vp, i32, vp, vp]
     k = R.constants()
     for i, name in enumerate(R.SHIM_CONSTANTS):          # what the references read out of the headers is what the library was built with
         assert lib.shim_constant(i) == k[name], (name, lib.shim_constant(i), k[name])
@@ -309,3 +312,61 @@ def test_finalize_frames_rows_of_mixed_frames(shim, n_rows):
         msgs = [first_difference(R.bits(err.host()), R.bits(f['err']), f"loss {loss} n_render {n_render}: error bits of row"),
                 first_difference(sums.host().reshape(n_rows, -1), f['words'], f"loss {loss} n_render {n_render}: sums written back (row, word)")]
         assert not any(msgs), '\n'.join(m for m in msgs if m)
+
+
+# ------------------------------------------------------------------------------------------------ launch_score_queue
+@pytest.mark.parametrize('size', R.QUEUE_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize('form', R.QUEUE_FORMS, ids=lambda f: f.replace(' ', '-'))
+def test_score_queue_equals_the_reference(shim, form, size):
+    k = R.constants()
+    n_cls, n_ctr = k['QUEUE_CLASSES'], k['QUEUE_COUNTERS']
+    c = R.queue_case(form, *size)
+    rows, n_tiles, segment, want = c['rows'], c['n_tiles'], c['segment'], c['want']
+    assert c['words'] <= k['MAX_MASK_WORDS'] and n_tiles <= k['QUEUE_WEIGHT_TILES'] and rows <= 65535 and max(want['counts']) <= (segment or c['n_items'])
+    d = {key: (K.dev(c[key]) if c[key] is not None else None) for key in ('mask_lo', 'mask_hi', 'weights', 'layer_of', 'layer_rep', 'cand_of_row')}
+    layer_sums = filled('layer_sums', c['layer_sums'].size, np.uint64, c['layer_sums']) if c['layer_sums'] is not None else None
+    sums = filled('sums', c['sums'].size, np.uint64, c['sums'])
+    items = K.Out('items', c['n_items'], np.uint32)
+    counters = K.Out('counters', n_ctr + 4, np.int32)
+    counters.t[K.PAD:K.PAD + 4 * n_ctr] = 0
+    rc = shim.shim_score_queue(ptr(d['mask_lo']), ptr(d['mask_hi']), c['words'], ptr(d['layer_of']), ptr(d['layer_rep']),
+                               layer_sums.ptr if layer_sums else None, ptr(d['cand_of_row']), sums.ptr, rows, n_tiles, items.ptr, segment, counters.ptr,
+                               ptr(d['weights']), None)
+    assert rc == 0, rc
+    got_ctr, got_items, got_sums = counters.host(), items.host(), sums.host().reshape(c['sums'].shape)
+    guard = guard_words(1, np.uint32)[0]
+    assert got_ctr[2:n_ctr].tolist() == want['counts'], (got_ctr, want['counts'])
+    assert not got_ctr[:2].any() and (got_ctr[n_ctr:] == guard_words(1, np.int32)[0]).all(), got_ctr
+    written = np.zeros(len(got_items), bool)
+    for cls, (n, ref) in enumerate(zip(want['counts'], want['items'])):
+        seg = got_items[cls * segment:cls * segment + n]
+        written[cls * segment:cls * segment + n] = True
+        msg = first_difference(np.sort(seg), np.array(ref, np.uint32), f"class {cls} of {want['counts']}, sorted items (row | tile << 16)")
+        assert not msg, msg
+    stray = np.flatnonzero(~written & (got_items != guard))
+    assert not len(stray), f"item words written past the counts {want['counts']} (segment {segment}): {stray[:8]} hold {got_items[stray[:8]]}"
+    msg = first_difference(got_sums, want['sums'], 'sums (row, word)')
+    assert not msg, msg
+    assert np.array_equal(got_sums[rows:], c['sums'][rows:]) and (c['base'] == 'layers' or np.array_equal(got_sums, c['sums']))
+    if layer_sums:
+        assert np.array_equal(layer_sums.host(), c['layer_sums'].reshape(-1)), "the layers' stored sums were written"
+
+
+# ------------------------------------------------------------------------------------------------ launch_clear_pass
+@pytest.mark.parametrize('with_counters', [True, False])
+@pytest.mark.parametrize('n', R.CLEAR_SIZES)
+def test_clear_pass_clears_its_words_and_nothing_else(shim, n, with_counters):
+    k = R.constants()
+    n_words, n_ctr = k['SUM_WORDS'], 2 * k['QUEUE_COUNTERS']
+    sums, counters = K.Out('sums', (n + 2) * n_words, np.uint64), K.Out('queue_counters', n_ctr + 4, np.int32)
+    before = sums.host(), counters.host()
+    rc = shim.shim_clear_pass(sums.ptr, n, counters.ptr if with_counters else None, None)
+    assert rc == 0, rc
+    want_sums, want_ctr = R.clear_pass_ref(before[0], n, before[1] if with_counters else None)
+    got_sums, got_ctr = sums.host(), counters.host()
+    msg = first_difference(got_sums, want_sums, f"sums word (cleared: the first {n * n_words})")
+    assert not msg, msg
+    assert not got_sums[:n * n_words].any() and (got_sums[n * n_words:] == guard_words(1, np.uint64)[0]).all()
+    msg = first_difference(got_ctr, want_ctr if with_counters else before[1], 'queue counter')
+    assert not msg, msg
+    assert (got_ctr[n_ctr:] == guard_words(1, np.int32)[0]).all() and (not got_ctr[:n_ctr].any() if with_counters else (got_ctr == guard_words(1, np.int32)[0]).all())
