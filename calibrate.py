@@ -33,6 +33,10 @@ def calibrate(args):
     mask, extra = None, {}
     if args.silhouette > 0 and args.native:
         raise SystemExit("-native polishes on the depth term alone: it does not go with -silhouette")
+    if args.robust and (args.native or args.silhouette > 0 or args.joints == 'fixed'):
+        raise SystemExit("-robust weighs the depth term of the host loop: it goes with -joints frame or offset, not with -native or -silhouette")
+    if args.robust:
+        extra = dict(robust=args.robust, robust_scale='auto' if args.robust_scale is None else args.robust_scale)
     if args.silhouette > 0:
         # the robot masks: the frames' colour images reduced as the depth is, read by the colour code of the set (ColorSegmenter, what
         # Predictor(color_dict=...) sets reads its link masks with); masks made by a segmentation network are not taken here
@@ -72,9 +76,12 @@ def calibrate(args):
     if args.silhouette > 0:
         rep.update(silhouette=args.silhouette, radius=args.radius, cost_silhouette_before=float(res.cost_silhouette_before),
                    cost_silhouette_after=float(res.cost_silhouette_after), inliers_silhouette=float(res.inliers_silhouette))
+    if args.robust:
+        rep.update(robust=args.robust, robust_scale=float(res.robust_scale))
     names = ('x', 'y', 'z', 'a3', 'a4', 'a5')
     print(f"{args.dataset}: {n} frames at {w} x {h}, joints {args.joints}, {res.steps_taken} steps, {res.inliers:.0f} inlier pixels")
-    print(f"mean truncated cost {res.cost_before:.6e} -> {res.cost_after:.6e} m^2")
+    print(f"mean truncated cost {res.cost_before:.6e} -> {res.cost_after:.6e} m^2" if not args.robust else
+          f"mean {args.robust} cost at scale {res.robust_scale:.6f} m {res.cost_before:.6e} -> {res.cost_after:.6e} m^2")
     if args.silhouette > 0:
         print(f"mean truncated outline cost {res.cost_silhouette_before:.6e} -> {res.cost_silhouette_after:.6e} pixels^2 "
               f"(weight {args.silhouette:g}, radius {args.radius}, {res.inliers_silhouette:.0f} contour pixels)")
@@ -114,6 +121,10 @@ if __name__ == "__main__":
     parser.add_argument('-silhouette', type=float, default=0.0,
                         help="Weight of the outline term beside the depth term (0: off). Needs a colour-coded dataset (color_dict).")
     parser.add_argument('-radius', type=int, default=8, help="Pixels at which the outline distance is truncated, 1 .. 16.")
+    parser.add_argument('-robust', choices=('huber', 'tukey'), default=None,
+                        help="Weigh the depth residuals (Huber or Tukey) instead of counting them fully up to -clip. Host loop, depth term only.")
+    parser.add_argument('-robust_scale', type=float, default=None,
+                        help="Scale of the robust weights in metres, at most -clip (default: from the residuals at the start).")
     parser.add_argument('-native', action='store_true',
                         help="Run the loop inside the library (rope_refine_bundle): the solves on the device. Depth term only.")
     parser.add_argument('-json', type=str, default=None, help="File for the report.")

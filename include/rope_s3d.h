@@ -791,6 +791,55 @@ int rope_bundle_normal_equations(const float *render_depth_dev, const uint8_t *r
                                  const double *twists_dev, int n_cols, float clip_m, double *out_dev, double *work_dev, void *stream);
 size_t rope_bundle_normal_workspace(int n_frames, int H, int W);
 
+/* ---- Robust weights for the depth term of the bundle polish (csrc/rope_robust.hip; prediction/refinement.py,
+ * BundleRefiner(robust=...); tests/robust_ref.py restates the text below in numpy).  rope_bundle_normal_equations counts a residual
+ * fully up to clip_m and not at all beyond it; here the residuals are weighted by a Huber or Tukey rule at a scale below the
+ * truncation, and the scale comes from a histogram of the residuals.  Same conventions: no context, plain device pointers, the HIP
+ * stream to launch on, nothing synchronised or allocated in the call, no floating-point atomics.
+ *
+ * rope_residual_histogram: per frame, the counts of |r| over the BOTH pixels of rope_pose_normal_equations' step 3.
+ *   render_depth_dev, render_ids_dev, frame_depth_dev, n_frames, H, W, n_links, clip_m   as rope_bundle_normal_equations takes them
+ *   hist_dev             n_frames x ROPE_RESID_WORDS uint32 out, DEVICE, 4-byte aligned; written completely (the call zeroes it)
+ * With r = (double)R - (double)T and inv = 256.0 / (double)clip_m, one float64 division:
+ *   [b], b < 256   the BOTH pixels with |r| <= clip in bin b = min(255, (int)(fabs(r) * inv)): 256 bins of clip / 256 metres
+ *   [256]          the BOTH pixels that are not |r| <= clip (a NaN residual counts here)
+ *   [257]          the pixels that are not BOTH.  A frame's words add up to H W.
+ * Every addition is an integer addition (a workgroup counts in LDS, then adds its non-empty bins to the frame's words), so the words
+ * depend neither on the order of anything nor on how the frames are cut into calls.
+ * ROPE_E_ARG, with nothing enqueued and hist_dev untouched, for the shapes, n_links, clip_m and plane pointers
+ * rope_pose_normal_equations refuses, and for a null or misaligned hist_dev.  ROPE_E_HIP when the runtime refuses the fill or the launch.
+ *
+ * rope_bundle_normal_equations_robust: rope_bundle_normal_equations with a weight per inlier.  Every argument it shares with that call
+ * means the same, the words have the same layout and slots, work_dev has rope_bundle_normal_workspace_robust(n_frames, H, W) bytes
+ * (the same number), and the text on the arithmetic rule, steps 1 .. 5', determinism and the refusals holds; what differs:
+ *   kind                 ROPE_ROBUST_HUBER or ROPE_ROBUST_TUKEY
+ *   scale_m              finite, 0 < scale_m <= clip_m (compared as float32): the scale k of the weights, metres
+ * With k = (double)scale_m, r2 = r r and u = r2 / (k k), for a BOTH pixel:
+ *                        HUBER                                          TUKEY
+ *   within (rule 4')     fabs(r) <= clip                                fabs(r) <= k
+ *   weight w             1.0 if fabs(r) <= k, else k / fabs(r)          (1.0 - u) (1.0 - u)
+ *   cost share           r2 if fabs(r) <= k;                            ((k k) / 3.0) (1.0 - ((1.0 - u) (1.0 - u)) (1.0 - u)) within;
+ *                        (2.0 k) fabs(r) - k k up to clip;              (k k) / 3.0 beyond, or for a NaN
+ *                        (2.0 k) clip - k k beyond, or for a NaN
+ * INLIER: both, within, a normal, the test on nP.  An inlier's row v = (J_0 .. J_11, r) of rope_bundle_normal_equations becomes
+ * v' = s v with s = sqrt(w), one multiplication an entry, and the sums are taken over v' as that call takes them over v:
+ * Per frame:  [0] BOTH pixels   [1] the sum of the cost shares   [2] inliers   [3] sum of w r r   [4 + c] sum of w J_c r
+ *   [16 .. 93] sum of w J_a J_b   [94], [95] 0 — each product (s x)(s y), and added in rope_bundle_normal_equations' order.
+ * HUBER with scale_m == clip_m gives the BYTES of rope_bundle_normal_equations on any planes: every w is 1.0, sqrt(1.0) is 1.0, and
+ * (2 k) clip - k k is clip clip exactly.  The costs of two calls compare only at the same kind and scale.
+ * ROPE_E_ARG, with nothing enqueued and out_dev untouched, for every case of rope_bundle_normal_equations, a kind that is neither, and
+ * a scale_m that is not finite, not positive or above clip_m. */
+#define ROPE_RESID_WORDS 258
+#define ROPE_ROBUST_HUBER 1
+#define ROPE_ROBUST_TUKEY 2
+int rope_residual_histogram(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames, int H,
+                            int W, int n_links, float clip_m, uint32_t *hist_dev, void *stream);
+int rope_bundle_normal_equations_robust(const float *render_depth_dev, const uint8_t *render_ids_dev, const float *frame_depth_dev, int n_frames,
+                                        int H, int W, int n_links, float fx, float fy, float cx, float cy, const double *joints_dev, int n_joints,
+                                        const double *twists_dev, int n_cols, float clip_m, int kind, float scale_m, double *out_dev,
+                                        double *work_dev, void *stream);
+size_t rope_bundle_normal_workspace_robust(int n_frames, int H, int W);
+
 /* ---- The silhouette term (csrc/rope_silhouette.hip; prediction/refinement.py, BundleRefiner(silhouette=...);
  * tests/silhouette_ref.py restates the text below in numpy).  Depth along a ray barely changes when the robot slides across the
  * image; its outline does, and needs no depth at all.  Same conventions as above: no context, plain device pointers, the HIP stream

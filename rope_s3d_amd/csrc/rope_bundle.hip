@@ -34,14 +34,7 @@ __device__ __forceinline__ bool bneq_pixel(const float *__restrict__ r0, const u
     double nP;
     if (!depth_surface(r0, i0, p, x, y, H, W, id, z, cam, P, n, nP)) return false;      // no normal, or grazing
 
-#pragma unroll
-    for (int j = 0; j < NEQ_JOINTS; j++) {
-        v[j] = 0.0;
-        if (j < n_joints && j < id) v[j] = depth_column(z, n, nP, joint_velocity(jf, j, P));       // joint j moves the links behind it; the base none
-        v[NEQ_JOINTS + j] = 0.0;
-        if (j < n_cols) v[NEQ_JOINTS + j] = depth_column(z, n, nP, twist_velocity(tf, j, P));      // every column moves every drawn link
-    }
-    v[BNEQ_SLOTS] = r;
+    bneq_depth_columns(jf, n_joints, tf, n_cols, id, z, P, n, nP, r, v);                // rope_neq.h: rope_robust.hip fills the same entries
     head[2] += 1.0;
     return true;
 }

@@ -1,4 +1,4 @@
-// rope_neq.h — what the three normal-equation files (rope_refine.hip, rope_bundle.hip, rope_silhouette.hip) have in common, once:
+// rope_neq.h — what the normal-equation files (rope_refine.hip, rope_bundle.hip, rope_silhouette.hip, rope_robust.hip) have in common, once:
 // the camera and vector helpers, the depth surface of a pixel, the velocity of a surface point per unit of a column and the two ways
 // it becomes an entry of J, the workgroup shape and the chunk rule, the gather body, the pack-and-own-words body of the twelve-slot
 // kernels, and the host checks every entry point makes.  Everything is float64 with one IEEE operation per written operation
@@ -142,6 +142,21 @@ __device__ __forceinline__ double silhouette_column(double gx, double gy, const 
 {
     const double vx = (cam.fx * (u.x - kx * u.z)) / z, vy = (cam.fy * (u.y - ky * u.z)) / z;
     return gx * vx + gy * vy;
+}
+
+// The thirteen entries v = (J_0 .. J_11, r) of an inlier pixel of the DEPTH term over twelve slots (rope_bundle.hip and
+// rope_robust.hip): the pixel on link id at depth z with the surface (P, n, nP) and the residual r; jf, tf the frame's joints and twists.
+__device__ __forceinline__ void bneq_depth_columns(const double *__restrict__ jf, int n_joints, const double *__restrict__ tf, int n_cols, int id,
+                                                   double z, const Vec3 &P, const Vec3 &n, double nP, double r, double (&v)[BNEQ_VEC])
+{
+#pragma unroll
+    for (int j = 0; j < NEQ_JOINTS; j++) {
+        v[j] = 0.0;
+        if (j < n_joints && j < id) v[j] = depth_column(z, n, nP, joint_velocity(jf, j, P));       // joint j moves the links behind it; the base none
+        v[NEQ_JOINTS + j] = 0.0;
+        if (j < n_cols) v[NEQ_JOINTS + j] = depth_column(z, n, nP, twist_velocity(tf, j, P));      // every column moves every drawn link
+    }
+    v[BNEQ_SLOTS] = r;
 }
 
 // ---------------------------------------------------------------------------------------------- the gather

@@ -18,6 +18,8 @@ AGREE_WORDS = 28                 # ROPE_AGREE_WORDS (include/rope_s3d.h): the wo
 SHADE_MAX_NOISE_Q = 1023         # ROPE_SHADE_MAX_NOISE_Q
 NEQ_WORDS = 32                   # ROPE_NEQ_WORDS: the doubles rope_pose_normal_equations writes per frame
 BNEQ_WORDS = 96                  # ROPE_BNEQ_WORDS: the doubles rope_bundle_normal_equations writes per frame
+RESID_WORDS = 258                # ROPE_RESID_WORDS: the uint32 rope_residual_histogram writes per frame: 256 bins, beyond the clip, not both
+ROBUST_KINDS = {'huber': 1, 'tukey': 2}     # ROPE_ROBUST_HUBER, ROPE_ROBUST_TUKEY
 SIL_MAX_RADIUS = 16              # ROPE_SIL_MAX_RADIUS: the largest truncation of rope_mask_distance's field, pixels
 # rope_shade_params (include/rope_s3d.h), 64 bytes a record
 SHADE_DTYPE = np.dtype([('light', '<f4', 3), ('ambient', '<f4'), ('gain', '<f4', 3), ('bg_depth', '<f4'), ('noise_q', '<i4'), ('bg_index', '<i4'),
@@ -39,6 +41,7 @@ ABI_SYMBOLS = (
     'rope_depth_decimated_shape', 'rope_depth_decimate', 'rope_depth_spatial', 'rope_depth_temporal', 'rope_depth_align',
     'rope_shade_frames', 'rope_pose_normal_equations', 'rope_pose_normal_workspace', 'rope_camera_normal_equations',
     'rope_bundle_normal_equations', 'rope_bundle_normal_workspace',
+    'rope_residual_histogram', 'rope_bundle_normal_equations_robust', 'rope_bundle_normal_workspace_robust',
     'rope_mask_distance', 'rope_silhouette_normal_equations', 'rope_silhouette_normal_workspace',
     'rope_joint_axes', 'rope_levenberg_step', 'rope_formal_variance', 'rope_refine_poses', 'rope_refine_workspace',
     'rope_camera_twists', 'rope_bundle_pool', 'rope_bundle_schur_workspace', 'rope_bundle_schur_step', 'rope_bundle_schur_variance',
@@ -176,6 +179,11 @@ def load_library(path: str = None):
                                                  C.c_float, vp, vp, vp]
     lib.rope_bundle_normal_workspace.argtypes = [i32, i32, i32]
     lib.rope_bundle_normal_workspace.restype = C.c_size_t
+    lib.rope_residual_histogram.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp]
+    lib.rope_bundle_normal_equations_robust.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, i32, vp,
+                                                        i32, C.c_float, i32, C.c_float, vp, vp, vp]
+    lib.rope_bundle_normal_workspace_robust.argtypes = [i32, i32, i32]
+    lib.rope_bundle_normal_workspace_robust.restype = C.c_size_t
     lib.rope_mask_distance.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.rope_silhouette_normal_equations.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, i32, vp, i32,
                                                      i32, vp, vp, vp]
@@ -699,6 +707,42 @@ class Engine:
                                       ('frame_depth', frame_depth, 'float32'), self._two_blocks(joint_axes, twists), n_links, float(clip),
                                       f"clip {clip} (finite, positive)", intr)
 
+    def bundle_normal_equations_robust(self, render_depth, render_ids, frame_depth, joint_axes, twists, n_links: int, clip: float, intr, kind: str,
+                                       scale: float) -> np.ndarray:
+        """rope_bundle_normal_equations_robust: bundle_normal_equations with a Huber or Tukey weight w per inlier at the scale `scale`
+        metres (finite, 0 < scale <= clip) -> (N, 96) float64 in the same layout and slots: [1] the sum of the robust cost, [3] the sum
+        of w r^2, [4 + c] of w J_c r, [16..93] of w J_a J_b; Tukey's inliers end at the scale, Huber's at clip (include/rope_s3d.h).
+        kind: 'huber' or 'tukey'.  Huber at scale == clip gives bundle_normal_equations' bytes.  Everything else — the planes, the
+        columns, intr, the stream, determinism, the empty batch — is bundle_normal_equations'."""
+        if kind not in ROBUST_KINDS:
+            raise ValueError(f"kind: 'huber' or 'tukey', got {kind!r}")
+        return self._normal_equations('rope_bundle_normal_equations_robust', self._lib.rope_bundle_normal_workspace_robust, BNEQ_WORDS, render_depth,
+                                      render_ids, ('frame_depth', frame_depth, 'float32'), self._two_blocks(joint_axes, twists), n_links,
+                                      (float(clip), ROBUST_KINDS[kind], float(scale)),
+                                      f"clip {clip} (finite, positive), scale {scale} (finite, positive, at most clip)", intr)
+
+    def residual_histogram(self, render_depth, render_ids, frame_depth, n_links: int, clip: float) -> np.ndarray:
+        """rope_residual_histogram: N renders against the N depth frames -> (N, 258) uint32, per frame [b < 256] the pixels both
+        rendered and measured with |r| <= clip in bin min(255, int(|r| 256 / clip)), [256] those beyond clip (a NaN too), [257] the
+        pixels that are not both; a frame's words add up to H W (include/rope_s3d.h).  The planes are bundle_normal_equations'.
+        Integer adds alone: the words depend neither on order nor on how a batch is cut.  Runs on torch's current stream and the
+        counts are waited for here."""
+        import torch
+        N, H, W = self._planes((('render_depth', render_depth, 'float32'), ('render_ids', render_ids, 'uint8'), ('frame_depth', frame_depth, 'float32')))
+        if N == 0:
+            return np.zeros((0, RESID_WORDS), np.uint32)
+        dev = render_depth.device
+        with torch.cuda.device(dev):
+            hist = torch.empty((N, RESID_WORDS), dtype=torch.int32, device=dev)
+            rc = self._lib.rope_residual_histogram(_dp(render_depth), _dp(render_ids), _dp(frame_depth), int(N), int(H), int(W), int(n_links),
+                                                   float(clip), _dp(hist), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if rc == -1:
+                raise ValueError(f"rope_residual_histogram refused its arguments: {N} frames of {H} x {W} (at most 2^24 pixels), "
+                                 f"n_links {n_links} (1 .. 6), clip {clip} (finite, positive)")
+            if rc:
+                raise EngineError(f"rope_residual_histogram failed ({rc})")
+            return hist.cpu().numpy().view(np.uint32)
+
     def mask_distance(self, mask_t, radius: int):
         """rope_mask_distance: N masks -> (N, H, W) int32 on the device, the truncated signed squared distance of every pixel to
         its mask's boundary: -m inside the mask, +m outside, m the least dx^2 + dy^2 to a pixel of the other state within radius
@@ -747,7 +791,8 @@ class Engine:
         """The checks, the buffers and the call behind the four normal-equation entries.  workspace: the entry's scratch query;
         width: the words a frame gets (32 or 96); third: (name, tensor, dtype) of the planes the renders are held against; blocks:
         one or two (name, columns, what they are), columns (N, n, 6) float64 or None — not all None; scalar: what the entry takes
-        after the columns (clip or radius), checked and converted by the caller, and scalar_text its part of the refusal."""
+        after the columns (clip or radius; a tuple where it takes several), checked and converted by the caller, and scalar_text its part of
+        the refusal."""
         import torch
         N, H, W = self._planes((('render_depth', render_depth, 'float32'), ('render_ids', render_ids, 'uint8'), third))
         dev = render_depth.device
@@ -769,7 +814,8 @@ class Engine:
             out = torch.empty((N, width), dtype=torch.float64, device=dev)
             work = torch.empty(max(1, workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
             rc = getattr(self._lib, entry)(_dp(render_depth), _dp(render_ids), _dp(third[1]), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
-                                           *(a for c, n in zip(cols, counts) for a in (None if c is None else _dp(c), n)), scalar, _dp(out), _dp(work),
+                                           *(a for c, n in zip(cols, counts) for a in (None if c is None else _dp(c), n)),
+                                           *(scalar if isinstance(scalar, tuple) else (scalar,)), _dp(out), _dp(work),
                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
             if rc == -1:
                 columns = f"{counts[0]} {blocks[0][0]} (1 .. 6)" if len(blocks) == 1 else \

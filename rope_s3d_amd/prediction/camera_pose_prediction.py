@@ -124,8 +124,8 @@ class _CameraStageMachine:
 
     def __init__(self, base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine=False):
         self.base_pose = np.array(base_pose, dtype=float)
-        if isinstance(refine, str) and refine not in ('bundle', 'bundle+silhouette', 'bundle+native'):
-            raise ValueError(f"refine: True, False, 'bundle', 'bundle+silhouette' or 'bundle+native', got {refine!r}")
+        if isinstance(refine, str) and refine not in ('bundle', 'bundle+silhouette', 'bundle+native', 'bundle+robust'):
+            raise ValueError(f"refine: True, False, 'bundle', 'bundle+silhouette', 'bundle+native' or 'bundle+robust', got {refine!r}")
         self.refine, self.last_refinement, self._refiner = refine if isinstance(refine, str) else bool(refine), None, None
         self._robot_masks = None
         self.ds_factor, self.preview = ds_factor, preview
@@ -331,7 +331,9 @@ class _CameraStageMachine:
         so an encoder error is not absorbed into the pose; the caller's recorded angles are not changed.
         refine='bundle+silhouette': the same with the outline term at weight 1 (BundleRefiner(silhouette=1)) against the robot masks
         of this run (`_robot_masks`: the run's own, one per frame).
-        refine='bundle+native': 'bundle' through rope_refine_bundle (BundleRefiner(native=True)): the solves on the device."""
+        refine='bundle+native': 'bundle' through rope_refine_bundle (BundleRefiner(native=True)): the solves on the device.
+        refine='bundle+robust': 'bundle' with Huber weights at the scale the start's residuals give (BundleRefiner(robust='huber',
+        robust_scale='auto')): what sits a centimetre or two off a link, inside the truncation, pulls less."""
         self.last_refinement = None
         if not self.refine:
             return pose
@@ -339,6 +341,8 @@ class _CameraStageMachine:
             from .refinement import BundleRefiner, CameraPoseRefiner
             if self.refine == 'bundle+silhouette':
                 self._refiner = BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame', silhouette=1.0)
+            elif self.refine == 'bundle+robust':
+                self._refiner = BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame', robust='huber')
             else:
                 self._refiner = (BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame',
                                                native=self.refine == 'bundle+native') if self.refine in ('bundle', 'bundle+native')
@@ -403,7 +407,8 @@ class ModellessCameraPredictor(_CameraStageMachine):
         """`refine`: True polishes the pose the stages end on with refinement.CameraPoseRefiner and keeps its CameraRefineResult (the
         pooled formal sigma of the six parameters, every frame's own cost) in `last_refinement`; 'bundle' polishes it together with
         every frame's S, L and U (refinement.BundleRefiner, 'frame' mode) and keeps the BundleRefineResult ('bundle+native': the same
-        through rope_refine_bundle, the solves on the device); 'bundle+silhouette' adds
+        through rope_refine_bundle, the solves on the device; 'bundle+robust': the same with Huber weights at a scale taken from the
+        start's residuals); 'bundle+silhouette' adds
         the outline term.  This predictor has no segmentation: its robot mask is where the down-sampled depth frame holds a
         measurement, which is the robot only for frames whose background carries no depth (synthetic sets, background removed)."""
         super().__init__(base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine)

@@ -415,6 +415,9 @@ class BundleRefineResult:
     cost_silhouette_before: float = float('nan')    # pooled mean truncated squared outline distance at the start, pixels^2
     cost_silhouette_after: float = float('nan')     # the same at the end
     inliers_silhouette: float = 0.0                 # contour pixels of all frames that carried the final system
+    # robust weights (BundleRefiner(robust=...)): the scale every round of the call was weighted at, metres; nan without them.  The
+    # costs above are then means of the robust cost at that scale, and compare only with costs at the same kind and scale
+    robust_scale: float = float('nan')
 
 
 def unpack_bundle(words: np.ndarray):
@@ -506,6 +509,35 @@ def schur_sigma(words: np.ndarray, active_j, active_c):
     return sq, sc
 
 
+RESID_BINS = 256                # ROPE_RESID_WORDS - 2: the bins of |r| <= clip in a frame's residual histogram
+ROBUST_TUNING = {'huber': 1.345, 'tukey': 4.685}       # the usual constants of 95 % efficiency on Gaussian residuals
+
+
+def robust_scale_from_histogram(hist, clip: float, kind: str) -> float:
+    """The scale of the robust weights, metres, from residual histograms (Engine.residual_histogram: (N, 258) or (258,)): the
+    frames' counts pooled, n the sum of bins 0 .. 255 (the residuals within clip), m = (b + 1) clip / 256 with b the first bin at
+    which the running count reaches ceil(n / 2) — the median of |r|, taken at its bin's upper edge — sigma = 1.4826 m (the median
+    absolute deviation of a Gaussian), and the scale 1.345 sigma for 'huber', 4.685 sigma for 'tukey'.  Clamped to [clip / 128,
+    clip]: above clip nothing is left to weigh, and the floor, two bin widths, is a DESIGN CONSTANT, not a measurement — below it
+    the histogram cannot tell one scale from another, and a perfect fit would drive the scale, and with it every weight, to nothing.
+    With no residual within clip (n == 0) the scale is clip.  Pure host arithmetic on integers and Python floats."""
+    if kind not in ROBUST_TUNING:
+        raise ValueError(f"kind: 'huber' or 'tukey', got {kind!r}")
+    clip = float(clip)
+    if not (np.isfinite(clip) and clip > 0):
+        raise ValueError(f"clip must be finite and positive, got {clip}")
+    h = np.asarray(hist)
+    if h.ndim not in (1, 2) or h.shape[-1] != RESID_BINS + 2:
+        raise ValueError(f"hist: (N, {RESID_BINS + 2}) or ({RESID_BINS + 2},) counts, got {h.shape}")
+    bins = h.reshape(-1, RESID_BINS + 2)[:, :RESID_BINS].astype(np.int64).sum(axis=0)
+    n = int(bins.sum())
+    if n == 0:
+        return clip
+    b = int(np.searchsorted(np.cumsum(bins), (n + 1) // 2))            # the first bin whose running count is >= ceil(n / 2)
+    m = (b + 1) * clip / RESID_BINS
+    return float(min(max(ROBUST_TUNING[kind] * (1.4826 * m), clip / 128.0), clip))
+
+
 def bundle_columns_step(pooled: np.ndarray, active, lam: float) -> np.ndarray:
     """levenberg_step's rule over the twelve slots of a pooled system -> (12,)."""
     return _step(*unpack_bundle(pooled), active, lam)
@@ -542,12 +574,36 @@ class BundleRefiner(_DrawsEveryLink):
                         Engine.refine_bundle call per batch (rope_refine_bundle, csrc/rope_bundle_polish.hip) — the same loop with the
                         joint axes, the pool, the Schur or twelve-column solves, accept / reject, damping and the variances on the
                         device.  Same fields, same meanings; the numbers differ by the rounding of another elimination order and of
-                        the device's sine in the joint axes.  Depth term only: with silhouette > 0 it raises ValueError"""
+                        the device's sine in the joint axes.  Depth term only: with silhouette > 0 it raises ValueError
+    robust              None (the default): a residual counts fully up to clip and not at all beyond it, exactly as before, not a
+                        launch more.  'huber' or 'tukey': every inlier is weighted (rope_bundle_normal_equations_robust,
+                        csrc/rope_robust.hip) — Huber's weight falls as scale / |r| beyond the scale and its inliers end at clip,
+                        Tukey's falls to zero AT the scale and its inliers end there — so that a cable, a payload or a fringe of
+                        flying pixels a centimetre or two in front of a link, inside clip, does not pull the solve with full weight.
+                        The step, the Schur complement, the sigmas and frame_cost are the code below on the weighted words; cost_before,
+                        cost_after and frame_cost are means of the robust cost.  Not with native=True and not with silhouette > 0
+                        (ValueError): the native loop and the normalisation of a mixed robust cost are not built
+    robust_scale        'auto' (the default): the scale is robust_scale_from_histogram of the residuals at the START pose
+                        (rope_residual_histogram), once per refine call; or the scale in metres, finite, 0 < scale <= clip.  It is
+                        never re-estimated between the rounds of a call: a step is kept when the cost falls, and two costs compare
+                        only under one weighting.  The result's robust_scale says what was used"""
 
     def __init__(self, renderer_or_engine, intrinsics, do_angles: str = 'SLU', do_params=(True,) * 6, joints: str = 'frame',
                  clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3, silhouette: float = 0.0, radius: int = 8,
-                 native: bool = False):
+                 native: bool = False, robust=None, robust_scale='auto'):
         _check_loop_args(clip, iterations, damping)
+        if robust is not None and robust not in ROBUST_TUNING:
+            raise ValueError(f"robust: None, 'huber' or 'tukey', got {robust!r}")
+        if robust is not None and native:
+            raise ValueError("robust weights run in the host loop alone: native must be False (rope_refine_bundle has no weights)")
+        if robust is not None and silhouette > 0:
+            raise ValueError("robust weights are for the depth term alone: silhouette must be 0")
+        if isinstance(robust_scale, str) or isinstance(robust_scale, bool):
+            if robust_scale != 'auto':
+                raise ValueError(f"robust_scale: 'auto' or metres, got {robust_scale!r}")
+        elif not (np.isfinite(robust_scale) and 0 < robust_scale <= clip):
+            raise ValueError(f"robust_scale: 'auto' or metres, finite and in (0, clip], got {robust_scale!r}")
+        self.robust, self.robust_scale = robust, robust_scale if isinstance(robust_scale, str) else float(robust_scale)
         if not (np.isfinite(silhouette) and silhouette >= 0):
             raise ValueError(f"silhouette: a finite weight, 0 or more, got {silhouette}")
         if native and silhouette > 0:
@@ -573,34 +629,47 @@ class BundleRefiner(_DrawsEveryLink):
         """PoseRefiner.joint_axes under the camera `pose` -> (N, 6, 6)."""
         return joint_axes_camera(self.fk, *_camera_axes(pose), angles)
 
-    def _equations(self, pose, angles: np.ndarray, depth_t, sd2_t):
+    def _equations(self, pose, angles: np.ndarray, depth_t, sd2_t, scale=None):
         """One render of the N frames' angles under the camera `pose`, the joint axes and the twists there, and one kernel call per
-        term that is given -> (depth words (N, 96) or None without depth_t, outline words (N, 96) or None without sd2_t)."""
+        term that is given -> (depth words (N, 96) or None without depth_t, outline words (N, 96) or None without sd2_t).  With
+        robust weights the depth words are the weighted ones at `scale` metres."""
         angles = np.ascontiguousarray(angles, np.float64)
         rd, ri = _render_under(self.engine, self.intrinsics, pose, angles, self.n_links)
         axes = self.joint_axes(pose, angles) if self.active_j else None
         twists = np.tile(camera_twists(pose)[None], (len(angles), 1, 1)) if self.active_c else None
         intr4 = _intr4(self.intrinsics)
-        w_d = None if depth_t is None else self.engine.bundle_normal_equations(rd, ri, depth_t, axes, twists, self.n_links, self.clip, intr4)
+        if depth_t is None:
+            w_d = None
+        elif self.robust is None:
+            w_d = self.engine.bundle_normal_equations(rd, ri, depth_t, axes, twists, self.n_links, self.clip, intr4)
+        else:
+            w_d = self.engine.bundle_normal_equations_robust(rd, ri, depth_t, axes, twists, self.n_links, self.clip, intr4, self.robust, scale)
         w_s = None if sd2_t is None else self.engine.silhouette_normal_equations(rd, ri, sd2_t, axes, twists, self.n_links, self.radius, intr4)
         return w_d, w_s
 
-    def equations(self, pose, angles: np.ndarray, depth_t) -> np.ndarray:
+    def equations(self, pose, angles: np.ndarray, depth_t, scale=None) -> np.ndarray:
         """One render of the N frames' angles under the camera `pose`, the joint axes and the twists there and one kernel call ->
-        (N, 96), per frame."""
-        return self._equations(pose, angles, depth_t, None)[0]
+        (N, 96), per frame.  scale: the scale of the robust weights, metres; read only by a refiner with robust weights."""
+        return self._equations(pose, angles, depth_t, None, scale)[0]
+
+    def residual_scale(self, pose, angles: np.ndarray, depth_t) -> float:
+        """The 'auto' scale of the robust weights at (pose, angles): one render, one rope_residual_histogram call,
+        robust_scale_from_histogram of the frames' pooled counts -> metres."""
+        angles = np.ascontiguousarray(angles, np.float64)
+        rd, ri = _render_under(self.engine, self.intrinsics, pose, angles, self.n_links)
+        return robust_scale_from_histogram(self.engine.residual_histogram(rd, ri, depth_t, self.n_links, self.clip), self.clip, self.robust)
 
     def equations_both(self, pose, angles: np.ndarray, depth_t, sd2_t):
         """equations' render, axes and twists, handed to both kernels -> (depth words (N, 96) or None without depth_t, outline
         words (N, 96))."""
         return self._equations(pose, angles, depth_t, sd2_t)
 
-    def _result(self, pose, q, off, sigma_pose, sigma_joints, *fields) -> BundleRefineResult:
+    def _result(self, pose, q, off, sigma_pose, sigma_joints, *fields, **named) -> BundleRefineResult:
         """The result in the refiner's mode: sigma_joints is sigma_angles (N, 6) in 'frame' mode and sigma_offsets (6,) in 'offset'
-        mode; fields are cost_before and what follows it."""
+        mode; fields are cost_before and what follows it, named the fields given by name (robust_scale)."""
         if self.mode == 'frame':
-            return BundleRefineResult(pose, q, np.full(6, np.nan), sigma_pose, sigma_joints, None, *fields)
-        return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), sigma_pose, None, sigma_joints, *fields)
+            return BundleRefineResult(pose, q, np.full(6, np.nan), sigma_pose, sigma_joints, None, *fields, **named)
+        return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), sigma_pose, None, sigma_joints, *fields, **named)
 
     def _stage_masks(self, mask, depth, N):
         """refine's masks and, where given, depth of the same shape -> (depth_t or None, mask_distance's field of the masks)."""
@@ -640,13 +709,17 @@ class BundleRefiner(_DrawsEveryLink):
         depth_t, sd2_t = self._stage_masks(mask, depth, N) if outline else (_stage_depth(self.engine, depth, N), None)
         if self.native:
             return self._refine_native(pose, q0, depth_t)
+        # the scale of the robust weights: fixed here, at the start pose, for every round of this call
+        scale = None if self.robust is None else self.residual_scale(pose, q0, depth_t) if self.robust_scale == 'auto' else self.robust_scale
+        if scale is not None:
+            scale = float(np.float32(scale))                                            # what the kernel is handed, and what the result reports
         far = np.sqrt(self.radius * self.radius + 1.0) - 0.5                            # R'
         norm_d, norm_s = self.clip * self.clip, far * far
 
         def evaluate(state):
             """-> ((the terms' words, their pools, their mean costs), the cost a step is judged by): depth alone its mean cost,
             with the outline c_d / clip^2 + silhouette c_s / R'^2"""
-            w_d, w_s = self._equations(state[0], state[2], depth_t, sd2_t)
+            w_d, w_s = self._equations(state[0], state[2], depth_t, sd2_t, scale)
             p_d, p_s = (None if w is None else pool_bundle(w) for w in (w_d, w_s))
             c_d, c_s = (nan if p is None else float(p[1] / p[0]) if p[0] > 0 else np.inf for p in (p_d, p_s))
             if not outline:
@@ -697,7 +770,7 @@ class BundleRefiner(_DrawsEveryLink):
         sj, sp = schur_sigma(words, self.active_j, self.active_c) if frame_mode else np.split(bundle_columns_sigma(pooled, slots), 2)
         return self._result(pose, q, off, sp, sj, first[2], c_d, steps, 0.0 if p_d is None else float(p_d[2]),
                             np.full(N, np.nan) if w_d is None else mean_cost(w_d[:, :NEQ_WORDS]),
-                            *((first[5], c_s, float(p_s[2])) if outline else ()))
+                            *((first[5], c_s, float(p_s[2])) if outline else ()), **({} if scale is None else {'robust_scale': float(scale)}))
 
     def _refine_native(self, pose: np.ndarray, q0: np.ndarray, depth_t) -> BundleRefineResult:
         """refine through rope_refine_bundle: ONE call, because one system spans all frames — a batch whose scratch one call does
