@@ -35,6 +35,8 @@ def calibrate(args):
         raise SystemExit("-native polishes on the depth term alone: it does not go with -silhouette")
     if args.robust and (args.native or args.silhouette > 0 or args.joints == 'fixed'):
         raise SystemExit("-robust weighs the depth term of the host loop: it goes with -joints frame or offset, not with -native or -silhouette")
+    if args.both_ways and not args.silhouette > 0:
+        raise SystemExit("-both_ways is the second direction of the outline term: it goes with -silhouette")
     if args.robust:
         extra = dict(robust=args.robust, robust_scale='auto' if args.robust_scale is None else args.robust_scale)
     if args.silhouette > 0:
@@ -52,7 +54,7 @@ def calibrate(args):
         for i, c in enumerate(colour):
             m = seg(resize_linear(c, w, h) if f > 1 else c)['masks']
             mask[i] = m.any(axis=2)
-        extra = dict(silhouette=args.silhouette, radius=args.radius)
+        extra = dict(silhouette=args.silhouette, radius=args.radius, both_ways=bool(args.both_ways))
     renderer = Renderer('seg', pose0, str(ds.attrs['color_intrinsics']), intrinsic_ds_factor=f if f > 1 else None)
     try:
         if args.joints == 'fixed' and args.native:
@@ -75,7 +77,8 @@ def calibrate(args):
                steps_taken=int(res.steps_taken), inliers=float(res.inliers), frame_cost=res.frame_cost.tolist(), worst_frames=worst.tolist())
     if args.silhouette > 0:
         rep.update(silhouette=args.silhouette, radius=args.radius, cost_silhouette_before=float(res.cost_silhouette_before),
-                   cost_silhouette_after=float(res.cost_silhouette_after), inliers_silhouette=float(res.inliers_silhouette))
+                   cost_silhouette_after=float(res.cost_silhouette_after), inliers_silhouette=float(res.inliers_silhouette),
+                   both_ways=bool(args.both_ways), inliers_silhouette_reverse=float(res.inliers_silhouette_reverse))
     if args.robust:
         rep.update(robust=args.robust, robust_scale=float(res.robust_scale))
     names = ('x', 'y', 'z', 'a3', 'a4', 'a5')
@@ -84,7 +87,8 @@ def calibrate(args):
           f"mean {args.robust} cost at scale {res.robust_scale:.6f} m {res.cost_before:.6e} -> {res.cost_after:.6e} m^2")
     if args.silhouette > 0:
         print(f"mean truncated outline cost {res.cost_silhouette_before:.6e} -> {res.cost_silhouette_after:.6e} pixels^2 "
-              f"(weight {args.silhouette:g}, radius {args.radius}, {res.inliers_silhouette:.0f} contour pixels)")
+              f"(weight {args.silhouette:g}, radius {args.radius}, {res.inliers_silhouette:.0f} contour pixels" +
+              (f" of the renders and {res.inliers_silhouette_reverse:.0f} of the masks, both ways)" if args.both_ways else ")"))
     for k in range(6):
         print(f"  {names[k]:>2} {pose0[k]:+.6f} -> {res.pose[k]:+.6f}  (change {res.pose[k] - pose0[k]:+.2e}, formal sigma {sigma_pose[k]:.2e})")
     if args.joints == 'offset':
@@ -121,6 +125,8 @@ if __name__ == "__main__":
     parser.add_argument('-silhouette', type=float, default=0.0,
                         help="Weight of the outline term beside the depth term (0: off). Needs a colour-coded dataset (color_dict).")
     parser.add_argument('-radius', type=int, default=8, help="Pixels at which the outline distance is truncated, 1 .. 16.")
+    parser.add_argument('-both_ways', action='store_true',
+                        help="With -silhouette: measure the masks' outlines against the render as well as the render's against the masks.")
     parser.add_argument('-robust', choices=('huber', 'tukey'), default=None,
                         help="Weigh the depth residuals (Huber or Tukey) instead of counting them fully up to -clip. Host loop, depth term only.")
     parser.add_argument('-robust_scale', type=float, default=None,

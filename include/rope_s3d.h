@@ -896,6 +896,53 @@ int rope_silhouette_normal_equations(const float *render_depth_dev, const uint8_
                                      const double *twists_dev, int n_cols, int radius, double *out_dev, double *work_dev, void *stream);
 size_t rope_silhouette_normal_workspace(int n_frames, int H, int W);
 
+/* ---- The silhouette term's second direction, mask -> render (csrc/rope_silhouette_reverse.hip; prediction/refinement.py,
+ * BundleRefiner(silhouette=..., both_ways=True); tests/silhouette_reverse_ref.py restates the text below in numpy).  The term above
+ * walks the RENDER's contour against a field of the mask; a part of the mask that no outline of the render comes near pulls
+ * nothing there.  Here the MASK's contour is walked against a field of the render, which moves, so the field is made every round:
+ * one int16 a pixel.  Same conventions as above; the words of the two directions are in the same units and slots, and add.
+ *
+ * rope_render_nearest: for every pixel the nearest pixel of the other state of a render's coverage, in exact integers.
+ *   render_ids_dev       N planes H x W uint8, DEVICE: rope_render_batch_device's ids; rendered(p) = ids[p] < n_links
+ *   n_links              1 .. 255
+ *   radius               R, 1 .. ROPE_SIL_MAX_RADIUS
+ *   near_dev             N planes H x W int16 out, DEVICE, 2-byte aligned; written completely
+ * For a pixel p: over the pixels u INSIDE THE IMAGE with |dx| <= R, |dy| <= R (u = p + (dx, dy)) and rendered(u) != rendered(p), the
+ * one with the least dx dx + dy dy; among several at that distance the FIRST IN RASTER ORDER, the smallest y, then the smallest x.
+ * near[p] = (dy + 16) 33 + (dx + 16), 0 .. ROPE_SIL_NEAREST_MAX.  Without such a u, or with a least distance > R R: near[p] = -1
+ * (FAR).  The image edge is not a boundary.  What follows from it: sd(p) = -(dx dx + dy dy) when rendered(p), else +(dx dx + dy dy),
+ * and -(R R + 1) / +(R R + 1) for FAR — bit for bit what rope_mask_distance writes for the mask ids < n_links at the same radius.
+ * ROPE_E_ARG, with nothing enqueued, for every case of rope_mask_distance (near_dev in place of sd2_dev, misaligned: odd), and for
+ * n_links outside 1 .. 255.  N == 0 succeeds.  ROPE_E_HIP when the runtime refuses a launch.
+ *
+ * rope_silhouette_normal_equations_reverse: per frame, the normal equations of the distance between the MASK's outline and the
+ * render's boundary, in the layout and slots of rope_silhouette_normal_equations.
+ *   mask_dev             n_frames planes H x W uint8, DEVICE: non-zero = robot
+ *   near_dev             n_frames planes H x W int16 as rope_render_nearest writes them for render_ids_dev at this n_links and
+ *                        radius, DEVICE, 2-byte aligned.  A value it never writes there — out of range, or one whose anchor is
+ *                        outside the image or not rendered — is read as FAR
+ *   everything else      rope_silhouette_normal_equations'
+ * sd(q) as above from near[q] and ids[q]; phi(q) is step 1 above on sd(q).  Every operation float64, one IEEE operation each.
+ *   1'. CONTOUR: mask[p] != 0 and at least one of the 4-neighbours INSIDE THE IMAGE has mask == 0.  NEAR: |sd(p)| <= R R.  INLIER: both.
+ *   2'. e = phi(p) + 0.5: step 3 mirrored — a mask contour pixel's centre sits half a pixel inside the MASK's outline, so a mask that
+ *       is the render's coverage has e = 0 on every contour pixel.
+ *   3'. gx, gy: step 4 on this phi.
+ *   4'. The ANCHOR c, the rendered pixel whose surface point carries the boundary that p sees, with u = p + (dx, dy) of near[p]:
+ *       p not rendered: c = u.  p rendered: c = u moved ONE pixel towards p along x when |dx| >= |dy|, else along y.  c is inside the
+ *       image, rendered, and strictly nearer to p than u.
+ *   5'. z = R[c], kx = (c.x - cx) / fx, ky = (c.y - cy) / fy, P = (kx z, ky z, z), id = ids[c]; u_c of a column as in step 6 with
+ *       this id and P; vx, vy as in step 7 with kx, ky, z of c; J_c = -(gx vx + gy vy): it is the boundary that moves and not the
+ *       pixel, d phi(p) / d theta = -grad phi(p) . (the image velocity of c).  J_c = 0, exactly, for every other slot.
+ * Per frame: [0] contour pixels of the mask  [1] their sum of e e  [2] inliers  [3] their sum of e e  [4 + c] sum of J_c e
+ *   [16 .. 93] sum of J_a J_b  [94], [95] 0.  Determinism, the workspace (rope_silhouette_normal_workspace) and ROPE_E_ARG are
+ * rope_silhouette_normal_equations', with mask_dev and near_dev in place of sd2_dev (null; near_dev odd). */
+#define ROPE_SIL_NEAREST_MAX 1088
+int rope_render_nearest(const uint8_t *render_ids_dev, int N, int H, int W, int n_links, int radius, int16_t *near_dev, void *stream);
+int rope_silhouette_normal_equations_reverse(const uint8_t *mask_dev, const int16_t *near_dev, const float *render_depth_dev,
+                                             const uint8_t *render_ids_dev, int n_frames, int H, int W, int n_links, float fx, float fy,
+                                             float cx, float cy, const double *joints_dev, int n_joints, const double *twists_dev,
+                                             int n_cols, int radius, double *out_dev, double *work_dev, void *stream);
+
 /* ---- The polish, natively (csrc/rope_polish.hip; prediction/refinement.py, PoseRefiner(native=True); tests/polish_ref.py restates
  * the text below with plain loops over Python floats).  What rope_pose_normal_equations leaves to its caller — the joint axes of a
  * pose, the Levenberg step, the formal variances, and the loop around them — for a host that is not Python.

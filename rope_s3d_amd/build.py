@@ -11,7 +11,7 @@ _SOURCES = ['rope_kernels.hip', 'rope_fragments.hip', 'rope_table.hip', 'rope_ab
             'rope_hostprep.cpp', 'rope_seg.hip', 'rope_masks.hip',
             'rope_predict.cpp', 'rope_meshlets.cpp', 'rope_contours.cpp', 'rope_train.hip', 'rope_targets.hip', 'rope_synth.hip',
             'rope_eval.hip', 'rope_verify.hip', 'rope_feed.hip', 'rope_shade.hip', 'rope_refine.hip', 'rope_bundle.hip', 'rope_silhouette.hip',
-            'rope_polish.hip', 'rope_bundle_polish.hip', 'rope_robust.hip']
+            'rope_silhouette_reverse.hip', 'rope_polish.hip', 'rope_bundle_polish.hip', 'rope_robust.hip']
 _DEPS = _SOURCES + ['rope_kernels.h', 'rope_lossmath.h', 'rope_launch.h', 'rope_buffers.h', 'rope_ctx.h', 'rope_geomcache.h', 'rope_fragstore.h', 'rope_passplan.h', 'rope_fk.h', 'rope_neq.h', 'rope_solve.h', os.path.join('..', '..', 'include', 'rope_s3d.h')]
 
 # -ffp-contract=off: the arithmetic contract with the CPU oracle is "one IEEE operation per

@@ -1,4 +1,5 @@
-// rope_neq.h — what the normal-equation files (rope_refine.hip, rope_bundle.hip, rope_silhouette.hip, rope_robust.hip) have in common, once:
+// rope_neq.h — what the normal-equation files (rope_refine.hip, rope_bundle.hip, rope_silhouette.hip,
+// rope_silhouette_reverse.hip, rope_robust.hip) have in common, once:
 // the camera and vector helpers, the depth surface of a pixel, the velocity of a surface point per unit of a column and the two ways
 // it becomes an entry of J, the workgroup shape and the chunk rule, the gather body, the pack-and-own-words body of the twelve-slot
 // kernels, and the host checks every entry point makes.  Everything is float64 with one IEEE operation per written operation
@@ -157,6 +158,16 @@ __device__ __forceinline__ void bneq_depth_columns(const double *__restrict__ jf
         if (j < n_cols) v[NEQ_JOINTS + j] = depth_column(z, n, nP, twist_velocity(tf, j, P));      // every column moves every drawn link
     }
     v[BNEQ_SLOTS] = r;
+}
+
+// The outline terms' phi (rope_silhouette.hip, rope_silhouette_reverse.hip): the signed distance to the boundary in pixels, from a
+// distance field's integer (rope_mask_distance); beyond the truncation it is that of FAR, far2 = R R + 1
+__device__ __forceinline__ double sil_phi(int32_t sd, int far2)
+{
+    const long long a = sd < 0 ? -(long long)sd : (long long)sd;
+    const int m = a > far2 ? far2 : (int)a;
+    const double d = sqrt((double)m) - 0.5;
+    return sd < 0 ? -d : d;
 }
 
 // ---------------------------------------------------------------------------------------------- the gather

@@ -4,7 +4,8 @@
 //                                      over rope_bundle_normal_equations' twelve column slots and in its 96-word layout.
 // Everything floating is float64 with one IEEE operation per written operation (-ffp-contract=off); tests/silhouette_ref.py restates
 // both contracts in numpy.  The normal-equation half holds what is particular to the outline term, sneq_pixel; the vector helpers,
-// the columns' velocities and the body of the kernel are rope_bundle.hip's as well and live in rope_neq.h.
+// the columns' velocities and the body of the kernel are rope_bundle.hip's as well and live in rope_neq.h, and so does sil_phi, which
+// rope_silhouette_reverse.hip (the mask's outline against a field of the render) reads its field through as well.
 //
 // Distance.  A workgroup takes a tile of 32 x 32 pixels of one plane.  With R <= 16 the tile and its halo are 64 columns wide: a row
 // of it is ONE 64-bit word.  Each wave reads rows of 64 mask bytes, a lane a byte, and two ballots turn the row into the word of its
@@ -87,15 +88,6 @@ mask_distance_kernel(const uint8_t *__restrict__ mask, int n_planes, int H, int 
 }
 
 // ---------------------------------------------------------------------------------------------- the normal equations
-// phi of step 1: the signed distance to the boundary in pixels, from the field's integer; beyond the truncation it is that of FAR
-__device__ __forceinline__ double sil_phi(int32_t sd, int far2)
-{
-    const long long a = sd < 0 ? -(long long)sd : (long long)sd;
-    const int m = a > far2 ? far2 : (int)a;
-    const double d = sqrt((double)m) - 0.5;
-    return sd < 0 ? -d : d;
-}
-
 // Pixel p of a frame: adds its share of words 0 .. 2 to head and, for an inlier, fills v and returns true.
 __device__ __forceinline__ bool sneq_pixel(const float *__restrict__ r0, const uint8_t *__restrict__ i0, const int32_t *__restrict__ d0, int p, int H,
                                            int W, int n_links, const Camera &cam, const double *__restrict__ jf, int n_joints,

@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     'rope_bundle_normal_equations', 'rope_bundle_normal_workspace',
     'rope_residual_histogram', 'rope_bundle_normal_equations_robust', 'rope_bundle_normal_workspace_robust',
     'rope_mask_distance', 'rope_silhouette_normal_equations', 'rope_silhouette_normal_workspace',
+    'rope_render_nearest', 'rope_silhouette_normal_equations_reverse',
     'rope_joint_axes', 'rope_levenberg_step', 'rope_formal_variance', 'rope_refine_poses', 'rope_refine_workspace',
     'rope_camera_twists', 'rope_bundle_pool', 'rope_bundle_schur_workspace', 'rope_bundle_schur_step', 'rope_bundle_schur_variance',
     'rope_bundle_columns_step', 'rope_bundle_columns_variance', 'rope_refine_bundle', 'rope_refine_bundle_workspace')
@@ -189,6 +190,9 @@ def load_library(path: str = None):
                                                      i32, vp, vp, vp]
     lib.rope_silhouette_normal_workspace.argtypes = [i32, i32, i32]
     lib.rope_silhouette_normal_workspace.restype = C.c_size_t
+    lib.rope_render_nearest.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
+    lib.rope_silhouette_normal_equations_reverse.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, i32,
+                                                             vp, i32, i32, vp, vp, vp]
     lib.rope_joint_axes.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.rope_levenberg_step.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     lib.rope_formal_variance.argtypes = [vp, i32, i32, vp, vp]
@@ -776,6 +780,43 @@ class Engine:
                                       render_ids, ('sd2', sd2, 'int32'), self._two_blocks(joint_axes, twists), n_links, self._radius(radius),
                                       f"radius {radius}", intr)
 
+    def render_nearest(self, render_ids, n_links: int, radius: int):
+        """rope_render_nearest: N id planes of a render -> (N, H, W) int16 on the device, per pixel the nearest pixel of the other
+        state (rendered, id < n_links, or not) within radius pixels and inside the image as (dy + 16) 33 + (dx + 16), of several at
+        the least distance the first in raster order; -1 where there is none (include/rope_s3d.h).  It is mask_distance's field of
+        the render's coverage, sd = -+(dx^2 + dy^2), and where that distance is reached.  render_ids (N, H, W) uint8, a contiguous
+        torch tensor on this engine's device (render_batch_device's); n_links 1 .. 255; radius 1 .. 16.  The kernel runs on torch's
+        current stream and nothing is waited for."""
+        import torch
+        N, H, W = self._planes([('render_ids', render_ids, 'uint8')])
+        radius = self._radius(radius)
+        dev = render_ids.device
+        with torch.cuda.device(dev):
+            near = torch.empty((N, H, W), dtype=torch.int16, device=dev)
+            if N == 0:
+                return near
+            rc = self._lib.rope_render_nearest(_dp(render_ids), int(N), int(H), int(W), int(n_links), radius, _dp(near),
+                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc == -1:
+            raise ValueError(f"rope_render_nearest refused its arguments: {N} planes of {H} x {W} (fewer than 2^31 pixels), n_links {n_links} "
+                             f"(1 .. 255), radius {radius}")
+        if rc:
+            raise EngineError(f"rope_render_nearest failed ({rc})")
+        return near
+
+    def silhouette_normal_equations_reverse(self, mask, near, render_depth, render_ids, joint_axes, twists, n_links: int, radius: int,
+                                            intr) -> np.ndarray:
+        """rope_silhouette_normal_equations_reverse: the outline of the N frames' MASKS against the nearest-pixel fields of the N
+        renders -> (N, 96) float64 in silhouette_normal_equations' layout, slots and units, so that the two directions' words add:
+        [0] the contour pixels of the mask, [1] their sum of e^2, [2] those within radius of the render's boundary, [3] their sum
+        of e^2, [4 + c] J_c^T e, [16..93] the upper triangle of J^T J, [94], [95] 0; a column's J is taken at the rendered pixel
+        that carries the boundary the mask pixel sees (include/rope_s3d.h).  mask (N, H, W) uint8 or bool, non-zero = robot; near
+        (N, H, W) int16: render_nearest's of render_ids at the same n_links and radius.  Everything else — the renders, joint_axes,
+        twists, intr, the stream, determinism, the empty batch — is silhouette_normal_equations'."""
+        return self._normal_equations('rope_silhouette_normal_equations_reverse', self._lib.rope_silhouette_normal_workspace, BNEQ_WORDS,
+                                      render_depth, render_ids, None, self._two_blocks(joint_axes, twists), n_links, self._radius(radius),
+                                      f"radius {radius}", intr, lead=(('mask', mask, ('uint8', 'bool')), ('near', near, 'int16')))
+
     @staticmethod
     def _radius(radius) -> int:
         if int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
@@ -787,14 +828,16 @@ class Engine:
         return [('joint_axes', joint_axes, 'axis and a point on it per joint'), ('twists', twists, 'angular and linear part per column')]
 
     def _normal_equations(self, entry: str, workspace, width: int, render_depth, render_ids, third, blocks, n_links: int, scalar, scalar_text: str,
-                          intr) -> np.ndarray:
-        """The checks, the buffers and the call behind the four normal-equation entries.  workspace: the entry's scratch query;
-        width: the words a frame gets (32 or 96); third: (name, tensor, dtype) of the planes the renders are held against; blocks:
+                          intr, lead=()) -> np.ndarray:
+        """The checks, the buffers and the call behind the normal-equation entries.  workspace: the entry's scratch query;
+        width: the words a frame gets (32 or 96); third: (name, tensor, dtype) of the planes the renders are held against, handed
+        over after the renders — or None for an entry that takes its planes BEFORE the renders, lead: such (name, tensor, dtype); blocks:
         one or two (name, columns, what they are), columns (N, n, 6) float64 or None — not all None; scalar: what the entry takes
         after the columns (clip or radius; a tuple where it takes several), checked and converted by the caller, and scalar_text its part of
         the refusal."""
         import torch
-        N, H, W = self._planes((('render_depth', render_depth, 'float32'), ('render_ids', render_ids, 'uint8'), third))
+        third = () if third is None else (third,)
+        N, H, W = self._planes((('render_depth', render_depth, 'float32'), ('render_ids', render_ids, 'uint8'), *third, *lead))
         dev = render_depth.device
         if all(c is None for _, c, _ in blocks):
             raise ValueError(f"{' and '.join(name for name, _, _ in blocks)}: at least one of them" if len(blocks) > 1 else f"{blocks[0][0]}: not None")
@@ -813,7 +856,8 @@ class Engine:
             cols = [None if c is None or n == 0 else c.to(dev).contiguous() for c, n in zip(cols, counts)]
             out = torch.empty((N, width), dtype=torch.float64, device=dev)
             work = torch.empty(max(1, workspace(int(N), int(H), int(W)) // 8), dtype=torch.float64, device=dev)
-            rc = getattr(self._lib, entry)(_dp(render_depth), _dp(render_ids), _dp(third[1]), int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
+            rc = getattr(self._lib, entry)(*(_dp(t) for _, t, _ in lead), _dp(render_depth), _dp(render_ids), *(_dp(t) for _, t, _ in third),
+                                           int(N), int(H), int(W), int(n_links), fx, fy, cx, cy,
                                            *(a for c, n in zip(cols, counts) for a in (None if c is None else _dp(c), n)),
                                            *(scalar if isinstance(scalar, tuple) else (scalar,)), _dp(out), _dp(work),
                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))

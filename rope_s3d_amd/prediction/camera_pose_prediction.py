@@ -117,6 +117,10 @@ def segmented_stages() -> list:
 
 
 # ------------------------------------------------------------------------------ shared machine
+BUNDLE_REFINES = ('bundle', 'bundle+silhouette', 'bundle+native', 'bundle+robust', 'bundle+silhouette+both')    # refine= as a string
+OUTLINE_REFINES = ('bundle+silhouette', 'bundle+silhouette+both')       # the refine switches that take the run's robot masks
+
+
 class _CameraStageMachine:
     """Stage loop common to both predictors (the reference repeats it in each class)."""
 
@@ -124,8 +128,9 @@ class _CameraStageMachine:
 
     def __init__(self, base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine=False):
         self.base_pose = np.array(base_pose, dtype=float)
-        if isinstance(refine, str) and refine not in ('bundle', 'bundle+silhouette', 'bundle+native', 'bundle+robust'):
-            raise ValueError(f"refine: True, False, 'bundle', 'bundle+silhouette', 'bundle+native' or 'bundle+robust', got {refine!r}")
+        if isinstance(refine, str) and refine not in BUNDLE_REFINES:
+            names = [repr(n) for n in BUNDLE_REFINES]
+            raise ValueError(f"refine: True, False, {', '.join(names[:-1])} or {names[-1]}, got {refine!r}")
         self.refine, self.last_refinement, self._refiner = refine if isinstance(refine, str) else bool(refine), None, None
         self._robot_masks = None
         self.ds_factor, self.preview = ds_factor, preview
@@ -331,6 +336,8 @@ class _CameraStageMachine:
         so an encoder error is not absorbed into the pose; the caller's recorded angles are not changed.
         refine='bundle+silhouette': the same with the outline term at weight 1 (BundleRefiner(silhouette=1)) against the robot masks
         of this run (`_robot_masks`: the run's own, one per frame).
+        refine='bundle+silhouette+both': that with the outline measured both ways (BundleRefiner(silhouette=1, both_ways=True)): the
+        masks' outlines against the render as well.
         refine='bundle+native': 'bundle' through rope_refine_bundle (BundleRefiner(native=True)): the solves on the device.
         refine='bundle+robust': 'bundle' with Huber weights at the scale the start's residuals give (BundleRefiner(robust='huber',
         robust_scale='auto')): what sits a centimetre or two off a link, inside the truncation, pulls less."""
@@ -341,13 +348,16 @@ class _CameraStageMachine:
             from .refinement import BundleRefiner, CameraPoseRefiner
             if self.refine == 'bundle+silhouette':
                 self._refiner = BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame', silhouette=1.0)
+            elif self.refine == 'bundle+silhouette+both':
+                self._refiner = BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame', silhouette=1.0,
+                                              both_ways=True)
             elif self.refine == 'bundle+robust':
                 self._refiner = BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame', robust='huber')
             else:
                 self._refiner = (BundleRefiner(self.renderer, self.renderer.intrinsics, do_angles='SLU', joints='frame',
                                                native=self.refine == 'bundle+native') if self.refine in ('bundle', 'bundle+native')
                                  else CameraPoseRefiner(self.renderer, self.renderer.intrinsics))
-        if self.refine == 'bundle+silhouette':
+        if self.refine in OUTLINE_REFINES:
             self.last_refinement = self._refiner.refine(pose, self.robot_poses, np.asarray(self._tgt_depths, np.float32), self._robot_masks)
         else:
             self.last_refinement = self._refiner.refine(pose, self.robot_poses, np.asarray(self._tgt_depths, np.float32))
@@ -408,8 +418,8 @@ class ModellessCameraPredictor(_CameraStageMachine):
         pooled formal sigma of the six parameters, every frame's own cost) in `last_refinement`; 'bundle' polishes it together with
         every frame's S, L and U (refinement.BundleRefiner, 'frame' mode) and keeps the BundleRefineResult ('bundle+native': the same
         through rope_refine_bundle, the solves on the device; 'bundle+robust': the same with Huber weights at a scale taken from the
-        start's residuals); 'bundle+silhouette' adds
-        the outline term.  This predictor has no segmentation: its robot mask is where the down-sampled depth frame holds a
+        start's residuals); 'bundle+silhouette' adds the outline term, 'bundle+silhouette+both' that term measured both ways.
+        This predictor has no segmentation: its robot mask is where the down-sampled depth frame holds a
         measurement, which is the robot only for frames whose background carries no depth (synthetic sets, background removed)."""
         super().__init__(base_pose, ds_factor, preview, save_to, min_angle_inc, history_length, base_intrinsics, device, refine)
 
@@ -421,7 +431,7 @@ class ModellessCameraPredictor(_CameraStageMachine):
         self._preview_targets(og_images[0], target_depths[0])
         self._tgt_depths = self._batch_downsample(target_depths, self.ds_factor)
         self._n_pix = float(self._tgt_depths.shape[1] * self._tgt_depths.shape[2])
-        self._robot_masks = np.asarray(self._tgt_depths) > 0 if self.refine == 'bundle+silhouette' else None
+        self._robot_masks = np.asarray(self._tgt_depths) > 0 if self.refine in OUTLINE_REFINES else None
         self._frame_planes = (np.stack([pack_target(d) for d in self._tgt_depths]), self._tgt_depths.astype(np.float32))
         self.engine.set_frames(self.robot_poses, *self._frame_planes)
         if self.stages is None:
@@ -516,7 +526,7 @@ class CameraPredictor(_CameraStageMachine):
         if self.stages is None:
             self._setStages()
         self._load_targets(segmentation_data, target_depths)
-        if self.refine == 'bundle+silhouette':          # every frame's own links, merged: not the planes shared by all frames
+        if self.refine in OUTLINE_REFINES:              # every frame's own links, merged: not the planes shared by all frames
             self._robot_masks = np.stack([np.any([d[k]['mask'] for k in self.link_names if k in d] or [np.zeros(target_depths.shape[1:], bool)],
                                                  axis=0) for d in segmentation_data])
         return self._polish(self.run_stages(pose))

@@ -418,6 +418,9 @@ class BundleRefineResult:
     # robust weights (BundleRefiner(robust=...)): the scale every round of the call was weighted at, metres; nan without them.  The
     # costs above are then means of the robust cost at that scale, and compare only with costs at the same kind and scale
     robust_scale: float = float('nan')
+    # the outline's second direction (BundleRefiner(both_ways=True)): the MASK's contour pixels of all frames that carried the final
+    # system.  The outline costs above are then means over both directions' contour pixels; inliers_silhouette stays the render's
+    inliers_silhouette_reverse: float = 0.0
 
 
 def unpack_bundle(words: np.ndarray):
@@ -567,8 +570,8 @@ class BundleRefiner(_DrawsEveryLink):
                         and may go without depth frames altogether.  Both costs are normalised by their truncations, c_d = mean
                         cost / clip^2 and c_s = mean outline cost / R'^2 with R' = sqrt(radius^2 + 1) - 0.5; a step is kept if
                         c_d + silhouette c_s is strictly smaller, and the system solved is the sum of the two terms' words, each
-                        divided by its pixel count and truncation at the iterate held.  One-directional: the render's outline is
-                        measured against the mask
+                        divided by its pixel count and truncation at the iterate held.  One-directional unless both_ways: the
+                        render's outline is measured against the mask
     radius              1 .. 16 pixels: the truncation of the mask's distance field
     native              False (the default): the loop below, on the host, numpy's LAPACK for the solves.  True: refine is one
                         Engine.refine_bundle call per batch (rope_refine_bundle, csrc/rope_bundle_polish.hip) — the same loop with the
@@ -586,11 +589,17 @@ class BundleRefiner(_DrawsEveryLink):
     robust_scale        'auto' (the default): the scale is robust_scale_from_histogram of the residuals at the START pose
                         (rope_residual_histogram), once per refine call; or the scale in metres, finite, 0 < scale <= clip.  It is
                         never re-estimated between the rounds of a call: a step is kept when the cost falls, and two costs compare
-                        only under one weighting.  The result's robust_scale says what was used"""
+                        only under one weighting.  The result's robust_scale says what was used
+    both_ways           False (the default): the outline term as above, not a launch more.  True, with silhouette > 0 (ValueError
+                        without): the MASK's outline is measured against the render as well — every round one rope_render_nearest of
+                        the round's own render and one rope_silhouette_normal_equations_reverse (csrc/rope_silhouette_reverse.hip),
+                        whose words are ADDED to the forward ones, both in pixels^2 under the same truncation; c_s, the term's share
+                        of the system and its s^2 are then the rules above on the summed words.  A part of the mask that no outline of
+                        the render comes near then pulls: a link rotated out of its mask, a forearm hidden inside the mask's area"""
 
     def __init__(self, renderer_or_engine, intrinsics, do_angles: str = 'SLU', do_params=(True,) * 6, joints: str = 'frame',
                  clip: float = 2 ** -5, iterations: int = 5, damping: float = 1e-3, silhouette: float = 0.0, radius: int = 8,
-                 native: bool = False, robust=None, robust_scale='auto'):
+                 native: bool = False, robust=None, robust_scale='auto', both_ways: bool = False):
         _check_loop_args(clip, iterations, damping)
         if robust is not None and robust not in ROBUST_TUNING:
             raise ValueError(f"robust: None, 'huber' or 'tukey', got {robust!r}")
@@ -612,6 +621,9 @@ class BundleRefiner(_DrawsEveryLink):
         if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= SIL_MAX_RADIUS:
             raise ValueError(f"radius: a whole number of pixels in 1 .. {SIL_MAX_RADIUS}, got {radius}")
         self.silhouette, self.radius = float(silhouette), int(radius)
+        if both_ways and not silhouette > 0:
+            raise ValueError("both_ways is the outline term's second direction: silhouette must be > 0")
+        self.both_ways = bool(both_ways)
         if joints not in ('frame', 'offset'):
             raise ValueError(f"joints: 'frame' or 'offset', got {joints!r}")
         self.active_c = _active_params(do_params)
@@ -629,10 +641,11 @@ class BundleRefiner(_DrawsEveryLink):
         """PoseRefiner.joint_axes under the camera `pose` -> (N, 6, 6)."""
         return joint_axes_camera(self.fk, *_camera_axes(pose), angles)
 
-    def _equations(self, pose, angles: np.ndarray, depth_t, sd2_t, scale=None):
+    def _equations(self, pose, angles: np.ndarray, depth_t, sd2_t, scale=None, mask_t=None):
         """One render of the N frames' angles under the camera `pose`, the joint axes and the twists there, and one kernel call per
-        term that is given -> (depth words (N, 96) or None without depth_t, outline words (N, 96) or None without sd2_t).  With
-        robust weights the depth words are the weighted ones at `scale` metres."""
+        term that is given -> (depth words (N, 96) or None without depth_t, outline words (N, 96) or None without sd2_t, the
+        words of the outline's second direction or None without mask_t: the masks against render_nearest's field of THIS render).
+        With robust weights the depth words are the weighted ones at `scale` metres."""
         angles = np.ascontiguousarray(angles, np.float64)
         rd, ri = _render_under(self.engine, self.intrinsics, pose, angles, self.n_links)
         axes = self.joint_axes(pose, angles) if self.active_j else None
@@ -645,7 +658,11 @@ class BundleRefiner(_DrawsEveryLink):
         else:
             w_d = self.engine.bundle_normal_equations_robust(rd, ri, depth_t, axes, twists, self.n_links, self.clip, intr4, self.robust, scale)
         w_s = None if sd2_t is None else self.engine.silhouette_normal_equations(rd, ri, sd2_t, axes, twists, self.n_links, self.radius, intr4)
-        return w_d, w_s
+        w_r = None
+        if mask_t is not None:
+            near_t = self.engine.render_nearest(ri, self.n_links, self.radius)
+            w_r = self.engine.silhouette_normal_equations_reverse(mask_t, near_t, rd, ri, axes, twists, self.n_links, self.radius, intr4)
+        return w_d, w_s, w_r
 
     def equations(self, pose, angles: np.ndarray, depth_t, scale=None) -> np.ndarray:
         """One render of the N frames' angles under the camera `pose`, the joint axes and the twists there and one kernel call ->
@@ -662,7 +679,7 @@ class BundleRefiner(_DrawsEveryLink):
     def equations_both(self, pose, angles: np.ndarray, depth_t, sd2_t):
         """equations' render, axes and twists, handed to both kernels -> (depth words (N, 96) or None without depth_t, outline
         words (N, 96))."""
-        return self._equations(pose, angles, depth_t, sd2_t)
+        return self._equations(pose, angles, depth_t, sd2_t)[:2]
 
     def _result(self, pose, q, off, sigma_pose, sigma_joints, *fields, **named) -> BundleRefineResult:
         """The result in the refiner's mode: sigma_joints is sigma_angles (N, 6) in 'frame' mode and sigma_offsets (6,) in 'offset'
@@ -672,7 +689,8 @@ class BundleRefiner(_DrawsEveryLink):
         return BundleRefineResult(pose, q, np.where(np.isin(np.arange(6), self.active_j), off, 0.0), sigma_pose, None, sigma_joints, *fields, **named)
 
     def _stage_masks(self, mask, depth, N):
-        """refine's masks and, where given, depth of the same shape -> (depth_t or None, mask_distance's field of the masks)."""
+        """refine's masks and, where given, depth of the same shape -> (depth_t or None, mask_distance's field of the masks, the
+        masks as uint8 on the device)."""
         import torch
         if not isinstance(mask, torch.Tensor):
             mask = torch.from_numpy(np.ascontiguousarray(mask))
@@ -682,7 +700,7 @@ class BundleRefiner(_DrawsEveryLink):
         depth_t = None if depth is None else _stage_depth(self.engine, depth, N)
         if depth_t is not None and depth_t.shape != mask_t.shape:
             raise ValueError(f"depth: {tuple(mask_t.shape)} as the masks, got {tuple(depth_t.shape)}")
-        return depth_t, self.engine.mask_distance(mask_t, self.radius)                  # once: the masks do not move
+        return depth_t, self.engine.mask_distance(mask_t, self.radius), mask_t          # once: the masks do not move
 
     def refine(self, camera_pose, angles, depth, mask=None) -> BundleRefineResult:
         """camera_pose (6,); angles (N, 6); depth (N, H, W) metres at the refiner's resolution, a numpy array or a torch tensor on
@@ -706,7 +724,7 @@ class BundleRefiner(_DrawsEveryLink):
             c_d = np.inf if depth is not None or not outline else nan
             return self._result(pose, q0, np.zeros(6), sp, np.zeros((0, 6)) if frame_mode else so, c_d, c_d, 0, 0.0, np.zeros(0),
                                 *((np.inf, np.inf, 0.0) if outline else ()))
-        depth_t, sd2_t = self._stage_masks(mask, depth, N) if outline else (_stage_depth(self.engine, depth, N), None)
+        depth_t, sd2_t, mask_t = self._stage_masks(mask, depth, N) if outline else (_stage_depth(self.engine, depth, N), None, None)
         if self.native:
             return self._refine_native(pose, q0, depth_t)
         # the scale of the robust weights: fixed here, at the start pose, for every round of this call
@@ -717,16 +735,20 @@ class BundleRefiner(_DrawsEveryLink):
         norm_d, norm_s = self.clip * self.clip, far * far
 
         def evaluate(state):
-            """-> ((the terms' words, their pools, their mean costs), the cost a step is judged by): depth alone its mean cost,
-            with the outline c_d / clip^2 + silhouette c_s / R'^2"""
-            w_d, w_s = self._equations(state[0], state[2], depth_t, sd2_t, scale)
+            """-> ((the terms' words, their pools, their mean costs, the outline's inliers by direction), the cost a step is judged
+            by): depth alone its mean cost, with the outline c_d / clip^2 + silhouette c_s / R'^2"""
+            w_d, w_s, w_r = self._equations(state[0], state[2], depth_t, sd2_t, scale, mask_t if self.both_ways else None)
+            n_sr = None
+            if w_r is not None:                                         # both directions: ONE outline term, the sum of their words
+                n_sr = (float(pool_bundle(w_s)[2]), float(pool_bundle(w_r)[2]))
+                w_s = w_s + w_r
             p_d, p_s = (None if w is None else pool_bundle(w) for w in (w_d, w_s))
             c_d, c_s = (nan if p is None else float(p[1] / p[0]) if p[0] > 0 else np.inf for p in (p_d, p_s))
             if not outline:
                 cost = c_d
             else:
                 cost = float(self.silhouette * (c_s / norm_s)) if p_d is None else float(c_d / norm_d + self.silhouette * (c_s / norm_s))
-            return (w_d, p_d, c_d, w_s, p_s, c_s), cost
+            return (w_d, p_d, c_d, w_s, p_s, c_s, n_sr), cost
 
         def system(w_d, p_d, w_s, p_s):
             """a_d w_d + a_s w_s on the words of the system, [4 .. 93], each term divided by its pixel count and truncation; the rest 0"""
@@ -738,7 +760,7 @@ class BundleRefiner(_DrawsEveryLink):
 
         def propose(state, held, lam):
             pose, off, q = state
-            w_d, p_d, _, w_s, p_s, _ = held
+            w_d, p_d, _, w_s, p_s, _, _ = held
             words = system(w_d, p_d, w_s, p_s) if outline else w_d      # depth alone: the kernel's words as they came
             if frame_mode:
                 dq, dc = schur_step(words, self.active_j, self.active_c, lam)
@@ -747,7 +769,7 @@ class BundleRefiner(_DrawsEveryLink):
             t_off = off + d[:6]
             return pose + d[6:], t_off, np.clip(q0 + t_off, lo, hi)
 
-        (pose, off, q), (w_d, p_d, c_d, w_s, p_s, c_s), first, steps = _levenberg_loop(evaluate, propose, (pose, np.zeros(6), q0.copy()),
+        (pose, off, q), (w_d, p_d, c_d, w_s, p_s, c_s, n_sr), first, steps = _levenberg_loop(evaluate, propose, (pose, np.zeros(6), q0.copy()),
                                                                                      self.iterations, self.damping)
         words, pooled = w_d, p_d
         if outline:
@@ -770,7 +792,9 @@ class BundleRefiner(_DrawsEveryLink):
         sj, sp = schur_sigma(words, self.active_j, self.active_c) if frame_mode else np.split(bundle_columns_sigma(pooled, slots), 2)
         return self._result(pose, q, off, sp, sj, first[2], c_d, steps, 0.0 if p_d is None else float(p_d[2]),
                             np.full(N, np.nan) if w_d is None else mean_cost(w_d[:, :NEQ_WORDS]),
-                            *((first[5], c_s, float(p_s[2])) if outline else ()), **({} if scale is None else {'robust_scale': float(scale)}))
+                            *((first[5], c_s, float(p_s[2]) if n_sr is None else n_sr[0]) if outline else ()),
+                            **({} if scale is None else {'robust_scale': float(scale)}),
+                            **({} if n_sr is None else {'inliers_silhouette_reverse': n_sr[1]}))
 
     def _refine_native(self, pose: np.ndarray, q0: np.ndarray, depth_t) -> BundleRefineResult:
         """refine through rope_refine_bundle: ONE call, because one system spans all frames — a batch whose scratch one call does
